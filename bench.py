@@ -6,6 +6,7 @@ weights of the named architecture.
     python bench.py --gpus 1 --steps 5 --warmup 2
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR    # + the last timed step's top-1 labels as DIR/top1.npy
 
 One step = one pass of the hot path over one batch of B=1024 pre-processed query images per GPU
 (the reference's loader batch, main.py:505): prototype reduction from the (rank-sharded) 16 000-row
@@ -451,6 +452,8 @@ def self_launch(args):
            "--master-port", str(port), os.path.abspath(__file__), "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup)]
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", args.dump_outputs]
     raise SystemExit(subprocess.run(cmd, env=env).returncode)
 
 
@@ -482,8 +485,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the un-timed side measurements of the `extra` block")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the top-1 class of every query) as DIR/<name>.npy, float64")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_worker:
         return cpu_worker(args)
     return run(args, HipHooks)
@@ -533,10 +540,15 @@ def run(args, hooks, out=None):
     t0 = time.perf_counter()
     for i in range(args.steps):
         if evs: evs[i].record()
-        step(st)
+        last = step(st)
     if evs: evs[args.steps].record()
     barrier()
     dt = time.perf_counter() - t0
+    dump_dir = getattr(args, "dump_outputs", None)
+    if dump_dir:
+        # the last timed step's result, copied out before anything else runs a step; every rank writes its own queries
+        os.makedirs(dump_dir, exist_ok=True)
+        np.save(os.path.join(dump_dir, "top1.npy" if world == 1 else f"top1_rank{rank}.npy"), last.cpu().numpy().astype(np.float64))
     step_ms = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)) if evs else []
     pct = lambda q: step_ms[min(len(step_ms) - 1, int(round(q * (len(step_ms) - 1))))] if step_ms else None
     if launched:

@@ -8,7 +8,8 @@ fixtures hold input seeds/shapes and the reference's OUTPUT tensors only.
     python tests/golden/make_golden.py C2 tiny    # a subset
 
 Inputs are regenerated in the tests from proto_clip_amd.synth / clip.model.random_state_dict with the
-same seeds, so they are not stored (except the small random adapter state dicts).
+same seeds, so they are not stored (except the small random adapter state dicts and the weights of the two adapter
+checkpoints the reference ships).
 """
 import io
 import os
@@ -357,6 +358,15 @@ def make_shipped(ref_model):
         tb = torch.load(os.path.join(REF, "pretrained_ckpt", sub, "memory_bank_t.pt"), map_location="cpu").detach()
         zt = tb / tb.norm(dim=-1, keepdim=True)                                             # main.py:404-405 on the real bank
         savez("shipped_" + tag, y=y, text_rows_head=tb[:32], text_proto_head=zt[:32], n_text=np.array(tb.shape))
+    make_shipped_weights()
+
+
+def make_shipped_weights():
+    """The two shipped adapter checkpoints themselves (weights only, key order kept: conftest.adapter_sd reads them back), so
+    that the tests that load them need nothing outside the repository."""
+    for tag, sub in (("imagenetF", "imagenet-F"), ("fewsol198F", "fewsol-198-F")):
+        sd = torch.load(os.path.join(REF, "pretrained_ckpt", sub, "query_adapter.pt"), map_location="cpu")
+        savez(f"shipped_{tag}_adapter", adapter_keys=np.array(list(sd.keys())), **{"adapter__" + k: v for k, v in sd.items()})
 
 
 # ---------------------------------------------------------------- encoders --------------------------

@@ -5,6 +5,7 @@ payload layout, the rank-order combine and that every rank ends with identical p
 import os
 import sys
 
+import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
@@ -234,7 +235,8 @@ def _bench_main_worker(rank, world, port, outdir):
     CpuHooks.build_state, CpuHooks.step, CpuHooks.self_check = staticmethod(build_state), staticmethod(step), staticmethod(self_check)
 
     buf = io.StringIO()
-    args = argparse.Namespace(gpus=world, steps=3, warmup=1, no_cpu_baseline=True, no_extra=True, cpu_worker=None)
+    args = argparse.Namespace(gpus=world, steps=3, warmup=1, no_cpu_baseline=True, no_extra=True, cpu_worker=None,
+                              dump_outputs=os.path.join(outdir, "dump"))
     bench.run(args, CpuHooks, out=buf)
     assert calls["build"] == 1 and calls["check"] == 1 and calls["step"] == 1 + 3 + 2       # warm-up + timed + the self-check's two
     with open(os.path.join(outdir, f"out{rank}.txt"), "w") as f:
@@ -254,3 +256,7 @@ def test_bench_main_plumbing_two_ranks(tmp_path):
     # value = the units ALL ranks processed / the slowest rank's time
     assert abs(line["value"] - 3 * 12 * 2 / (line["ms_per_step"] * 3 / 1e3)) < 1e-6 * line["value"]
     assert "cpu_baseline" not in line and "extra" not in line
+    # --dump-outputs: every rank's top-1 labels of its last timed step
+    for r in range(2):
+        top1 = np.load(tmp_path / "dump" / f"top1_rank{r}.npy")
+        assert top1.shape == (12,) and top1.dtype == np.float64 and np.all((top1 >= 0) & (top1 < 9) & (top1 == np.round(top1)))

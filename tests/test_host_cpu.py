@@ -229,10 +229,9 @@ def test_model_surface_and_state_dict_names():
     assert {k: tuple(v.shape) for k, v in f.items()} == {"fc.0.weight": (192, 768), "fc.1.weight": (192,), "fc.1.bias": (192,),
                                                          "fc.2.weight": (768, 192), "fc.3.weight": (768,), "fc.3.bias": (768,)}
     assert Adapter(512, "conv-3x").bn1.weight.shape == (16, 23, 23) and Adapter(768, "conv-3x").bn3.weight.shape == (1, 28, 28)
-    ck = "/root/reference/pretrained_ckpt/imagenet-F/query_adapter.pt"
-    if os.path.exists(ck):                       # the shipped checkpoints load unchanged
-        a.load_state_dict(torch.load(ck, map_location="cpu"))
-        Adapter_FC(768, dtype=torch.half).load_state_dict(torch.load(ck.replace("imagenet-F", "fewsol-198-F"), map_location="cpu"))
+    from conftest import adapter_sd              # the shipped checkpoints (tests/golden/shipped_*_adapter.npz) load unchanged
+    a.load_state_dict(adapter_sd(golden("shipped_imagenetF_adapter")))
+    Adapter_FC(768, dtype=torch.half).load_state_dict(adapter_sd(golden("shipped_fewsol198F_adapter")))
     sd = random_state_dict(seed=11, **TINY)
     m = build_model({k: v.clone() for k, v in sd.items()})
     assert set(m.state_dict()) == set(sd)

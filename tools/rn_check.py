@@ -1,5 +1,5 @@
 import os, sys, time, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from proto_clip_amd.clip.model import BACKBONES, build_model, random_state_dict
 for name, B in (("RN50", 256), ("RN101", 256), ("RN50", 256)):
     kw = BACKBONES[name]
