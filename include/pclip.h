@@ -106,7 +106,9 @@ int pclip_fuse_probs(const float* d2i, const float* d2t, int Q, int N, int ldd, 
                      float one_minus_alpha, float beta, float* p, int32_t* argmax, float* topk_p,
                      int32_t* topk_i, int k, pclip_stream_t stream);
 
-/* Convenience: pclip_sqdist_f16 + pclip_fuse_probs with the distance rows held in `ws`. */
+/* Convenience: pclip_sqdist_f16 + pclip_fuse_probs with the distance rows held in `ws` (or one of the one-launch routes, pclip_classify_route).  N <= 4096 on every
+ * route (PCLIP_E_INVALID beyond).  Pass ws_bytes = pclip_workspace_bytes(PCLIP_OP_CLASSIFY, Q, N, D) — that size, not a larger buffer's, keeps the route a function of the
+ * shape and the routing settings, the one pclip_classify_route reports (the fused row panels run only if their scratch fits in ws_bytes). */
 int pclip_classify_f16(const void* q, const void* zi, const void* zt, int Q, int N, int D,
                        const float* q_sq, const float* zi_sq, const float* zt_sq, float alpha,
                        float one_minus_alpha, float beta, float* p, int32_t* argmax, float* topk_p,
@@ -445,6 +447,8 @@ int pclip_preprocess_u8(const void* const* srcs, const int32_t* desc, int B, int
                         float mean2, float std0, float std1, float std2, void* out, int out_f16, void* ws, pclip_stream_t stream);
 
 /* ---- workspace sizing -------------------------------------------------------------------- */
+/* PCLIP_OP_CLASSIFY: the two-stage distance rows (the least pclip_classify_f16 accepts), or the fused row panels' scratch where that is larger and the routing may
+ * send the shape there (forced routing at small Q) — so depends on pclip_classify_panel_config as well as on the shape. */
 #define PCLIP_OP_SQDIST 1
 #define PCLIP_OP_CLASSIFY 2
 #define PCLIP_OP_ADAPTER_FC 3

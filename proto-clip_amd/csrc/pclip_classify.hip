@@ -271,6 +271,16 @@ __device__ __forceinline__ void load_row(const float* __restrict__ row, int N, i
     }
 }
 
+// A product rounded to fp32 that the compiler cannot merge into a following addition: __fmul_rn is a plain `*` to hipcc, and under -ffp-contract=fast (which
+// ignores `#pragma clang fp contract`) it fused `beta * (-d) - max` into one fma for every unrolled element but the last register slot — the class of that slot
+// (N = 1000: 960 .. 999; N = 4096: 4032 .. 4095) got p one ulp away from a class with the same distances, and an exact tie went to the higher class
+// (tests/test_gpu_envelope.py::test_duplicate_prototypes_across_far_tiles).  torch rounds the product and the sum separately.
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+    float r = a * b;
+    asm("" : "+v"(r));
+    return r;
+}
+
 // e[i] = exp(beta*(-d_i) - max_n beta*(-d_n)) for valid classes (0 for padding); returns the wave-wide
 // sum.  Rounding is monotone, so the max is beta*(-dmin) for beta >= 0 and beta*(-dmax) otherwise.
 template <int NV>
@@ -280,7 +290,7 @@ __device__ __forceinline__ float softmax_terms(const float (&d)[NV], float beta,
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-        e[i] = (i * 64 + lane < N) ? expf(__fsub_rn(__fmul_rn(beta, -d[i]), mx)) : 0.f;
+        e[i] = (i * 64 + lane < N) ? expf(__fsub_rn(mul_rounded(beta, -d[i]), mx)) : 0.f;
         s += e[i];
     }
     return wave_sum(s);
@@ -320,8 +330,8 @@ __global__ __launch_bounds__(256) void fuse_probs_kernel(const float* __restrict
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int n = i * 64 + lane;
-            float pv = __fmul_rn(alpha, __fdiv_rn(ei[i], li));
-            if (d2t) pv = __fadd_rn(pv, __fmul_rn(oma, __fdiv_rn(et[i], lt)));
+            float pv = mul_rounded(alpha, __fdiv_rn(ei[i], li));
+            if (d2t) pv = __fadd_rn(pv, mul_rounded(oma, __fdiv_rn(et[i], lt)));
             ei[i] = pv;   // reuse as p
             if (n < N) {
                 if (p) p[(size_t)row * N + n] = pv;
@@ -390,7 +400,7 @@ __global__ __launch_bounds__(256) void hp_sweep_kernel(const float* __restrict__
 #pragma unroll
                 for (int i = 0; i < NV; ++i) {
                     const int n = i * 64 + lane;
-                    const float pv = __fadd_rn(__fmul_rn(a, ei[i]), __fmul_rn(oma, et[i]));
+                    const float pv = __fadd_rn(mul_rounded(a, ei[i]), mul_rounded(oma, et[i]));
                     if (n < N && pv > best) { best = pv; besti = n; }
                 }
                 wave_argmax(best, besti);
@@ -440,6 +450,8 @@ inline SqWs carve_sq(void* ws, int Q, int N) {
     return w;
 }
 inline int padded_ld(int N) { return (N + 63) / 64 * 64; }
+// what every route of pclip_classify_f16 can work in: the norms and the two stages' distance rows
+inline size_t classify_rows_bytes(int Q, int N) { return carve_sq(nullptr, Q, N).bytes + 2 * align_up((size_t)Q * padded_ld(N) * 4, 256); }
 
 }  // namespace
 
@@ -452,12 +464,22 @@ inline int padded_ld(int N) { return (N + 63) / 64 * 64; }
     } while (0)
 
 extern "C" size_t pclip_workspace_bytes(int op, int Q, int N, int D) {
-    (void)D;
     if (Q < 0 || N < 0) return 0;
     size_t sq = carve_sq(nullptr, Q, N).bytes;
     switch (op) {
         case PCLIP_OP_SQDIST: return sq;
-        case PCLIP_OP_CLASSIFY: return sq + 2 * align_up((size_t)Q * padded_ld(N) * 4, 256);
+        case PCLIP_OP_CLASSIFY: {
+            const size_t rows = classify_rows_bytes(Q, N);
+            // A shape the routing may hand to the fused row panels also gets their scratch (interleaved banks, candidate records), so that a caller passing this
+            // size gets the route of the shape and the routing settings, never one that depends on how large a buffer it happens to hold.  The default routing sends
+            // only large Q there, where the distance rows are the larger by far; forced routing (pclip_classify_panel_config(2)) at small Q is what pays for the max.
+            // (pclip_classify_f16 itself requires the rows only: with less than the panels' scratch it takes the two stages.)
+            if (pclip_classify_panel_applies(Q, N, D, 0.5f, 0.5f, 1.f)) {
+                const size_t panel = sq + pclip_classify_panel_workspace(Q, N, D);
+                return panel > rows ? panel : rows;
+            }
+            return rows;
+        }
         case PCLIP_OP_ADAPTER_FC: {
             // h1 [Q, D/4] fp16, h1n [Q, D/4] fp16, h2 [Q, D] fp16  (N is the hidden width here)
             return 2 * align_up((size_t)Q * N * 2, 256) + align_up((size_t)Q * D * 2, 256);
@@ -546,7 +568,8 @@ extern "C" int pclip_classify_f16(const void* q, const void* zi, const void* zt,
                                   float one_minus_alpha, float beta, float* p, int32_t* argmax, float* topk_p,
                                   int32_t* topk_i, int k, void* ws, size_t ws_bytes, pclip_stream_t stream) {
     PCLIP_REQUIRE(ws != nullptr, "pclip_classify_f16: workspace required");
-    const size_t need = pclip_workspace_bytes(PCLIP_OP_CLASSIFY, Q, N, D);
+    PCLIP_REQUIRE(N <= 4096, "pclip_classify_f16: N=%d classes (<= 4096: the fusion kernels hold a class row in registers, the row panels walk 32 class tiles)", N);
+    const size_t need = classify_rows_bytes(Q, N);
     if (ws_bytes < need) { pclip_set_error("pclip_classify_f16: workspace %zu < %zu", ws_bytes, need); return PCLIP_E_WORKSPACE; }
     if (Q == 0) return PCLIP_OK;
     // mid-sized class counts (32 < N <= 256; tests / probes: any N <= 256), p and / or argmax: one launch, norms in-kernel (pclip_classify_mid.hip).  PCLIP_CLASSIFY_MID=0: off.
@@ -608,7 +631,8 @@ extern "C" int pclip_classify_route(int Q, int N, int D, float alpha, float one_
 extern "C" int pclip_classify_panel_dump_f16(const void* q, const void* zi, const void* zt, int Q, int N, int D, float* dump, int exact, void* ws, size_t ws_bytes,
                                              pclip_stream_t stream) {
     PCLIP_REQUIRE(q && zi && zt && dump && ws, "pclip_classify_panel_dump_f16: null pointer");
-    PCLIP_REQUIRE(N > 32 && D >= 128 && D % 64 == 0 && D <= 4096 && Q >= 1, "pclip_classify_panel_dump_f16: shape outside the fused kernel");
+    PCLIP_REQUIRE(N > 32 && N <= 4096 && D >= 128 && D % 64 == 0 && D <= 4096 && Q >= 1,
+                  "pclip_classify_panel_dump_f16: shape Q=%d N=%d (<= 4096) D=%d outside the fused kernel", Q, N, D);
     SqWs w = carve_sq(ws, Q, N);
     if (ws_bytes < w.bytes + pclip_classify_panel_workspace(Q, N, D)) { pclip_set_error("pclip_classify_panel_dump_f16: workspace too small"); return PCLIP_E_WORKSPACE; }
     int e;

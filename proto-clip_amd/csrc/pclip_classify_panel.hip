@@ -412,7 +412,8 @@ bool pclip_classify_panel_applies(int Q, int N, int D, float alpha, float one_mi
     // the candidate proof bounds a class through p's monotonicity in both distances: both mixing weights and beta must be non-negative (a user's --alpha outside
     // [0, 1] takes the two stages)
     const bool monotone = alpha >= 0.f && one_minus_alpha >= 0.f && beta >= 0.f;
-    return g_panel_mode > 0 && enough && monotone && N > 32 && D >= 128 && D % 64 == 0 && D <= 4096 && Q >= 1 && (long)256 * D * 2 < 0x7fffffffL;
+    // N <= 4096: at most 32 class tiles of 128 — the kernel walks its tiles through a 32-bit mask (pclip_classify_f16 refuses a larger N on every route)
+    return g_panel_mode > 0 && enough && monotone && N > 32 && N <= 4096 && D >= 128 && D % 64 == 0 && D <= 4096 && Q >= 1 && (long)256 * D * 2 < 0x7fffffffL;
 }
 
 // q_sq / zi_sq / zt_sq: device arrays or null (computed by the preparation launch with pclip_row_sqnorm_f16's arithmetic).  dump != nullptr: test mode (distances of panel 0 / tile 0, no argmax; dump_exact:

@@ -199,11 +199,14 @@ def classify(q, zi, zt, alpha: float, beta: float, want_p=False, want_argmax=Tru
     am = torch.empty(Q, dtype=torch.int32, device=dev) if want_argmax else None
     tp = torch.empty(Q, topk, dtype=torch.float32, device=dev) if topk else None
     ti = torch.empty(Q, topk, dtype=torch.int32, device=dev) if topk else None
-    ws = _workspace(_lib.workspace_bytes(_lib.OP_CLASSIFY, Q, N, D), dev)
+    # the library is told this shape's own workspace size, not the cached buffer's (which grows with whatever ran before on the stream): the route it
+    # takes — the fused row panels only if their scratch fits in that size — is then a function of the shape alone, the one `classify_route` reports
+    nws = _lib.workspace_bytes(_lib.OP_CLASSIFY, Q, N, D)
+    ws = _workspace(nws, dev)
     a32, oma32 = float(np.float32(alpha)), float(np.float32(1 - float(alpha)))
     check(_lib.load().pclip_classify_f16(ptr(q), ptr(zi), ptr(zt), Q, N, D, ptr(q_sq), ptr(zi_sq), ptr(zt_sq), a32,
                                          oma32, float(np.float32(beta)), ptr(p), ptr(am), ptr(tp), ptr(ti), topk,
-                                         ptr(ws), ws.numel(), stream()), "pclip_classify_f16")
+                                         ptr(ws), nws, stream()), "pclip_classify_f16")
     return p, am, tp, ti
 
 

@@ -29,7 +29,7 @@ def dev(t):
 
 
 # ---------------------------------------------------------------- row reductions -------------------
-@pytest.mark.parametrize("R,D", [(1, 512), (5, 64), (1000, 512), (333, 768), (4097, 1024), (7, 2048)])
+@pytest.mark.parametrize("R,D", [(1, 512), (5, 64), (1000, 512), (333, 768), (4097, 1024), (7, 2048), (65, 4096)])
 def test_l2norm_rows(ops, R, D):
     x = torch.from_numpy(synth.normal((R, D), 3, 0)).half() * 3
     y, sq = ops.l2norm_rows(dev(x), want_sq=True)
@@ -49,7 +49,7 @@ def test_l2norm_inplace_and_empty(ops):
     assert e.shape == (0, 512)
 
 
-@pytest.mark.parametrize("N,K,D", [(10, 16, 512), (100, 1, 1024), (198, 16, 768), (1000, 16, 512), (37, 3, 512), (5, 7, 64)])
+@pytest.mark.parametrize("N,K,D", [(10, 16, 512), (100, 1, 1024), (198, 16, 768), (1000, 16, 512), (37, 3, 512), (5, 7, 64), (300, 32, 512), (16, 32, 4096)])
 @pytest.mark.parametrize("per_shot", [True, False])
 def test_proto_build(ops, N, K, D, per_shot):
     mem = (torch.from_numpy(synth.normal((N * K, D), 5, 1)).float() * 0.7).half()

@@ -69,7 +69,8 @@ def test_colsum_and_addscaled(ops):
     assert rel_l2(got, c + 2.0 * rs[:, None] * x) < 1e-6
 
 
-@pytest.mark.parametrize("Q,N,D,alpha,beta", [(50, 12, 64, 0.4, 6.0), (333, 198, 96, 0.2, 12.0), (64, 1000, 32, 1.0, 0.7), (40, 70, 48, 0.0, 3.0)])
+@pytest.mark.parametrize("Q,N,D,alpha,beta", [(50, 12, 64, 0.4, 6.0), (333, 198, 96, 0.2, 12.0), (64, 1000, 32, 1.0, 0.7), (40, 70, 48, 0.0, 3.0),
+                                                  (70, 4096, 64, 0.5, 12.0)])
 def test_nll_grad_and_cdist_backward(ops, Q, N, D, alpha, beta):
     g = torch.Generator().manual_seed(Q + N)
     zq = F.normalize(torch.randn(Q, D, generator=g), dim=-1).requires_grad_()
@@ -121,7 +122,8 @@ def test_info_nce_pieces(ops):
 
 
 @pytest.mark.parametrize("N,K,D,per_shot,final", [(12, 8, 256, True, True), (37, 1, 100, False, True), (20, 1, 144, True, False),
-                                                   (5, 16, 512, True, True), (9, 4, 70, True, True)])
+                                                   (5, 16, 512, True, True), (9, 4, 70, True, True),
+                                                   (40, 32, 2048, True, True), (8, 32, 3072, True, False)])     # the kernel's limits: K <= 32, D <= 3072
 def test_proto_backward(ops, N, K, D, per_shot, final):
     g = torch.Generator().manual_seed(N * K + D)
     mem = (torch.randn(N * K, D, generator=g) * 0.7).half().requires_grad_()
@@ -137,7 +139,7 @@ def test_proto_backward(ops, N, K, D, per_shot, final):
     assert_grad_close(got, mem.grad, "proto_backward")
 
 
-@pytest.mark.parametrize("R,D,scale", [(100, 64, 1.0), (333, 256, 0.2), (17, 192, 1.0), (1000, 768, 0.2), (5, 1024, 1.0)])
+@pytest.mark.parametrize("R,D,scale", [(100, 64, 1.0), (333, 256, 0.2), (17, 192, 1.0), (1000, 768, 0.2), (5, 1024, 1.0), (70, 2048, 0.2)])
 def test_layernorm_backward(ops, R, D, scale):
     g = torch.Generator().manual_seed(R + D)
     x = (torch.randn(R, D, generator=g) * 1.5 + 0.2).half().requires_grad_()
