@@ -279,7 +279,7 @@ int pclip_add_layernorm_f16(const void* x, const void* delta, int ld, void* x_ou
 /* Multi-head self-attention core on a fused QKV buffer (nn.MultiheadAttention inside
  * ResidualAttentionBlock.attention, clip/model.py:183-185): qkv [B, L, 3*H*dh] fp16 (q|k|v blocks,
  * heads contiguous inside each) -> out [B, L, H*dh] fp16 = softmax(q k^T / sqrt(dh) [+causal]) v.
- * dh must be 64; L <= 288. */
+ * dh must be 64; L <= 288 (longer non-causal sequences: pclip_attention_long_q_f16). */
 int pclip_attention_f16(const void* qkv, void* out, int B, int L, int H, int dh, int causal,
                         pclip_stream_t stream);
 
@@ -288,6 +288,13 @@ int pclip_attention_f16(const void* qkv, void* out, int B, int L, int H, int dh,
  * Lq < L serves the last vision block, whose output is only read at the class token (clip/model.py:233); causal needs Lq == L. */
 int pclip_attention_q_f16(const void* q, int ldq, long q_batch_stride, const void* kv, int ldkv, int k_off, int v_off, void* out,
                           int B, int L, int Lq, int H, int dh, int causal, pclip_stream_t stream);
+
+/* The same operands and layout as pclip_attention_q_f16 for long NON-causal sequences: 1 <= Lq <= L <= 4096 (ViT-L/14@336px: 577
+ * tokens; pclip_attention_q_f16 stops at 288).  K / V are streamed through LDS 128 keys at a time.  For 128 < L <= 288 the result
+ * equals pclip_attention_q_f16's bit for bit, and a query row's result does not depend on Lq.  Refuses causal != 0, dh != 64,
+ * strides / offsets that are not multiples of 8 halves, and rows that cannot hold H heads at k_off / v_off. */
+int pclip_attention_long_q_f16(const void* q, int ldq, long q_batch_stride, const void* kv, int ldkv, int k_off, int v_off, void* out,
+                               int B, int L, int Lq, int H, int dh, int causal, pclip_stream_t stream);
 
 /* Kernel choice behind the two attention entry points (same results bit for bit either way): mode -1 / 0 = one workgroup per
  * (image, head) pair (default); 1 = where its shape conditions hold (Lq == L, L <= 256), the persistent kernel that prefetches the

@@ -71,6 +71,7 @@ _SIGS = {
     "pclip_add_layernorm_f16": [_P, _P, c_int, _P, _P, _P, c_float, _P, c_int, c_int, _P],
     "pclip_attention_f16": [_P, _P, c_int, c_int, c_int, c_int, c_int, _P],
     "pclip_attention_q_f16": [_P, c_int, c_long, _P, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P],
+    "pclip_attention_long_q_f16": [_P, c_int, c_long, _P, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P],
     "pclip_attention_config": [c_int, c_int],
     "pclip_im2col_patches_f16": [_P, c_int, c_int, c_int, _P, c_int, _P],
     "pclip_im2col_patches_f32": [_P, c_int, c_int, c_int, _P, c_int, _P],

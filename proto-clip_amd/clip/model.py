@@ -490,6 +490,9 @@ BACKBONES = {
                   context_length=77, vocab_size=49408, transformer_width=512, transformer_heads=8, transformer_layers=12),
     "ViT-L/14": dict(embed_dim=768, image_resolution=224, vision_layers=24, vision_width=1024, vision_patch_size=14,
                      context_length=77, vocab_size=49408, transformer_width=768, transformer_heads=12, transformer_layers=12),
+    # OpenAI's ViT-L-14-336px.pt (not in the reference's download list: load it by path; 24 x 24 patches + 1 = 577 tokens)
+    "ViT-L/14@336px": dict(embed_dim=768, image_resolution=336, vision_layers=24, vision_width=1024, vision_patch_size=14,
+                           context_length=77, vocab_size=49408, transformer_width=768, transformer_heads=12, transformer_layers=12),
 }
 
 

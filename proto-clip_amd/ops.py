@@ -580,11 +580,20 @@ def add_layernorm(x, delta, gamma, beta, eps: float = 1e-5, out=None, update_x: 
     return out
 
 
+ATT_SHORT_MAX_L = 288      # pclip_attention_f16 / _q_f16 keep K / V resident in LDS up to here; pclip_attention_long_q_f16 streams them (non-causal, L <= 4096)
+
+
 def attention(qkv, B: int, L: int, H: int, causal: bool = False, out=None):
+    """softmax(q k^T / 8) v per head on a fused QKV buffer [B*L, 3W].  The kernel follows L alone: L <= 288 the resident-K/V
+    kernels, longer (non-causal) sequences the streamed one — bit-identical to each other where both apply."""
     require_cuda(qkv)
     W = H * 64
     if out is None:
         out = torch.empty(B * L, W, dtype=torch.float16, device=qkv.device)
+    if L > ATT_SHORT_MAX_L:
+        check(_lib.load().pclip_attention_long_q_f16(ptr(qkv), 3 * W, L * 3 * W, ptr(qkv), 3 * W, W, 2 * W, ptr(out), B, L, L, H, 64,
+                                                     int(causal), stream()), "pclip_attention_long_q_f16")
+        return out
     check(_lib.load().pclip_attention_f16(ptr(qkv), ptr(out), B, L, H, 64, int(causal), stream()),
           "pclip_attention_f16")
     return out
@@ -592,12 +601,12 @@ def attention(qkv, B: int, L: int, H: int, causal: bool = False, out=None):
 
 def attention_first_queries(q, kv, B: int, L: int, Lq: int, H: int):
     """Attention output of the first Lq tokens only: q [B*Lq, W] (projected queries of those tokens), kv [B*L, 2W] (keys |
-    values of every token).  Same arithmetic per query row as `attention`."""
+    values of every token).  Same arithmetic per query row as `attention`, and the same kernel choice (by L alone)."""
     require_cuda(q, kv)
     W = H * 64
     out = torch.empty(B * Lq, W, dtype=torch.float16, device=q.device)
-    check(_lib.load().pclip_attention_q_f16(ptr(q), W, Lq * W, ptr(kv), 2 * W, 0, W, ptr(out), B, L, Lq, H, 64, 0, stream()),
-          "pclip_attention_q_f16")
+    fn = "pclip_attention_long_q_f16" if L > ATT_SHORT_MAX_L else "pclip_attention_q_f16"
+    check(getattr(_lib.load(), fn)(ptr(q), W, Lq * W, ptr(kv), 2 * W, 0, W, ptr(out), B, L, Lq, H, 64, 0, stream()), fn)
     return out
 
 
