@@ -184,7 +184,8 @@ int pclip_adapter_conv_f16(const void* x, int B, int D, int three_x, const void*
  *   bias (nullable, fp16 [N]) is added before rounding (nn.Linear, clip/model.py:176-178);
  *   act: 0 none, 1 QuickGELU x*sigmoid(1.702x) (clip/model.py:164-166) with per-op fp16 rounding;
  *   residual (nullable, fp16 [M,N], ldc): out = r16(residual + r16(...)) (clip/model.py:188-189).
- * lda/ldb/ldc in elements.  K % 64 == 0 required.  Calls with no more 128x64 output tiles than the device has CUs (a serving request, the class-token tail) run a latency-oriented kernel with the same arithmetic (bit-identical results). */
+ * lda/ldb/ldc in elements.  K % 8 == 0 required (K % 64 != 0 runs K-tail instantiations of the same kernels: no element at a column >= K of A or B is read;
+ * with N % 8 == 0 they also take N ragged against the tile).  K % 64 == 0 runs the same kernels as before that relaxation.  Calls with no more 128x64 output tiles than the device has CUs (a serving request, the class-token tail) run a latency-oriented kernel with the same arithmetic (bit-identical results). */
 int pclip_gemm_f16(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
                    const void* bias, int act, const void* residual, pclip_stream_t stream);
 
@@ -223,13 +224,13 @@ int pclip_gemm_splitk_f16(const void* A, int lda, const void* B, int ldb, void* 
 
 /* Convolution-as-GEMM with the eval-mode BatchNorm (+ReLU) that follows it in the ModifiedResNet tower (clip/model.py:43-52,
  * 138-142): C = relu?( r16( r16(A B^T) * scale[n] + shift[n] ) ), scale/shift fp32 [N] = the folded running statistics and
- * affine.  Same rounding points as conv (fp16 tensor) followed by pclip_bn_act_f16. */
+ * affine.  Same rounding points as conv (fp16 tensor) followed by pclip_bn_act_f16.  K % 8 == 0 (as pclip_gemm_f16). */
 int pclip_gemm_bn_f16(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
                       const float* scale, const float* shift, int relu, pclip_stream_t stream);
 
 /* conv3 + bn3 + `out += identity` + ReLU of a bottleneck (clip/model.py:49-52) in one launch:
  * C = relu( r16( r16( r16(A B^T) * scale[n] + shift[n] ) + residual ) ), residual fp16 [M, N] with the row stride ldc of C.
- * Identical to pclip_gemm_f16 followed by pclip_bn_act_f16(residual, relu).  N % 64 == 0, K % 64 == 0, 16-byte aligned operands
+ * Identical to pclip_gemm_f16 followed by pclip_bn_act_f16(residual, relu).  N % 64 == 0, K % 8 == 0, 16-byte aligned operands
  * (PCLIP_E_INVALID otherwise: use the two calls). */
 int pclip_gemm_bn_res_f16(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
                           const float* scale, const float* shift, const void* residual, pclip_stream_t stream);
@@ -237,8 +238,9 @@ int pclip_gemm_bn_res_f16(const void* A, int lda, const void* B, int ldb, void* 
 /* 3x3 convolution, stride 1, padding 1, on NHWC fp16 activations x [B, H, W, Cin] + eval BatchNorm (+ReLU), as an implicit
  * GEMM: the im2col matrix is never materialised (each K-tile is gathered by buffer LDS-DMA; taps outside the image are out-of-range
  * offsets, i.e. zeros — `zero_line`, >= 128 zero bytes in device memory, is still required non-null for ABI stability but no longer read).  w [Cout, 3, 3, Cin] fp16; y [B*H*W, Cout].
- * Cin % 64 == 0, or Cin = 8 / 16 / 32 (the stem, clip/model.py:138-142) with every row of w zero-padded to a multiple of 64
- * halves; Cout % 64 == 0, or Cout = 32.  Identical to pclip_im2col3x3_f16 + pclip_gemm_bn_f16 (clip/model.py:20-22, 45-46). */
+ * Cin % 8 == 0 and Cout % 8 == 0; every row of w is zero-padded to round_up(9 Cin, 64) halves.  Cin outside {8, 16, 32, 64k} or Cout outside
+ * {32, 64k} (RN50x4 / RN50x16: 40, 48, 80, 96, 160) run tail instantiations (per-chunk tap gather; columns >= Cout never stored, scale / shift
+ * beyond Cout never read).  Identical to pclip_im2col3x3_f16 + pclip_gemm_bn_f16 (clip/model.py:20-22, 45-46) on the 16x16x32 kernels. */
 int pclip_conv3x3_bn_f16(const void* x, const void* w, const void* zero_line, int B, int H, int W, int Cin, int Cout,
                          const float* scale, const float* shift, int relu, void* y, pclip_stream_t stream);
 

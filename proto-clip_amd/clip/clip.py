@@ -13,9 +13,13 @@ from .._lib import PclipError
 from .model import BACKBONES, build_model, random_state_dict
 
 _FILES = {"RN50": "RN50.pt", "RN101": "RN101.pt", "ViT-B/32": "ViT-B-32.pt", "ViT-B/16": "ViT-B-16.pt", "ViT-L/14": "ViT-L-14.pt"}
+# names `load` also accepts by name (the reference's file names for them); `available_models()` keeps listing the five above
+_MORE_FILES = {"RN50x4": "RN50x4.pt", "RN50x16": "RN50x16.pt"}
 
 
 def available_models() -> List[str]:
+    """The five backbones listed since the first release.  `load` also accepts "RN50x4" and "RN50x16" by name (checkpoints
+    RN50x4.pt / RN50x16.pt in `download_root`), and every `BACKBONES` name as "random:<name>"."""
     return list(_FILES)
 
 
@@ -36,8 +40,8 @@ def load(name: str, device: Union[str, torch.device] = "cuda", jit: bool = False
         if backbone not in BACKBONES:
             raise RuntimeError(f"Model {backbone} not found; available models = {available_models()}")
         sd = random_state_dict(seed=1, **BACKBONES[backbone])
-    elif name in _FILES:
-        path = os.path.join(download_root or os.path.expanduser("~/.cache/clip"), _FILES[name])
+    elif name in _FILES or name in _MORE_FILES:
+        path = os.path.join(download_root or os.path.expanduser("~/.cache/clip"), _FILES.get(name) or _MORE_FILES[name])
         if not os.path.isfile(path):
             raise RuntimeError(f"checkpoint {path} not found and downloading is disabled (no network); "
                                f"place the OpenAI checkpoint there or pass a path")

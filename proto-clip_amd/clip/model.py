@@ -9,9 +9,9 @@ fused bias/QuickGELU/residual epilogues, fp32-statistics LayerNorm, whole-sequen
 
 Precision follows `convert_weights` (clip/model.py:373-394): Linear/conv/projection weights fp16,
 LayerNorm and embedding parameters fp32, activations fp16 with fp32 accumulation.
-Both vision towers are built: VisionTransformer (ViT-B/32, ViT-B/16, ViT-L/14) and ModifiedResNet (RN50 /
-RN101: NHWC activations, 1x1 convs as GEMMs and 3x3 convs as implicit GEMMs with the eval BatchNorm (+ReLU) in their
-epilogue; im2col + GEMM only for the strided 3-channel first convolution of the stem)."""
+Both vision towers are built: VisionTransformer (ViT-B/32, ViT-B/16, ViT-L/14) and ModifiedResNet (RN50 / RN101 /
+RN50x4 / RN50x16: NHWC activations, 1x1 convs as GEMMs and 3x3 convs as implicit GEMMs with the eval BatchNorm (+ReLU) in
+their epilogue; im2col + GEMM only for the strided 3-channel first convolution of the stem)."""
 import os
 from collections import OrderedDict
 
@@ -252,8 +252,10 @@ class _Bottleneck(_Box):
 
 class ModifiedResNet(nn.Module):
     """clip/model.py:95-152 on the gfx950 kernels.  Activations are NHWC fp16 rows [B*H*W, C]: 1x1 convolutions are
-    plain MFMA GEMMs, 3x3 convolutions are an im2col gather + the same GEMM, BatchNorm(eval)+ReLU(+residual) is one
-    streaming pass, the attention pool reuses the transformer attention kernel (head dim 64)."""
+    plain MFMA GEMMs (K a multiple of 8: the 80 / 96 / 160-channel inputs of RN50x4 / x16 take the GEMM's K-tail
+    instantiations), stride-1 3x3 convolutions are implicit GEMMs for any channel counts that are multiples of 8, and only
+    the stride-2 3-channel stem convolution goes through an im2col matrix.  BatchNorm(eval) + ReLU (+ residual) rides in
+    the GEMM epilogues; the attention pool reuses the transformer attention kernel (head dim 64)."""
 
     def __init__(self, layers, output_dim, heads, input_resolution=224, width=64):
         super().__init__()
@@ -279,8 +281,8 @@ class ModifiedResNet(nn.Module):
         # images per pass: small passes are launch-bound and leave the tail tiles of every convolution idle — 1024 images in passes of 128 / 256 / 512 / 1024:
         # RN50 33.4 / 37.0 / 39.6 / 41.6 k img/s, RN101 22.5 / 25.7 / 27.0 / 28.5 k (profiles/r06_rn_chunk_probe.txt); the widest activation of a 1024-image pass
         # (layer1's 56 x 56 x 256 fp16) is 1.6 GB.  Same bits for every pass size (tests/test_gpu_encoder.py).
-        # (Widths whose narrow convolutions go through a materialised im2col matrix — RN50x4 / x16: 40 / 48 stem channels — keep passes of 256: the matrix of a
-        # 1024-image pass would be 16 - 34 GB.)
+        # (RN50x4 / x16 — 40 / 48 stem channels — keep passes of 256: their stem convolution still goes through an im2col matrix (288 / 384 px, no fused stem
+        # kernel), 4 - 9 GB for a 1024-image pass, and their widest activation at 1024 images is 4 - 7 GB.  Same bits for every pass size.)
         self.chunk = int(os.environ.get("PCLIP_RN_CHUNK", "1024" if width // 2 in (32, 64) else "256"))
 
     # -- helpers ---------------------------------------------------------------------------------------------------
@@ -308,8 +310,7 @@ class ModifiedResNet(nn.Module):
 
     def _conv3_bn_relu(self, key, x, strides, B, H, W, C, conv, bn, stride=1):
         sc, sh = self._bn_affine(key, bn)
-        if stride == 1 and (C % 64 == 0 or C in (8, 16, 32)) and (conv.weight.shape[0] % 64 == 0 or conv.weight.shape[0] == 32) \
-                and strides == (H * W * C, W * C, C, 1):
+        if stride == 1 and C % 8 == 0 and conv.weight.shape[0] % 8 == 0 and strides == (H * W * C, W * C, C, 1):
             return ops.conv3x3_bn(x, self._w3x3(key, conv), sc, sh, B, H, W, C, relu=True)   # implicit GEMM: no im2col buffer
         cols = ops.im2col3x3(x, strides, B, H, W, C, stride)
         return ops.gemm_bn(cols, self._w3x3(key, conv), sc, sh, relu=True)                   # relu(bn(conv3x3(x))) in one launch
@@ -490,6 +491,11 @@ BACKBONES = {
                   context_length=77, vocab_size=49408, transformer_width=512, transformer_heads=8, transformer_layers=12),
     "ViT-L/14": dict(embed_dim=768, image_resolution=224, vision_layers=24, vision_width=1024, vision_patch_size=14,
                      context_length=77, vocab_size=49408, transformer_width=768, transformer_heads=12, transformer_layers=12),
+    # OpenAI's wide ResNets (the reference's RN50x4.pt / RN50x16.pt): 80 / 96-wide stems, 288 / 384 px, attention pools of 82 / 145 tokens
+    "RN50x4": dict(embed_dim=640, image_resolution=288, vision_layers=(4, 6, 10, 6), vision_width=80, vision_patch_size=None,
+                   context_length=77, vocab_size=49408, transformer_width=640, transformer_heads=10, transformer_layers=12),
+    "RN50x16": dict(embed_dim=768, image_resolution=384, vision_layers=(6, 8, 18, 8), vision_width=96, vision_patch_size=None,
+                    context_length=77, vocab_size=49408, transformer_width=768, transformer_heads=12, transformer_layers=12),
     # OpenAI's ViT-L-14-336px.pt (not in the reference's download list: load it by path; 24 x 24 patches + 1 = 577 tokens)
     "ViT-L/14@336px": dict(embed_dim=768, image_resolution=336, vision_layers=24, vision_width=1024, vision_patch_size=14,
                            context_length=77, vocab_size=49408, transformer_width=768, transformer_heads=12, transformer_layers=12),

@@ -42,6 +42,13 @@ struct Cfg {
     static constexpr int ROWS_PER_PASS = NTHREADS / CPR, NPASS = HR / ROWS_PER_PASS;
     static_assert(HR * BN * 2 <= STAGE_BYTES, "epilogue slab must fit one stage buffer");
     static_assert(BM % (8 * NWAVES) == 0 && BN % (8 * NWAVES) == 0, "tile rows must split over the waves");
+    static constexpr bool TAIL = false;
+};
+// The tail form of a tile configuration (the GEMM's K % 64 != 0 / ragged-N instantiations, the convolution's channel-tail ones): the same tile with
+// TAIL = true.  A type of its own, so that a kernel instantiated on it gets a symbol of its own and the plain instantiations keep theirs.
+template <class Base>
+struct Tail : Base {
+    static constexpr bool TAIL = true;
 };
 using CfgSmall = Cfg<128, 128, 2, 2>;
 
@@ -109,9 +116,12 @@ __device__ __forceinline__ rsrc_t make_rsrc(const void* base, unsigned bytes) {
 
 // All waves of the workgroup stage a ROWS x 64 tile: each LDS-DMA piece is 8 rows x 128 B (64 lanes x 16 B).  The descriptor starts at the tile's first row, so
 // the lane offsets stay small whatever the matrix (rows beyond nrows re-read the last row: never stored).
-template <int ROWS, int NWAVES>
+// KT (K tail, K % 64 != 0, K % 8 == 0): a 16-byte chunk at column >= K takes an offset beyond the descriptor and loads zeros — its bytes would be the next row's
+// data (any fp16 value, Inf / NaN included) or lie past the operand's last element; the descriptor's 2^31-byte range does not catch either.
+constexpr unsigned KTAIL_OFF = 0x80000000u;        // >= every descriptor's num_records (<= 0x7fffffff), and + a scalar K-tile offset < 2^31 does not wrap
+template <int ROWS, int NWAVES, bool KT = false>
 __device__ __forceinline__ void stage_tile(const half_t* __restrict__ g, int ld, int row0, int nrows, int k0,
-                                           char* lds_tile, int wave, int lane) {
+                                           char* lds_tile, int wave, int lane, int K = 0) {
     constexpr int RPW = ROWS / NWAVES;                               // rows per wave
     const rsrc_t rs = make_rsrc(g + (size_t)row0 * ld, 0x7fffffffu);
     const int last = nrows - 1 - row0;
@@ -120,7 +130,8 @@ __device__ __forceinline__ void stage_tile(const half_t* __restrict__ g, int ld,
     for (int i = 0; i < RPW / 8; ++i) {
         const int r = wave * RPW + i * 8 + (lane >> 3);              // tile row this lane fills
         const int c = (lane & 7) ^ swz_key(r);                       // source chunk for LDS slot (lane&7)
-        const int voff = ((r < last ? r : last) * ld + k0 + c * 8) * 2;
+        int voff = ((r < last ? r : last) * ld + k0 + c * 8) * 2;
+        if (KT && k0 + c * 8 >= K) voff = (int)KTAIL_OFF;
         char* dst = lds_tile + (wave * RPW + i * 8) * ROW_BYTES;     // wave-uniform base; HW adds lane*16
         (void)voff; (void)dst;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -170,13 +181,13 @@ __device__ __forceinline__ float4_t acc_quad(const Acc<C>& acc, int i, int j, in
 __device__ __forceinline__ float4_t acc_quad(const Acc16& acc, int i, int j, int g) { return acc.q[2 * i + (g >> 1)][2 * j + (g & 1)]; }
 
 // Stage K-tile 0 of output tile (m0, n0) into buffer p.
-template <class C>
+template <class C, bool KT = false>
 __device__ __forceinline__ void stage_first(const half_t* __restrict__ A, int lda, const half_t* __restrict__ B, int ldb,
-                                            int M, int N, int m0, int n0, char* smem, int p) {
+                                            int M, int N, int m0, int n0, char* smem, int p, int K = 0) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     char* a = smem + p * C::STAGE_BYTES;
-    stage_tile<C::BM, C::NWAVES>(A, lda, m0, M, 0, a, wave, lane);
-    stage_tile<C::BN, C::NWAVES>(B, ldb, n0, N, 0, a + C::A_BYTES, wave, lane);
+    stage_tile<C::BM, C::NWAVES, KT>(A, lda, m0, M, 0, a, wave, lane, K);
+    stage_tile<C::BN, C::NWAVES, KT>(B, ldb, n0, N, 0, a + C::A_BYTES, wave, lane, K);
 }
 
 // K-loop over a tile whose K-tile 0 has ALREADY been staged into buffer `p` (0/1) by stage_first().
@@ -190,9 +201,10 @@ __device__ __forceinline__ void stage_first(const half_t* __restrict__ A, int ld
 // v_mfma_f32_32x32x16_f16: same FLOPs per cycle and the same LDS traffic, a quarter of the accumulator-register traffic per
 // FLOP.  Element e of acc.v[i][j] is then sub-tile (a, b) = (e >> 3, (e >> 2) & 1), row a*16 + (lane & 15), columns
 // b*16 + 4*(lane >> 4) + (e & 3).
-template <class C, int YOUNGER = 0, bool ZERO_ACC = true, bool M16 = false, class StageA>
+// KT: B's chunks at columns >= K load zeros (stage_tile); nt = ceil(K / 64).
+template <class C, int YOUNGER = 0, bool ZERO_ACC = true, bool M16 = false, bool KT = false, class StageA>
 __device__ __forceinline__ void mainloop_g(const StageA& stage_a, const half_t* __restrict__ B, int ldb, int N, int nt, int n0,
-                                           char* smem, Acc<C>& acc, int& p, bool counted_first = false) {
+                                           char* smem, Acc<C>& acc, int& p, bool counted_first = false, int K = 0) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / C::WN, wn = wave % C::WN;
     if (ZERO_ACC) {                                        // otherwise the caller pre-loaded the accumulators (e.g. with the bias)
@@ -218,7 +230,7 @@ __device__ __forceinline__ void mainloop_g(const StageA& stage_a, const half_t* 
             if (t + 1 < nt) {
                 char* na = smem + (p ^ 1) * C::STAGE_BYTES;
                 stage_a(t + 1, na);
-                stage_tile<C::BN, C::NWAVES>(B, ldb, n0, N, (t + 1) * BK, na + C::A_BYTES, wave, lane);
+                stage_tile<C::BN, C::NWAVES, KT>(B, ldb, n0, N, (t + 1) * BK, na + C::A_BYTES, wave, lane, K);
             }
         };
         if (!late) stage_next();
@@ -273,13 +285,13 @@ __device__ __forceinline__ void mainloop_g(const StageA& stage_a, const half_t* 
     }
 }
 
-template <class C, int YOUNGER = 0, bool ZERO_ACC = true, bool M16 = false>
+template <class C, int YOUNGER = 0, bool ZERO_ACC = true, bool M16 = false, bool KT = false>
 __device__ __forceinline__ void mainloop(const half_t* __restrict__ A, int lda, const half_t* __restrict__ B, int ldb,
                                          int M, int N, int K, int m0, int n0, char* smem, Acc<C>& acc, int& p,
                                          bool counted_first = false) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    mainloop_g<C, YOUNGER, ZERO_ACC, M16>([&](int t, char* dst) { stage_tile<C::BM, C::NWAVES>(A, lda, m0, M, t * BK, dst, wave, lane); },
-                                     B, ldb, N, K / BK, n0, smem, acc, p, counted_first);
+    mainloop_g<C, YOUNGER, ZERO_ACC, M16, KT>([&](int t, char* dst) { stage_tile<C::BM, C::NWAVES, KT>(A, lda, m0, M, t * BK, dst, wave, lane, K); },
+                                         B, ldb, N, KT ? (K + BK - 1) / BK : K / BK, n0, smem, acc, p, counted_first, K);
 }
 
 // ---- buffer-descriptor staging + register-pipelined K-loop (the persistent linear kernels) ---------------------------------
@@ -297,13 +309,16 @@ __device__ __forceinline__ void mainloop(const half_t* __restrict__ A, int lda, 
 #ifndef PCLIP_NT_A
 #define PCLIP_NT_A 0             // cache-policy bits of the A-operand LDS-DMA (2 = nt measured 7 % slower: every A line has 3 - 12 readers)
 #endif
-template <int ROWS, int NWAVES>
+// KT: chunks at columns >= K load zeros (stage_tile); the test runs per piece at every K-tile, in the KT instantiation only.
+template <int ROWS, int NWAVES, bool KT = false>
 struct TileSrc {
     static constexpr int RPW = ROWS / NWAVES, NL = RPW / 8;          // rows per wave, LDS-DMA pieces per wave and K-tile
     rsrc_t rs;
     int voff[NL];
+    int K;                                                           // (KT only)
     // rows >= nrows are clamped to the last row (never stored); row0 <= nrows - 1
-    __device__ __forceinline__ void prepare(const half_t* __restrict__ g, int ld, int row0, int nrows, int wave, int lane) {
+    __device__ __forceinline__ void prepare(const half_t* __restrict__ g, int ld, int row0, int nrows, int wave, int lane, int K_ = 0) {
+        K = K_;
 #if defined(__HIP_DEVICE_COMPILE__)
         // descriptor inputs through readfirstlane: hipcc must be able to PROVE the descriptor wave-uniform, otherwise every
         // buffer op is wrapped in a waterfall loop (guide T20)
@@ -325,22 +340,28 @@ struct TileSrc {
         stress_jitter(100);
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
-        for (int i = 0; i < NL; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(lds_tile + (wave * RPW + i * 8) * ROW_BYTES), 16, voff[i], k_bytes, 0, AUX);
+        for (int i = 0; i < NL; ++i) {
+            int v = voff[i];
+            if constexpr (KT) {
+                const int lane = threadIdx.x & 63, r = wave * RPW + i * 8 + (lane >> 3), c = (lane & 7) ^ swz_key(r);
+                if ((k_bytes >> 1) + c * 8 >= K) v = (int)KTAIL_OFF;
+            }
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(lds_tile + (wave * RPW + i * 8) * ROW_BYTES), 16, v, k_bytes, 0, AUX);
+        }
 #endif
     }
 };
 
-template <class C>
+template <class C, bool KT = false>
 struct TilePair {
     static constexpr bool ROLES = false;
     static constexpr int NA = TileSrc<C::BM, C::NWAVES>::NL, NB = TileSrc<C::BN, C::NWAVES>::NL;
-    TileSrc<C::BM, C::NWAVES> a;
-    TileSrc<C::BN, C::NWAVES> b;
+    TileSrc<C::BM, C::NWAVES, KT> a;
+    TileSrc<C::BN, C::NWAVES, KT> b;
     __device__ __forceinline__ void prepare(const half_t* __restrict__ A, int lda, const half_t* __restrict__ B, int ldb, int M, int N,
-                                            int m0, int n0, int wave, int lane) {
-        a.prepare(A, lda, m0, M, wave, lane);
-        b.prepare(B, ldb, n0, N, wave, lane);
+                                            int m0, int n0, int wave, int lane, int K = 0) {
+        a.prepare(A, lda, m0, M, wave, lane, K);
+        b.prepare(B, ldb, n0, N, wave, lane, K);
     }
     __device__ __forceinline__ void stage(int t, char* stage_buf, int wave) const {
         a.template stage<PCLIP_NT_A>(t * (BK * 2), stage_buf, wave);
@@ -357,7 +378,7 @@ struct TilePair {
 #ifndef PCLIP_DMA_ROLES
 #define PCLIP_DMA_ROLES 1
 #endif
-template <class C>
+template <class C, bool KT = false>
 struct TilePairR {
     static constexpr bool ROLES = true;
     static_assert(C::NWAVES == 8, "role split: waves w and w + 4 share a SIMD");
@@ -371,8 +392,10 @@ struct TilePairR {
     int voff[2];
     int row16;                                                        // bytes of 16 operand rows (wave-uniform)
     bool is_b;                                                        // wave-uniform
+    int K;                                                            // (KT only: chunks at columns >= K load zeros; the chunk of piece i depends on i & 1 only)
     __device__ __forceinline__ void prepare(const half_t* __restrict__ A, int lda, const half_t* __restrict__ B, int ldb, int M, int N,
-                                            int m0, int n0, int wave, int lane) {
+                                            int m0, int n0, int wave, int lane, int K_ = 0) {
+        K = K_;
         is_b = wave < 4;
         const half_t* g = is_b ? B : A;
         const int ld = is_b ? ldb : lda, row0 = is_b ? n0 : m0, nrows = is_b ? N : M, rpw = (is_b ? C::BN : C::BM) / 4, w4 = wave & 3;
@@ -396,15 +419,24 @@ struct TilePairR {
         stress_jitter(101);
 #if defined(__HIP_DEVICE_COMPILE__)
         const int w4 = wave & 3, k = t * (BK * 2);
+        int v[2] = {voff[0], voff[1]};
+        if constexpr (KT) {
+            const int lane = threadIdx.x & 63, rpw = is_b ? C::BN / 4 : C::BM / 4;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int r = w4 * rpw + i * 8 + (lane >> 3), c = (lane & 7) ^ swz_key(r);
+                if (t * BK + c * 8 >= K) v[i] = (int)KTAIL_OFF;
+            }
+        }
         if (is_b) {
 #pragma unroll
             for (int i = 0; i < NB; ++i)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(stage_buf + C::A_BYTES + (w4 * (C::BN / 4) + i * 8) * ROW_BYTES), 16, voff[i & 1],
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(stage_buf + C::A_BYTES + (w4 * (C::BN / 4) + i * 8) * ROW_BYTES), 16, v[i & 1],
                                                          k + (i >> 1) * row16, 0, 0);
         } else {
 #pragma unroll
             for (int i = 0; i < NA; ++i)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(stage_buf + (w4 * (C::BM / 4) + i * 8) * ROW_BYTES), 16, voff[i & 1],
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(stage_buf + (w4 * (C::BM / 4) + i * 8) * ROW_BYTES), 16, v[i & 1],
                                                          k + (i >> 1) * row16, 0, PCLIP_NT_A);
         }
 #endif
@@ -541,10 +573,11 @@ __device__ __forceinline__ void mainloop_sr(const TP& tp, int nt, char* smem, Ac
 
 // ---- implicit-GEMM gather for a 3x3 / stride 1 / pad 1 convolution on NHWC fp16 activations ------------------------------
 // Row m of the GEMM is output pixel (b, y, x); K-tile t covers tap = (t*64) / Cin and input channels c0 = (t*64) % Cin
-// (Cin % 64 == 0; Cin = 8 / 16 / 32 take the per-chunk path of stage()), i.e. the 128 contiguous bytes x[b, y+dy-1, x+dx-1, c0 .. c0+63] — or 128 zero bytes outside the image:
+// (Cin % 64 == 0; Cin = 8 / 16 / 32 take the per-chunk path of stage(), and so does every Cin % 8 == 0 in the TAIL instantiation: Cin = 40, 48, 80, 96, 160 of
+// RN50x4 / x16), i.e. the 128 contiguous bytes x[b, y+dy-1, x+dx-1, c0 .. c0+63] — or 128 zero bytes outside the image:
 // a buffer load beyond the descriptor's range (an LDS-DMA cannot be predicated per lane without leaving stale LDS; round 6: was a caller-provided zero line).
 // The im2col matrix (9x the activation) is never materialised.
-template <class C>
+template <class C, bool TAIL = false>
 struct ConvGather {
     static constexpr int NR = C::BM / C::NWAVES / 8;       // A rows per lane
     const half_t* __restrict__ x;
@@ -573,9 +606,9 @@ struct ConvGather {
     __device__ __forceinline__ void stage(int t, char* dst, int wave) const {
         const int lane = threadIdx.x & 63;
         (void)lane;
-        if (Cin < BK) {
-            // Cin = 8 / 16 / 32 (the ResNet stem): a K-tile spans 64 / Cin taps, so the tap belongs to the 16-byte chunk, not to the
-            // row; taps >= 9 (K padded to the K-tile, zero weights there) read zeros
+        if (TAIL ? Cin % BK != 0 : Cin < BK) {
+            // Cin = 8 / 16 / 32 (the ResNet stem), or any Cin % 8 == 0 (TAIL): a K-tile may span several taps, so the tap belongs to the 16-byte chunk
+            // (8 channels of one tap: Cin % 8 == 0), not to the row; taps >= 9 (K padded to the K-tile, zero weights there) read zeros
 #pragma unroll
             for (int i = 0; i < NR; ++i) {
                 const int r = wave * (C::BM / C::NWAVES) + i * 8 + (lane >> 3);
@@ -607,17 +640,17 @@ struct ConvGather {
 };
 
 // The convolution's operand pair for mainloop_sr (the software-pipelined K-loop with the staggered refill): A = the gather above, B = the weights [Cout, 9 Cin].
-template <class C>
+template <class C, bool TAIL = false>
 struct ConvPair {
     static constexpr bool ROLES = false;
-    static constexpr int NA = ConvGather<C>::NR, NB = TileSrc<C::BN, C::NWAVES>::NL;
+    static constexpr int NA = ConvGather<C, TAIL>::NR, NB = TileSrc<C::BN, C::NWAVES>::NL;
     struct AOp {
-        ConvGather<C> g;
+        ConvGather<C, TAIL> g;
         template <int AUX = 0>
         __device__ __forceinline__ void stage(int k_bytes, char* dst, int wave) const { g.stage(k_bytes / (BK * 2), dst, wave); }
     } a;
     TileSrc<C::BN, C::NWAVES> b;
-    __device__ __forceinline__ ConvPair(const half_t* x, int H, int W, int Cin, int M) : a{ConvGather<C>(x, H, W, Cin, M)} {}
+    __device__ __forceinline__ ConvPair(const half_t* x, int H, int W, int Cin, int M) : a{ConvGather<C, TAIL>(x, H, W, Cin, M)} {}
     __device__ __forceinline__ void stage(int t, char* stage_buf, int wave) const {
         a.g.stage(t, stage_buf, wave);
         b.template stage<0>(t * (BK * 2), stage_buf + C::A_BYTES, wave);
@@ -632,9 +665,10 @@ struct ConvPair {
 // (bit-identical accumulation).  `init()` runs after the first NS-1 stages are on their way and sets the accumulators (zero,
 // or the bias as in linear_fast_kernel: its loads overlap the stages' latency).
 // `stage_a(t, dst)` stages K-tile t of the A operand (stage_tile, or ConvGather::stage for the implicit convolution).
-template <class C, int NS, class StageA, class Init>
+// KT: B's chunks at columns >= K load zeros (stage_tile).
+template <class C, int NS, bool KT = false, class StageA, class Init>
 __device__ __forceinline__ void mainloop_ring_g(const StageA& stage_a, const half_t* __restrict__ B, int ldb, int N, int nt, int n0,
-                                                char* smem, Acc<C>& acc, const Init& init) {
+                                                char* smem, Acc<C>& acc, const Init& init, int K = 0) {
     constexpr int PER = (C::BM + C::BN) / (8 * C::NWAVES);          // LDS-DMA instructions per wave per stage
     static_assert(NS >= 3 && NS <= 6 && (NS - 2) * PER < 64, "ring depth / vmcnt range");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -642,7 +676,7 @@ __device__ __forceinline__ void mainloop_ring_g(const StageA& stage_a, const hal
     auto stage = [&](int t, int slot) {
         char* a = smem + slot * C::STAGE_BYTES;
         stage_a(t, a);
-        stage_tile<C::BN, C::NWAVES>(B, ldb, n0, N, t * BK, a + C::A_BYTES, wave, lane);
+        stage_tile<C::BN, C::NWAVES, KT>(B, ldb, n0, N, t * BK, a + C::A_BYTES, wave, lane, K);
     };
     for (int t = 0; t < NS - 1 && t < nt; ++t) stage(t, t);
     init();
@@ -693,12 +727,12 @@ __device__ __forceinline__ void mainloop_ring_g(const StageA& stage_a, const hal
     }
 }
 
-template <class C, int NS, class Init>
+template <class C, int NS, bool KT = false, class Init>
 __device__ __forceinline__ void mainloop_ring(const half_t* __restrict__ A, int lda, const half_t* __restrict__ B, int ldb, int M,
-                                              int N, int nt, int m0, int n0, char* smem, Acc<C>& acc, const Init& init) {
+                                              int N, int nt, int m0, int n0, char* smem, Acc<C>& acc, const Init& init, int K = 0) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    mainloop_ring_g<C, NS>([&](int t, char* dst) { stage_tile<C::BM, C::NWAVES>(A, lda, m0, M, t * BK, dst, wave, lane); }, B, ldb, N, nt,
-                           n0, smem, acc, init);
+    mainloop_ring_g<C, NS, KT>([&](int t, char* dst) { stage_tile<C::BM, C::NWAVES, KT>(A, lda, m0, M, t * BK, dst, wave, lane, K); }, B, ldb, N, nt,
+                               n0, smem, acc, init, K);
 }
 
 // ---- fp16 output through an LDS-staged, fully coalesced epilogue -----------------------------------------

@@ -17,6 +17,8 @@ namespace {
 // Every vector-memory operation of this kernel is an LDS-DMA or a store (the bias row of the tile also
 // travels by global_load_lds into a small double-buffered LDS strip), because hipcc answers any ordinary
 // VGPR load issued beside an LDS-DMA with a full vmcnt(0) drain at its use (guide §5, trap (b)).
+// KT (C = pgemm::Tail<Cfg>): K % 64 != 0 (K % 8 == 0) — the operands' chunks at columns >= K load zeros (pgemm::stage_tile) — and N % 8 == 0 ragged against
+// the tile: the last column tile's columns >= N are never stored, and no bias / scale / shift / residual element beyond N is read (descriptors sized to N).
 template <class C, bool HAS_BIAS, int ACT>
 __global__ __launch_bounds__(C::NTHREADS, 2) void linear_fast_kernel(const half_t* __restrict__ A, int lda,
                                                                      const half_t* __restrict__ B, int ldb, int M, int N,
@@ -32,6 +34,7 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void linear_fast_kernel(const half_
     // in the epilogue of out_proj / c_proj; Cout may BE residual (the residual stream is updated in place: every 16-byte chunk is
     // read and then written by the same thread)
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr bool KT = C::TAIL;                                             // C = pgemm::Tail<Cfg>: the K-tail / ragged-N instantiation
     constexpr bool M16 = true;                                               // 16x16x32 MFMAs (accumulator layout of pgemm::mainloop_sr)
     half_t* bias_lds = reinterpret_cast<half_t*>(smem + C::LDS_BYTES);       // [2][BN] fp16
     float* affine_lds = reinterpret_cast<float*>(smem + C::LDS_BYTES);       // ACT >= 2: [2][ scale BN | shift BN ] fp32
@@ -56,12 +59,14 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void linear_fast_kernel(const half_
     int p = 0;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), wn = wave % C::WN;
     // M16: buffer-descriptor staging + pipelined K-loop; eight-wave tiles split the DMA issue by wave role (pgemm::TilePairR)
-    using TP = std::conditional_t<(PCLIP_DMA_ROLES && C::NWAVES == 8), pgemm::TilePairR<C>, pgemm::TilePair<C>>;
+    using TP = std::conditional_t<(PCLIP_DMA_ROLES && C::NWAVES == 8), pgemm::TilePairR<C, KT>, pgemm::TilePair<C, KT>>;
     TP tp;
     // The bias enters as the INITIAL VALUE of the accumulators (fp32 copy of the fp16 bias: r16(bias + sum) instead of
     // r16(sum + bias), same value up to fp32 summation order), so the epilogue has no bias pass.  Its strip is copied one
     // tile ahead (double-buffered); every wave copies the same BN values: uniform vmcnt bookkeeping.
-    const pgemm::rsrc_t rs_bias = pgemm::make_rsrc(bias, 0x7fffffffu), rs_scale = pgemm::make_rsrc(scale, 0x7fffffffu), rs_shift = pgemm::make_rsrc(shift, 0x7fffffffu);
+    // (KT: descriptors sized to N — strip entries beyond N load zeros, nothing past the vectors is read)
+    const pgemm::rsrc_t rs_bias = pgemm::make_rsrc(bias, KT ? (unsigned)N * 2u : 0x7fffffffu), rs_scale = pgemm::make_rsrc(scale, KT ? (unsigned)N * 4u : 0x7fffffffu),
+                        rs_shift = pgemm::make_rsrc(shift, KT ? (unsigned)N * 4u : 0x7fffffffu);
     (void)rs_bias; (void)rs_scale; (void)rs_shift;
     auto copy_bias = [&](int t, int par) {
         int tm_, tn;
@@ -93,7 +98,7 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void linear_fast_kernel(const half_
     {
         int tm, tn;
         decomp(tile, tm, tn);
-        tp.prepare(A, lda, B, ldb, M, N, tm * C::BM, tn * C::BN, wave, lane);
+        tp.prepare(A, lda, B, ldb, M, N, tm * C::BM, tn * C::BN, wave, lane, K);
         tp.stage(0, smem + p * C::STAGE_BYTES, wave);
     }
     // vector-memory operations a wave issues between a tile's K-tile 0 pieces and the first wait of its K-loop: the previous tile's stores + the strip copies
@@ -109,7 +114,7 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void linear_fast_kernel(const half_
         if (HAS_BIAS) {
             // the strip of this tile was copied one tile ago; with two or more K-tiles the K-loop's vmcnt(0) + barrier in
             // between made it visible, a single K-tile (K = 64) only has the counted wait: close that case explicitly
-            if (K == pgemm::BK) { pgemm::wait_vm<0>(); pgemm::lds_barrier(); }
+            if (KT ? K <= pgemm::BK : K == pgemm::BK) { pgemm::wait_vm<0>(); pgemm::lds_barrier(); }
             const half_t* bl = bias_lds + parity * C::BN + wn * (C::BN / C::WN);
 #pragma unroll
             for (int j = 0; j < C::TN; ++j)
@@ -130,11 +135,11 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void linear_fast_kernel(const half_
         // 4-byte LDS-DMA per line — out_proj 301 -> 341 us, c_proj 854 -> 879 us: 1024 more requests per tile in the queue the operand
         // DMAs wait in.)
         const int next = tile + G;
-        pgemm::mainloop_sr<C, YOUNGER, !HAS_BIAS, TP>(tp, K / pgemm::BK, smem, acc, p, prev_full, wave, lane);
+        pgemm::mainloop_sr<C, YOUNGER, !HAS_BIAS, TP>(tp, KT ? (K + pgemm::BK - 1) / pgemm::BK : K / pgemm::BK, smem, acc, p, prev_full, wave, lane);
         if (next < ntiles) {                                  // buffer p is free: prefetch the next tile's K-tile 0
             int tm, tn;
             decomp(next, tm, tn);
-            tp.prepare(A, lda, B, ldb, M, N, tm * C::BM, tn * C::BN, wave, lane);
+            tp.prepare(A, lda, B, ldb, M, N, tm * C::BM, tn * C::BN, wave, lane, K);
             tp.stage(0, smem + p * C::STAGE_BYTES, wave);
         }
         char* stg = smem + (p ^ 1) * C::STAGE_BYTES;          // buffer of the last K-tile, reused after a barrier
@@ -143,6 +148,7 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void linear_fast_kernel(const half_
         asm volatile("" : "+v"(etid));
 #endif
         const int col = n0 + 8 * (etid % C::CPR);
+        const bool colok = !KT || col < N;                    // KT: the chunk exists (N % 8 == 0)
         auto pre = [&](int i, int j, int coff, float4_t v, int rl, int g) {
             if (ACT == 1) return quick_gelu16x4(v);
             half4_t h;
@@ -176,7 +182,7 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void linear_fast_kernel(const half_
 #pragma unroll
             for (int ps = 0; ps < 4; ++ps) {
                 const int rs = etid / C::CPR + ps * 16, r = (rs >> 5) * 128 + k * 32 + (rs & 31);
-                if (full || m0 + r < M) rr[RES ? (k & 1) * 4 + ps : 0] = ld_half8(residual + (size_t)(m0 + r) * ldc + col);
+                if ((full || m0 + r < M) && colok) rr[RES ? (k & 1) * 4 + ps : 0] = ld_half8(residual + (size_t)(m0 + r) * ldc + col);
             }
         };
         auto slab = [&](int h) {
@@ -184,7 +190,7 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void linear_fast_kernel(const half_
 #pragma unroll
             for (int ps = 0; ps < C::NPASS; ++ps) {
                 const int r = h * C::HR + etid / C::CPR + ps * C::ROWS_PER_PASS;
-                if (full || m0 + r < M) rr[ps] = ld_half8(residual + (size_t)(m0 + r) * ldc + col);
+                if ((full || m0 + r < M) && colok) rr[ps] = ld_half8(residual + (size_t)(m0 + r) * ldc + col);
             }
         };
         auto add_res = [&](int pass, half8_t h) {
@@ -202,13 +208,13 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void linear_fast_kernel(const half_
                 pgemm::epilogue_pipe<C>(acc, stg, ahead, pre, [&](int r, int c, int pass, half8_t h) {
                     const size_t o = (size_t)(m0 + r) * ldc + col;
                     if (RES) h = add_res(pass, h);
-                    st_out(Cout + o, h);
+                    if (colok) st_out(Cout + o, h);
                 });
             else
                 pgemm::epilogue_pipe<C>(acc, stg, ahead, pre, [&](int r, int c, int pass, half8_t h) {
                     const size_t o = (size_t)(m0 + r) * ldc + col;
                     if (RES) h = add_res(pass, h);
-                    if (m0 + r < M) st_out(Cout + o, h);
+                    if (m0 + r < M && colok) st_out(Cout + o, h);
                 });
             prev_full = full;
             continue;
@@ -217,24 +223,27 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void linear_fast_kernel(const half_
             pgemm::epilogue_f16<C, M16>(acc, stg, slab, pre, [&](int r, int c, int pass, half8_t h) {
                 const size_t o = (size_t)(m0 + r) * ldc + col;
                 if (RES) h = add_res(pass, h);
-                st_out(Cout + o, h);
+                if (colok) st_out(Cout + o, h);
             });
         else
             pgemm::epilogue_f16<C, M16>(acc, stg, slab, pre, [&](int r, int c, int pass, half8_t h) {
                 const size_t o = (size_t)(m0 + r) * ldc + col;
                 if (RES) h = add_res(pass, h);
-                if (m0 + r < M) st_out(Cout + o, h);
+                if (m0 + r < M && colok) st_out(Cout + o, h);
             });
         prev_full = full;
     }
     pgemm::time_end(tslot);
 }
 
+
 // ---- 3x3 convolution (stride 1, pad 1, NHWC) + eval BatchNorm (+ReLU) as an implicit GEMM -----------------------------------
 // Same persistent structure as linear_fast_kernel; the A operand is gathered by pgemm::ConvGather instead of read from an
 // im2col matrix (clip/model.py:20-22, 45-46: conv2 / bn2 / relu of every bottleneck).  w is [Cout, ky, kx, Cin].
 // K-loop: the software-pipelined loop of the linears (pgemm::mainloop_sr: fragments a group ahead, K-tile t + 2 requested in two halves during iteration t) over
 // pgemm::ConvPair (round 6; before: mainloop_g's read-everything-then-multiply loop — the same k order, the same bits, RN50 +2 % in a same-box A/B).
+// TAIL (C = pgemm::Tail<Cfg>): any Cin % 8 == 0 (the per-chunk gather) and Cout % 8 == 0 ragged against the tile (columns >= Cout never stored, scale / shift
+// beyond Cout never read).
 template <class C, int ACT>
 __global__ __launch_bounds__(C::NTHREADS, 2) void conv3x3_fast_kernel(const half_t* __restrict__ x,
                                                                       const half_t* __restrict__ w, int H, int W, int Cin, int M,
@@ -243,14 +252,15 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void conv3x3_fast_kernel(const half
                                                                       int tiles_n, int ntiles) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* affine_lds = reinterpret_cast<float*>(smem + C::LDS_BYTES);       // [2][ scale BN | shift BN ] fp32
+    constexpr bool TAIL = C::TAIL;                                           // C = pgemm::Tail<Cfg>: the channel-tail instantiation
     const int G = gridDim.x;
     int tile = pgemm::xcd_remap(blockIdx.x, G);
     if (tile >= ntiles) return;
     const int nt = (9 * Cin + pgemm::BK - 1) / pgemm::BK, ldb = nt * pgemm::BK;    // w rows are zero-padded to the K-tile (Cin < 64)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), wn = wave % C::WN;
-    pgemm::ConvPair<C> cp(x, H, W, Cin, M);
-    pgemm::ConvGather<C>& ga = cp.a.g;
-    const pgemm::rsrc_t rs_scale = pgemm::make_rsrc(scale, 0x7fffffffu), rs_shift = pgemm::make_rsrc(shift, 0x7fffffffu);
+    pgemm::ConvPair<C, TAIL> cp(x, H, W, Cin, M);
+    pgemm::ConvGather<C, TAIL>& ga = cp.a.g;
+    const pgemm::rsrc_t rs_scale = pgemm::make_rsrc(scale, TAIL ? (unsigned)N * 4u : 0x7fffffffu), rs_shift = pgemm::make_rsrc(shift, TAIL ? (unsigned)N * 4u : 0x7fffffffu);
     (void)rs_scale; (void)rs_shift;
     auto copy_affine = [&](int t, int par) {
         const int tn = t - (t / tiles_n) * tiles_n;
@@ -283,7 +293,7 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void conv3x3_fast_kernel(const half
         const bool full = m0 + C::BM <= M;
         pgemm::Acc<C> acc;
         copy_affine(tile + G < ntiles ? tile + G : tile, parity ^ 1);
-        pgemm::mainloop_sr<C, YOUNGER, true, pgemm::ConvPair<C>>(cp, nt, smem, acc, p, prev_full, wave, lane);
+        pgemm::mainloop_sr<C, YOUNGER, true, pgemm::ConvPair<C, TAIL>>(cp, nt, smem, acc, p, prev_full, wave, lane);
         const int next = tile + G;
         if (next < ntiles) {                                  // buffer p is free: prefetch the next tile's K-tile 0
             ga.prepare((next / tiles_n) * C::BM);
@@ -303,18 +313,23 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void conv3x3_fast_kernel(const half
             }
             return h;
         };
+        const bool colok = !TAIL || col < N;
         if (full)
             pgemm::epilogue_f16<C, true>(acc, stg, [](int) {}, pre,
-                                   [&](int r, int, int, half8_t h) { st_half8(Cout + (size_t)(m0 + r) * N + col, h); });
+                                   [&](int r, int, int, half8_t h) { if (colok) st_half8(Cout + (size_t)(m0 + r) * N + col, h); });
         else
             pgemm::epilogue_f16<C, true>(acc, stg, [](int) {}, pre, [&](int r, int, int, half8_t h) {
-                if (m0 + r < M) st_half8(Cout + (size_t)(m0 + r) * N + col, h);
+                if (m0 + r < M && colok) st_half8(Cout + (size_t)(m0 + r) * N + col, h);
             });
         prev_full = full;
     }
 }
 
+
 // ---- generic kernel: any M, N, leading dimensions; optional residual; one 128x128 tile per workgroup ------
+// KT (K % 64 != 0): chunks at columns >= K load zeros, and the K-loop runs the 16x16x32 MFMAs of the persistent kernels (M16), so a
+// K-tail call gives the same bits whichever kernel takes it.
+template <bool KT = false>
 __global__ __launch_bounds__(256, 2) void linear_generic_kernel(const half_t* __restrict__ A, int lda,
                                                                 const half_t* __restrict__ B, int ldb, int M, int N,
                                                                 int K, LinearEpi epi, int tiles_n) {
@@ -325,14 +340,14 @@ __global__ __launch_bounds__(256, 2) void linear_generic_kernel(const half_t* __
     const int m0 = tile_m * C::BM, n0 = tile_n * C::BN;
     const int tid = threadIdx.x, wave = tid >> 6, wn = wave % C::WN;
     int p = 0;
-    pgemm::stage_first<C>(A, lda, B, ldb, M, N, m0, n0, smem, p);
+    pgemm::stage_first<C, KT>(A, lda, B, ldb, M, N, m0, n0, smem, p, K);
     pgemm::Acc<C> acc;
-    pgemm::mainloop<C, 0>(A, lda, B, ldb, M, N, K, m0, n0, smem, acc, p, false);
+    pgemm::mainloop<C, 0, true, KT, KT>(A, lda, B, ldb, M, N, K, m0, n0, smem, acc, p, false);
     const half_t* __restrict__ bias = epi.bias;
     const half_t* __restrict__ residual = epi.residual;
     const int act = epi.act, ldc = epi.ldc;
     const int col = n0 + 8 * (tid % C::CPR);
-    pgemm::epilogue_f16<C>(
+    pgemm::epilogue_f16<C, KT>(
         acc, smem + (p ^ 1) * C::STAGE_BYTES, [](int) {},
         [&](int, int j, int coff, float4_t v, int rl, int g) {
             const int n = n0 + wn * (C::BN / C::WN) + j * 32 + coff;
@@ -386,20 +401,23 @@ static const TileOrder& tile_order() {
     return order;
 }
 
-template <class C, bool HAS_BIAS, int ACT>
+// KT: the K-tail / ragged-N instantiation of linear_fast_kernel: column tiles = ceil(N / BN)
+template <class C, bool HAS_BIAS, int ACT, bool KT>
 static int launch_fast2(const void* A, int lda, const void* B, int ldb, int M, int N, int K, const LinearEpi& epi,
                         int slots, hipStream_t s) {
     static DevOnce attr;
     constexpr int LDS = C::LDS_BYTES + ((ACT == 2 || ACT == 3 || ACT == 5) ? 2 * 2 * C::BN * 4 : 2 * C::BN * 2) + 256;   // K-tile ring + double-buffered bias / affine strips + prefetch scrap
+    using CK = std::conditional_t<KT, pgemm::Tail<C>, C>;
+    const void* fn = (const void*)linear_fast_kernel<CK, HAS_BIAS, ACT>;
     if (!attr.done()) {
-        if (hipFuncSetAttribute((const void*)linear_fast_kernel<C, HAS_BIAS, ACT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 LDS) != hipSuccess) {
             pclip_set_error("pclip_gemm_f16: cannot raise the dynamic LDS limit to %d", LDS);
             return PCLIP_E_LAUNCH;
         }
         attr.set();
     }
-    const int tiles_m = ceil_div(M, C::BM), tiles_n = N / C::BN, ntiles = tiles_m * tiles_n;
+    const int tiles_m = ceil_div(M, C::BM), tiles_n = KT ? ceil_div(N, C::BN) : N / C::BN, ntiles = tiles_m * tiles_n;
     const int grid = ntiles < slots ? ntiles : slots;
     const TileOrder& order = tile_order();
     const int band = order.band;
@@ -409,25 +427,29 @@ static int launch_fast2(const void* A, int lda, const void* B, int ldb, int M, i
     const int rev_mode = order.rev;
     // 1: every launch descending; 2: only the launches that read a LayerNorm / attention output (K <= 1024: in_proj, c_fc, out_proj), c_proj ascending behind the descending c_fc
     const bool rev = rev_mode == 1 || (rev_mode == 2 && K <= 1024);
-    linear_fast_kernel<C, HAS_BIAS, ACT><<<grid, C::NTHREADS, LDS, s>>>(
+    linear_fast_kernel<CK, HAS_BIAS, ACT><<<grid, C::NTHREADS, LDS, s>>>(
         (const half_t*)A, lda, (const half_t*)B, ldb, M, N, K, epi.bias, epi.scale, epi.shift, epi.C, epi.ldc, tiles_n, ntiles, epi.residual,
         rev ? -1 : (tiles_n >= 8 ? band : 0), pclip_gemm_time_slot());
     return pclip_check_launch("gemm_f16");
 }
 
-template <class C>
+template <class C, bool KT = false>
 static int launch_fast(const void* A, int lda, const void* B, int ldb, int M, int N, int K, const LinearEpi& epi,
                        int slots, hipStream_t s) {
-    if (epi.act == 2) return launch_fast2<C, false, 2>(A, lda, B, ldb, M, N, K, epi, slots, s);
-    if (epi.act == 3) return launch_fast2<C, false, 3>(A, lda, B, ldb, M, N, K, epi, slots, s);
-    if (epi.act == 5) return launch_fast2<C, false, 5>(A, lda, B, ldb, M, N, K, epi, slots, s);
-    if (epi.act == 6) return launch_fast2<C, true, 6>(A, lda, B, ldb, M, N, K, epi, slots, s);
+    if (epi.act == 2) return launch_fast2<C, false, 2, KT>(A, lda, B, ldb, M, N, K, epi, slots, s);
+    if (epi.act == 3) return launch_fast2<C, false, 3, KT>(A, lda, B, ldb, M, N, K, epi, slots, s);
+    if (epi.act == 5) return launch_fast2<C, false, 5, KT>(A, lda, B, ldb, M, N, K, epi, slots, s);
+    if (epi.act == 6) return launch_fast2<C, true, 6, KT>(A, lda, B, ldb, M, N, K, epi, slots, s);
     if (epi.bias) {
-        if (epi.act == 1) return launch_fast2<C, true, 1>(A, lda, B, ldb, M, N, K, epi, slots, s);
-        return launch_fast2<C, true, 0>(A, lda, B, ldb, M, N, K, epi, slots, s);
+        if (epi.act == 1) return launch_fast2<C, true, 1, KT>(A, lda, B, ldb, M, N, K, epi, slots, s);
+        return launch_fast2<C, true, 0, KT>(A, lda, B, ldb, M, N, K, epi, slots, s);
     }
-    if (epi.act == 1) return launch_fast2<C, false, 1>(A, lda, B, ldb, M, N, K, epi, slots, s);
-    return launch_fast2<C, false, 0>(A, lda, B, ldb, M, N, K, epi, slots, s);
+    if (epi.act == 1) return launch_fast2<C, false, 1, KT>(A, lda, B, ldb, M, N, K, epi, slots, s);
+    return launch_fast2<C, false, 0, KT>(A, lda, B, ldb, M, N, K, epi, slots, s);
+}
+template <class C>
+static int launch_fast_k(bool kt, const void* A, int lda, const void* B, int ldb, int M, int N, int K, const LinearEpi& epi, int slots, hipStream_t s) {
+    return kt ? launch_fast<C, true>(A, lda, B, ldb, M, N, K, epi, slots, s) : launch_fast<C, false>(A, lda, B, ldb, M, N, K, epi, slots, s);
 }
 
 }  // namespace
@@ -470,19 +492,22 @@ constexpr int kNumCfgs = 5;                  // configurations the cost model ch
 constexpr TileCfg kTileCfgs[kNumCfgs] = {{128, 128, 2, 0.85}, {256, 128, 1, 0.85}, {256, 256, 1, 1.0}, {256, 64, 1, 0.6}, {256, 32, 2, 0.4}};
 constexpr double kLaunchCost = 0.5;          // extra launch of a split, in the same units
 
-inline double tile_cost(const TileCfg& c, long M, int N, int cus) {
-    if (N % c.bn) return 1e30;
-    const long slots = (long)c.wg_per_cu * cus, nt = ((M + c.bm - 1) / c.bm) * (N / c.bn);
+// ragged: the tail instantiations (K % 64 != 0, or a 3x3 convolution with Cout outside {32, 64k}) take any N % 8 == 0 as ceil(N / bn) column tiles
+inline long col_tiles(int N, int bn, bool ragged) { return ragged ? (N + bn - 1) / bn : N / bn; }
+inline double tile_cost(const TileCfg& c, long M, int N, int cus, bool ragged = false) {
+    if (!ragged && N % c.bn) return 1e30;
+    const long slots = (long)c.wg_per_cu * cus, nt = ((M + c.bm - 1) / c.bm) * col_tiles(N, c.bn, ragged);
     // two workgroups per CU share its matrix pipe — unless the launch has no more tiles than CUs: then every workgroup has a CU to itself
     // (the 60-tile tail of the N = 768 GEMMs as 240 tiles of 128 x 128: 10.6 / 28.8 us against 11.7 / 33.1 us as 256 x 64, K = 768 / 3072)
     const double share = nt <= cus ? 1.0 : (double)c.wg_per_cu;
     return (double)((nt + slots - 1) / slots) * (c.bm / 128.0) * (c.bn / 128.0) * share / c.eff;
 }
-inline int best_cfg(long M, int N, int cus, double* cost_out) {
+inline int best_cfg(long M, int N, int cus, double* cost_out, bool ragged = false, unsigned allowed = ~0u) {
     int pick = -1;
     double best = 1e29;
     for (int i = 0; i < kNumCfgs; ++i) {
-        const double c = tile_cost(kTileCfgs[i], M, N, cus);
+        if (!((allowed >> i) & 1)) continue;
+        const double c = tile_cost(kTileCfgs[i], M, N, cus, ragged);
         if (c < best) { best = c; pick = i; }
     }
     if (cost_out) *cost_out = best;
@@ -490,8 +515,8 @@ inline int best_cfg(long M, int N, int cus, double* cost_out) {
 }
 
 // fewer 128x64 tiles than CUs: the latency-oriented ring kernel (defined below), bit-identical to the persistent kernels
-bool small_applies(int M, int N, int cus);
-int launch_small_one(const half_t* A, int lda, const half_t* B, int ldb, int M, int N, int K, const LinearEpi& epi, hipStream_t s);
+bool small_applies(int M, int N, int cus, bool ragged = false);
+int launch_small_one(const half_t* A, int lda, const half_t* B, int ldb, int M, int N, int K, const LinearEpi& epi, hipStream_t s, bool kt = false);
 
 }  // namespace
 // four-wave 256 x 256 tile with the asm K-loop (pclip_gemm4w.hip)
@@ -499,33 +524,36 @@ bool pclip_gemm4w_supports(int M, int N, int K, int lda, int ldb, int ldc, const
 int pclip_gemm4w_launch(const half_t* A, int lda, const half_t* B, int ldb, int M, int N, int K, const half_t* bias, half_t* C, int ldc, int act,
                         const half_t* residual, int slots, int rev, int band, hipStream_t s);
 namespace {
+// K % 64 != 0 (kt): the KT instantiations of every kernel below (K-tail chunks load zeros); with N % 8 == 0 they also take N ragged against the tile.
+// K % 64 == 0 runs exactly what it ran before.
 int gemm_dispatch(const half_t* A, int lda, const half_t* B, int ldb, int M, int N, int K, LinearEpi epi, int cus, int forced,
                   bool may_split, hipStream_t s) {
+    const bool kt = K % pgemm::BK != 0;
     const bool aligned = (!epi.residual || ((epi.act == 5 || epi.act == 6) && ((uintptr_t)epi.residual & 15) == 0)) && epi.ldc % 8 == 0 && ((uintptr_t)epi.C & 15) == 0 &&
-                         (!epi.bias || ((uintptr_t)epi.bias & 15) == 0);
+                         (!epi.bias || ((uintptr_t)epi.bias & 15) == 0) && (!kt || N % 8 == 0);
     static const bool small_on = !(getenv("PCLIP_GEMM_SMALL") && getenv("PCLIP_GEMM_SMALL")[0] == '0');
-    if (aligned && forced == -1 && small_on && (epi.act <= 1 || epi.act == 6 || (((uintptr_t)epi.scale | (uintptr_t)epi.shift) & 15) == 0) && small_applies(M, N, cus))
-        return launch_small_one(A, lda, B, ldb, M, N, K, epi, s);
+    if (aligned && forced == -1 && small_on && (epi.act <= 1 || epi.act == 6 || (((uintptr_t)epi.scale | (uintptr_t)epi.shift) & 15) == 0) && small_applies(M, N, cus, kt))
+        return launch_small_one(A, lda, B, ldb, M, N, K, epi, s, kt);
     double cost = 1e30;
-    int pick = aligned ? best_cfg(M, N, cus, &cost) : -1;
+    int pick = aligned ? best_cfg(M, N, cus, &cost, kt) : -1;
     if (forced == -2) { may_split = false; pick = -1; }        // generic kernel
     if (epi.act == 5 && pick < 0) { pclip_set_error("pclip_gemm_bn_res_f16: N=%d / alignment not supported by the fused epilogue", N); return PCLIP_E_INVALID; }
     if (forced >= 0) {
         may_split = false;
-        if (aligned && forced < kNumCfgs && N % kTileCfgs[forced].bn == 0) pick = forced;
+        if (aligned && forced < kNumCfgs && (kt || N % kTileCfgs[forced].bn == 0)) pick = forced;
     }
     if (pick >= 0 && may_split) {
         long split_rows = 0;                                   // rows given to the full rounds of configuration split_cfg
         int split_cfg = -1;
         for (int i = 0; i < kNumCfgs; ++i) {
             const TileCfg& c = kTileCfgs[i];
-            if (N % c.bn) continue;
-            const long slots = (long)c.wg_per_cu * cus, tiles_n = N / c.bn, nt = ((M + c.bm - 1) / c.bm) * tiles_n;
+            if (!kt && N % c.bn) continue;
+            const long slots = (long)c.wg_per_cu * cus, tiles_n = col_tiles(N, c.bn, kt), nt = ((M + c.bm - 1) / c.bm) * tiles_n;
             const long full_rows = (nt / slots) * slots / tiles_n * c.bm;
             if (nt <= slots || nt % slots == 0 || full_rows >= M) continue;
             double rest = 1e30;
-            best_cfg(M - full_rows, N, cus, &rest);
-            const double split = tile_cost(c, full_rows, N, cus) + rest + kLaunchCost;
+            best_cfg(M - full_rows, N, cus, &rest, kt);
+            const double split = tile_cost(c, full_rows, N, cus, kt) + rest + kLaunchCost;
             if (split < cost) { cost = split; split_cfg = i; split_rows = full_rows; }
         }
         if (split_cfg >= 0) {
@@ -547,14 +575,17 @@ int gemm_dispatch(const half_t* A, int lda, const half_t* B, int ldb, int M, int
             const bool rev = order.rev == 1 || (order.rev == 2 && K <= 1024);
             return pclip_gemm4w_launch(A, lda, B, ldb, M, N, K, epi.bias, epi.C, epi.ldc, epi.act, epi.residual, cus, rev ? 1 : 0, N / 256 >= 8 ? order.band : order.band_n, s);
         }
-        return launch_fast<CfgBig>(A, lda, B, ldb, M, N, K, epi, cus, s);
+        return launch_fast_k<CfgBig>(kt, A, lda, B, ldb, M, N, K, epi, cus, s);
     }
-    if (pick == 1) return launch_fast<CfgWide>(A, lda, B, ldb, M, N, K, epi, cus, s);
-    if (pick == 0) return launch_fast<CfgSmall>(A, lda, B, ldb, M, N, K, epi, 2 * cus, s);
-    if (pick == 3) return launch_fast<CfgNarrow>(A, lda, B, ldb, M, N, K, epi, cus, s);
-    if (pick == 4) return launch_fast<CfgThin>(A, lda, B, ldb, M, N, K, epi, 2 * cus, s);
+    if (pick == 1) return launch_fast_k<CfgWide>(kt, A, lda, B, ldb, M, N, K, epi, cus, s);
+    if (pick == 0) return launch_fast_k<CfgSmall>(kt, A, lda, B, ldb, M, N, K, epi, 2 * cus, s);
+    if (pick == 3) return launch_fast_k<CfgNarrow>(kt, A, lda, B, ldb, M, N, K, epi, cus, s);
+    if (pick == 4) return launch_fast_k<CfgThin>(kt, A, lda, B, ldb, M, N, K, epi, 2 * cus, s);
     const int tiles_m = ceil_div(M, 128), tiles_n = ceil_div(N, 128);
-    linear_generic_kernel<<<tiles_m * tiles_n, 256, CfgSmall::LDS_BYTES, s>>>(A, lda, B, ldb, M, N, K, epi, tiles_n);
+    if (kt)
+        linear_generic_kernel<true><<<tiles_m * tiles_n, 256, CfgSmall::LDS_BYTES, s>>>(A, lda, B, ldb, M, N, K, epi, tiles_n);
+    else
+        linear_generic_kernel<false><<<tiles_m * tiles_n, 256, CfgSmall::LDS_BYTES, s>>>(A, lda, B, ldb, M, N, K, epi, tiles_n);
     return pclip_check_launch("gemm_f16 (generic)");
 }
 }  // namespace
@@ -563,7 +594,7 @@ extern "C" int pclip_gemm_f16(const void* A, int lda, const void* B, int ldb, vo
                               const void* bias, int act, const void* residual, pclip_stream_t stream) {
     PCLIP_REQUIRE(A && B && C, "pclip_gemm_f16: null pointer");
     PCLIP_REQUIRE(M >= 0 && N > 0 && K > 0, "pclip_gemm_f16: bad shape M=%d N=%d K=%d", M, N, K);
-    PCLIP_REQUIRE(K % pgemm::BK == 0, "pclip_gemm_f16: K=%d must be a multiple of %d", K, pgemm::BK);
+    PCLIP_REQUIRE(K % 8 == 0, "pclip_gemm_f16: K=%d must be a multiple of 8", K);
     PCLIP_REQUIRE(lda >= K && ldb >= K && ldc >= N && lda % 8 == 0 && ldb % 8 == 0, "pclip_gemm_f16: bad leading dims");
     PCLIP_REQUIRE(act == 0 || act == 1, "pclip_gemm_f16: unknown activation %d", act);
     if (M == 0) return PCLIP_OK;
@@ -601,7 +632,9 @@ constexpr int kSmallStages = 4;                             // 6 slots measured 
 constexpr int kSmallLds = kSmallStages * CfgSplit::STAGE_BYTES;        // the K-tile ring of pgemm::mainloop_ring (96 KiB)
 
 // S > 1: slice ks of the K range -> fp32 slab.  S == 1: the whole K range, bias / QuickGELU and the fp16 store right here.
-template <int ACT>
+// ACT_KT set in ACT_FLAGS (S == 1 only): the K-tail instantiation — K % 64 != 0 and N % 8 == 0 ragged against the tile, as linear_fast_kernel.
+constexpr int ACT_KT = 0x100;
+template <int ACT_FLAGS>
 __global__ __launch_bounds__(CfgSplit::NTHREADS, 1) void linear_small_kernel(const half_t* __restrict__ A, int lda,
                                                                            const half_t* __restrict__ B, int ldb, int M, int N,
                                                                            int K, int tiles_n, int S, int steps_per,
@@ -611,6 +644,8 @@ __global__ __launch_bounds__(CfgSplit::NTHREADS, 1) void linear_small_kernel(con
                                                                            const float* __restrict__ shift,
                                                                            const half_t* residual = nullptr, unsigned long long* tslot = nullptr) {
     using C = CfgSplit;
+    constexpr int ACT = ACT_FLAGS & 0xff;
+    constexpr bool KT = (ACT_FLAGS & ACT_KT) != 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     pgemm::time_begin(tslot);                                                 // (measurement hook: null in the product)
     const int tile = blockIdx.x / S, ks = blockIdx.x - tile * S;
@@ -621,19 +656,22 @@ __global__ __launch_bounds__(CfgSplit::NTHREADS, 1) void linear_small_kernel(con
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave / C::WN, wn = wave % C::WN;
     pgemm::Acc<C> acc;
     // S == 1: the bias is the accumulators' initial value exactly as in linear_fast_kernel -> the same bits as that kernel
-    pgemm::mainloop_ring<C, kSmallStages>(A + k0, lda, B + k0, ldb, M, N, klen / pgemm::BK, m0, n0, smem, acc, [&]() {
+    pgemm::mainloop_ring<C, kSmallStages, KT>(A + k0, lda, B + k0, ldb, M, N, KT ? (klen + pgemm::BK - 1) / pgemm::BK : klen / pgemm::BK, m0, n0, smem, acc, [&]() {
 #pragma unroll
         for (int j = 0; j < C::TN; ++j)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 half4_t b = {(half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
-                if (S == 1 && bias) b = *reinterpret_cast<const half4_t*>(bias + n0 + wn * (C::BN / C::WN) + j * 32 + (g & 1) * 16 + 4 * (lane >> 4));
+                if constexpr (KT) {
+                    const int nb = n0 + wn * (C::BN / C::WN) + j * 32 + (g & 1) * 16 + 4 * (lane >> 4);
+                    if (bias && nb < N) b = *reinterpret_cast<const half4_t*>(bias + nb);
+                } else if (S == 1 && bias) b = *reinterpret_cast<const half4_t*>(bias + n0 + wn * (C::BN / C::WN) + j * 32 + (g & 1) * 16 + 4 * (lane >> 4));
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
 #pragma unroll
                     for (int i = 0; i < C::TM; ++i) acc.v[i][j][4 * g + e] = (float)b[e];
             }
-    });
+    }, klen);
     if (S == 1) {
         const int col = n0 + 8 * (tid % C::CPR);
         auto pre = [&](int i, int j, int coff, float4_t v, int rl, int g) {
@@ -641,7 +679,8 @@ __global__ __launch_bounds__(CfgSplit::NTHREADS, 1) void linear_small_kernel(con
             half4_t h;
             if (ACT == 2 || ACT == 3 || ACT == 5) {         // eval BatchNorm (+ReLU) as in linear_fast_kernel: same roundings
                 const int n = n0 + wn * (C::BN / C::WN) + j * 32 + coff;
-                const float4_t sc = *reinterpret_cast<const float4_t*>(scale + n), sh = *reinterpret_cast<const float4_t*>(shift + n);
+                const float4_t z4 = {0.f, 0.f, 0.f, 0.f};
+                const float4_t sc = KT && n >= N ? z4 : *reinterpret_cast<const float4_t*>(scale + n), sh = KT && n >= N ? z4 : *reinterpret_cast<const float4_t*>(shift + n);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float y = r16(r16(v[e]) * sc[e] + sh[e]);
@@ -656,7 +695,7 @@ __global__ __launch_bounds__(CfgSplit::NTHREADS, 1) void linear_small_kernel(con
         };
         // slot 0 of the ring is the staging buffer: the epilogue's first barrier comes after every wave's last K-tile
         pgemm::epilogue_f16<C, true>(acc, smem, [](int) {}, pre, [&](int r, int c, int, half8_t h) {
-            const bool valid = m0 + r < M;
+            const bool valid = KT ? m0 + r < M && col < N : m0 + r < M;
             const size_t o = (size_t)(m0 + r) * ldc + col;
             if ((ACT == 5 || ACT == 6) && valid) {
                 const half8_t rr = ld_half8(residual + o);
@@ -689,20 +728,23 @@ __global__ __launch_bounds__(CfgSplit::NTHREADS, 1) void linear_small_kernel(con
 }
 
 // The implicit-GEMM 3x3 convolution (conv3x3_fast_kernel) for launches with no more tiles than CUs: the same gather, the ring
-// K-loop, the same BatchNorm (+ReLU) epilogue — bit-identical to the persistent kernel.
-template <int ACT>
+// K-loop, the same BatchNorm (+ReLU) epilogue — bit-identical to the persistent kernel.  ACT_KT set in ACT_FLAGS: the channel-tail instantiation
+// (TAIL of conv3x3_fast_kernel).
+template <int ACT_FLAGS>
 __global__ __launch_bounds__(CfgSplit::NTHREADS, 1) void conv3x3_small_kernel(const half_t* __restrict__ x,
                                                                             const half_t* __restrict__ w, int H, int W, int Cin, int M,
                                                                             int N, const float* __restrict__ scale,
                                                                             const float* __restrict__ shift, half_t* __restrict__ Cout,
                                                                             int tiles_n) {
     using C = CfgSplit;
+    constexpr int ACT = ACT_FLAGS & 0xff;
+    constexpr bool TAIL = (ACT_FLAGS & ACT_KT) != 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tile_m = blockIdx.x / tiles_n, tile_n = blockIdx.x - tile_m * tiles_n;
     const int m0 = tile_m * C::BM, n0 = tile_n * C::BN;
     const int nt = (9 * Cin + pgemm::BK - 1) / pgemm::BK, K = nt * pgemm::BK;       // w rows are zero-padded to the K-tile (Cin < 64)
     const int tid = threadIdx.x, wave = tid >> 6, wn = wave % C::WN;
-    pgemm::ConvGather<C> ga(x, H, W, Cin, M);
+    pgemm::ConvGather<C, TAIL> ga(x, H, W, Cin, M);
     ga.prepare(m0);
     pgemm::Acc<C> acc;
     pgemm::mainloop_ring_g<C, kSmallStages>([&](int t, char* dst) { ga.stage(t, dst); }, w, K, N, nt, n0, smem, acc, [&]() {
@@ -716,7 +758,8 @@ __global__ __launch_bounds__(CfgSplit::NTHREADS, 1) void conv3x3_small_kernel(co
     const int col = n0 + 8 * (tid % C::CPR);
     auto pre = [&](int, int j, int coff, float4_t v, int rl, int g) {
         const int n = n0 + wn * (C::BN / C::WN) + j * 32 + coff;
-        const float4_t sc = *reinterpret_cast<const float4_t*>(scale + n), sh = *reinterpret_cast<const float4_t*>(shift + n);
+        const float4_t z4 = {0.f, 0.f, 0.f, 0.f};
+        const float4_t sc = TAIL && n >= N ? z4 : *reinterpret_cast<const float4_t*>(scale + n), sh = TAIL && n >= N ? z4 : *reinterpret_cast<const float4_t*>(shift + n);
         half4_t h;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -727,9 +770,10 @@ __global__ __launch_bounds__(CfgSplit::NTHREADS, 1) void conv3x3_small_kernel(co
         return h;
     };
     pgemm::epilogue_f16<C, true>(acc, smem, [](int) {}, pre, [&](int r, int, int, half8_t h) {
-        if (m0 + r < M) st_half8(Cout + (size_t)(m0 + r) * N + col, h);
+        if (TAIL ? m0 + r < M && col < N : m0 + r < M) st_half8(Cout + (size_t)(m0 + r) * N + col, h);
     });
 }
+
 
 // out[m, n .. n+7] = act(sum_s slab[s][m][n ..] + bias[n ..]) — slices added in order, one thread per 8 columns
 template <int ACT>
@@ -766,7 +810,10 @@ inline int small_attr() {
     if (!done.done()) {
         const void* fns[] = {(const void*)linear_small_kernel<0>, (const void*)linear_small_kernel<1>, (const void*)linear_small_kernel<2>,
                              (const void*)linear_small_kernel<3>, (const void*)linear_small_kernel<5>, (const void*)linear_small_kernel<6>,
-                             (const void*)linear_small_kernel<7>, (const void*)linear_small_kernel<8>, (const void*)linear_small_kernel<9>, (const void*)conv3x3_small_kernel<2>, (const void*)conv3x3_small_kernel<3>};
+                             (const void*)linear_small_kernel<7>, (const void*)linear_small_kernel<8>, (const void*)linear_small_kernel<9>, (const void*)conv3x3_small_kernel<2>, (const void*)conv3x3_small_kernel<3>,
+                             (const void*)linear_small_kernel<0 | ACT_KT>, (const void*)linear_small_kernel<1 | ACT_KT>, (const void*)linear_small_kernel<2 | ACT_KT>,
+                             (const void*)linear_small_kernel<3 | ACT_KT>, (const void*)linear_small_kernel<5 | ACT_KT>, (const void*)linear_small_kernel<6 | ACT_KT>,
+                             (const void*)conv3x3_small_kernel<2 | ACT_KT>, (const void*)conv3x3_small_kernel<3 | ACT_KT>};
         for (const void* f : fns)
             if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kSmallLds) != hipSuccess) {
                 pclip_set_error("gemm_f16 (small M): cannot raise the dynamic LDS limit to %d", kSmallLds);
@@ -777,15 +824,28 @@ inline int small_attr() {
     return PCLIP_OK;
 }
 
-bool small_applies(int M, int N, int cus) {
-    return M > 0 && N % CfgSplit::BN == 0 && (long)ceil_div(M, CfgSplit::BM) * (N / CfgSplit::BN) <= cus;
+bool small_applies(int M, int N, int cus, bool ragged) {
+    return M > 0 && (ragged || N % CfgSplit::BN == 0) && (long)ceil_div(M, CfgSplit::BM) * col_tiles(N, CfgSplit::BN, ragged) <= cus;
 }
 
-int launch_small_one(const half_t* A, int lda, const half_t* B, int ldb, int M, int N, int K, const LinearEpi& epi, hipStream_t s) {
+int launch_small_one(const half_t* A, int lda, const half_t* B, int ldb, int M, int N, int K, const LinearEpi& epi, hipStream_t s, bool kt) {
     if (int e = small_attr()) return e;
-    const int tiles_n = N / CfgSplit::BN, grid = ceil_div(M, CfgSplit::BM) * tiles_n, steps = K / pgemm::BK;
+    const int tiles_n = kt ? ceil_div(N, CfgSplit::BN) : N / CfgSplit::BN, grid = ceil_div(M, CfgSplit::BM) * tiles_n, steps = K / pgemm::BK;
     ++g_gemm_launches;
     unsigned long long* tslot = pclip_gemm_time_slot();
+    if (kt) {                                                   // K % 64 != 0: the KT instantiation (no split-K: S == 1)
+#define PCLIP_SMALL_KT_LAUNCH(ACT)                                                                                                      \
+        linear_small_kernel<ACT | ACT_KT><<<grid, CfgSplit::NTHREADS, kSmallLds, s>>>(A, lda, B, ldb, M, N, K, tiles_n, 1, ceil_div(K, pgemm::BK), nullptr, \
+                                                                                  epi.bias, epi.C, epi.ldc, epi.scale, epi.shift, epi.residual, tslot)
+        if (epi.act == 5) PCLIP_SMALL_KT_LAUNCH(5);
+        else if (epi.act == 6) PCLIP_SMALL_KT_LAUNCH(6);
+        else if (epi.act == 1) PCLIP_SMALL_KT_LAUNCH(1);
+        else if (epi.act == 2) PCLIP_SMALL_KT_LAUNCH(2);
+        else if (epi.act == 3) PCLIP_SMALL_KT_LAUNCH(3);
+        else PCLIP_SMALL_KT_LAUNCH(0);
+#undef PCLIP_SMALL_KT_LAUNCH
+        return pclip_check_launch("gemm_f16 (small M)");
+    }
 #define PCLIP_SMALL_LAUNCH(ACT)                                                                                                          \
     linear_small_kernel<ACT><<<grid, CfgSplit::NTHREADS, kSmallLds, s>>>(A, lda, B, ldb, M, N, K, tiles_n, 1, steps, nullptr, epi.bias, epi.C, \
                                                                         epi.ldc, epi.scale, epi.shift, epi.residual, tslot)
@@ -862,7 +922,7 @@ extern "C" int pclip_gemm_bn_res_f16(const void* A, int lda, const void* B, int 
                                      const float* scale, const float* shift, const void* residual, pclip_stream_t stream) {
     PCLIP_REQUIRE(A && B && C && scale && shift && residual, "pclip_gemm_bn_res_f16: null pointer");
     PCLIP_REQUIRE(M >= 0 && N > 0 && K > 0, "pclip_gemm_bn_res_f16: bad shape M=%d N=%d K=%d", M, N, K);
-    PCLIP_REQUIRE(K % pgemm::BK == 0 && N % 64 == 0, "pclip_gemm_bn_res_f16: K=%d, N=%d must be multiples of 64", K, N);
+    PCLIP_REQUIRE(K % 8 == 0 && N % 64 == 0, "pclip_gemm_bn_res_f16: K=%d must be a multiple of 8 and N=%d a multiple of 64", K, N);
     PCLIP_REQUIRE(lda >= K && ldb >= K && ldc >= N && lda % 8 == 0 && ldb % 8 == 0, "pclip_gemm_bn_res_f16: bad leading dims");
     PCLIP_REQUIRE(((uintptr_t)scale & 15) == 0 && ((uintptr_t)shift & 15) == 0, "pclip_gemm_bn_res_f16: scale / shift must be 16-byte aligned");
     if (M == 0) return PCLIP_OK;
@@ -876,7 +936,7 @@ extern "C" int pclip_gemm_bn_f16(const void* A, int lda, const void* B, int ldb,
                                  const float* scale, const float* shift, int relu, pclip_stream_t stream) {
     PCLIP_REQUIRE(A && B && C && scale && shift, "pclip_gemm_bn_f16: null pointer");
     PCLIP_REQUIRE(M >= 0 && N > 0 && K > 0, "pclip_gemm_bn_f16: bad shape M=%d N=%d K=%d", M, N, K);
-    PCLIP_REQUIRE(K % pgemm::BK == 0, "pclip_gemm_bn_f16: K=%d must be a multiple of %d", K, pgemm::BK);
+    PCLIP_REQUIRE(K % 8 == 0, "pclip_gemm_bn_f16: K=%d must be a multiple of 8", K);
     PCLIP_REQUIRE(lda >= K && ldb >= K && ldc >= N && lda % 8 == 0 && ldb % 8 == 0, "pclip_gemm_bn_f16: bad leading dims");
     if (M == 0) return PCLIP_OK;
     LinearEpi epi{nullptr, nullptr, (half_t*)C, ldc, relu ? 3 : 2, scale, shift};
@@ -887,28 +947,56 @@ extern "C" int pclip_gemm_bn_f16(const void* A, int lda, const void* B, int ldb,
 }
 
 namespace {
-template <class C, int ACT>
+// TAIL: the tail instantiation of conv3x3_fast_kernel (any Cin % 8 == 0, Cout % 8 == 0 as ceil(Cout / BN) column tiles)
+template <class C, int ACT, bool TAIL>
 int launch_conv2(const void* x, const void* w, int B, int H, int W, int Cin, int Cout, const float* scale,
                  const float* shift, void* y, int slots, hipStream_t s) {
     static DevOnce attr;
     constexpr int LDS = C::LDS_BYTES + 2 * 2 * C::BN * 4;
+    using CK = std::conditional_t<TAIL, pgemm::Tail<C>, C>;
+    const void* fn = (const void*)conv3x3_fast_kernel<CK, ACT>;
     if (!attr.done()) {
-        if (hipFuncSetAttribute((const void*)conv3x3_fast_kernel<C, ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
             pclip_set_error("pclip_conv3x3_bn_f16: cannot raise the dynamic LDS limit to %d", LDS);
             return PCLIP_E_LAUNCH;
         }
         attr.set();
     }
-    const int M = B * H * W, tiles_m = ceil_div(M, C::BM), tiles_n = Cout / C::BN, ntiles = tiles_m * tiles_n;
-    conv3x3_fast_kernel<C, ACT><<<ntiles < slots ? ntiles : slots, C::NTHREADS, LDS, s>>>(
+    const int M = B * H * W, tiles_m = ceil_div(M, C::BM), tiles_n = TAIL ? ceil_div(Cout, C::BN) : Cout / C::BN, ntiles = tiles_m * tiles_n;
+    conv3x3_fast_kernel<CK, ACT><<<ntiles < slots ? ntiles : slots, C::NTHREADS, LDS, s>>>(
         (const half_t*)x, (const half_t*)w, H, W, Cin, M, Cout, scale, shift, (half_t*)y, tiles_n, ntiles);
     return pclip_check_launch("conv3x3_bn");
 }
-template <class C>
+template <class C, bool TAIL = false>
 int launch_conv(const void* x, const void* w, int B, int H, int W, int Cin, int Cout, const float* scale,
                 const float* shift, int relu, void* y, int slots, hipStream_t s) {
-    return relu ? launch_conv2<C, 3>(x, w, B, H, W, Cin, Cout, scale, shift, y, slots, s)
-                : launch_conv2<C, 2>(x, w, B, H, W, Cin, Cout, scale, shift, y, slots, s);
+    return relu ? launch_conv2<C, 3, TAIL>(x, w, B, H, W, Cin, Cout, scale, shift, y, slots, s)
+                : launch_conv2<C, 2, TAIL>(x, w, B, H, W, Cin, Cout, scale, shift, y, slots, s);
+}
+
+// Cin outside {8, 16, 32, 64k} or Cout outside {32, 64k} (RN50x4 / RN50x16: 40, 48, 80, 96, 160 channels): the TAIL instantiations, chosen by the shape alone.
+// Tiles: the cost model over ceil(Cout / BN) column tiles, among 128x128, 256x128, 256x64 and 256x32 (the 256x256 tile is not instantiated for the tail).
+int conv3x3_tail_dispatch(const void* x, const void* w, int B, int H, int W, int Cin, int Cout, const float* scale, const float* shift, int relu,
+                          void* y, int cus, hipStream_t s) {
+    const int M = B * H * W;
+    static const bool small_on = !(getenv("PCLIP_GEMM_SMALL") && getenv("PCLIP_GEMM_SMALL")[0] == '0');
+    if (small_on && small_applies(M, Cout, cus, true)) {                        // a request of a few images: the ring kernel
+        if (int e = small_attr()) return e;
+        const int tiles_n = ceil_div(Cout, CfgSplit::BN), grid = ceil_div(M, CfgSplit::BM) * tiles_n;
+        if (relu)
+            conv3x3_small_kernel<3 | ACT_KT><<<grid, CfgSplit::NTHREADS, kSmallLds, s>>>((const half_t*)x, (const half_t*)w, H, W, Cin, M, Cout, scale, shift,
+                                                                                   (half_t*)y, tiles_n);
+        else
+            conv3x3_small_kernel<2 | ACT_KT><<<grid, CfgSplit::NTHREADS, kSmallLds, s>>>((const half_t*)x, (const half_t*)w, H, W, Cin, M, Cout, scale, shift,
+                                                                                   (half_t*)y, tiles_n);
+        return pclip_check_launch("conv3x3_bn (small M)");
+    }
+    double cost;
+    const int pick = best_cfg(M, Cout, cus, &cost, true, (1u << 0) | (1u << 1) | (1u << 3) | (1u << 4));
+    if (pick == 1) return launch_conv<CfgWide, true>(x, w, B, H, W, Cin, Cout, scale, shift, relu, y, cus, s);
+    if (pick == 0) return launch_conv<CfgSmall, true>(x, w, B, H, W, Cin, Cout, scale, shift, relu, y, 2 * cus, s);
+    if (pick == 4) return launch_conv<CfgThin, true>(x, w, B, H, W, Cin, Cout, scale, shift, relu, y, 2 * cus, s);
+    return launch_conv<CfgNarrow, true>(x, w, B, H, W, Cin, Cout, scale, shift, relu, y, cus, s);
 }
 }  // namespace
 
@@ -921,8 +1009,8 @@ extern "C" int pclip_conv3x3_bn_f16(const void* x, const void* w, const void* ze
                                     const float* scale, const float* shift, int relu, void* y, pclip_stream_t stream) {
     PCLIP_REQUIRE(x && w && zero_line && scale && shift && y, "pclip_conv3x3_bn_f16: null pointer");
     PCLIP_REQUIRE(B >= 0 && H > 0 && W > 0 && H < 32768 && W < 32768, "pclip_conv3x3_bn_f16: bad shape B=%d H=%d W=%d", B, H, W);
-    PCLIP_REQUIRE(Cin > 0 && (Cin % 64 == 0 || Cin == 8 || Cin == 16 || Cin == 32), "pclip_conv3x3_bn_f16: Cin=%d must be a multiple of 64, or 8 / 16 / 32 (use im2col + pclip_gemm_bn_f16 otherwise)", Cin);
-    PCLIP_REQUIRE(Cout > 0 && (Cout % 64 == 0 || Cout == 32), "pclip_conv3x3_bn_f16: Cout=%d must be a multiple of 64, or 32", Cout);
+    PCLIP_REQUIRE(Cin > 0 && Cin % 8 == 0, "pclip_conv3x3_bn_f16: Cin=%d must be a multiple of 8 (use im2col + pclip_gemm_bn_f16 otherwise)", Cin);
+    PCLIP_REQUIRE(Cout > 0 && Cout % 8 == 0, "pclip_conv3x3_bn_f16: Cout=%d must be a multiple of 8", Cout);
     PCLIP_REQUIRE((long)B * H * W < (1L << 31) / 1, "pclip_conv3x3_bn_f16: too many output pixels");
     PCLIP_REQUIRE(((uintptr_t)scale & 15) == 0 && ((uintptr_t)shift & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)x & 15) == 0,
                   "pclip_conv3x3_bn_f16: pointers must be 16-byte aligned");
@@ -943,6 +1031,8 @@ extern "C" int pclip_conv3x3_bn_f16(const void* x, const void* w, const void* ze
         }
         return PCLIP_OK;
     }
+    if (!((Cin % 64 == 0 || Cin == 8 || Cin == 16 || Cin == 32) && (Cout % 64 == 0 || Cout == 32)))
+        return conv3x3_tail_dispatch(x, w, B, H, W, Cin, Cout, scale, shift, relu, y, cus, s);
     if (pclip_conv3x3_strip_applies(B, H, W, Cin, Cout))                        // narrow layers at 56 x 56 / 112 x 112: weights in registers, halo blocks in LDS
         return pclip_conv3x3_strip_launch(x, w, B, H, W, Cin, Cout, scale, shift, relu, y, cus, s, 1);
     if (Cout == 32)                                                             // the stem's 32 -> 32 convolution: 256 x 32 tiles

@@ -373,7 +373,8 @@ def adapter_conv(x, three_x: bool, conv1, ln1w, ln1b, conv2, ln2w, ln2b, conv3, 
 # ---- encoder building blocks -------------------------------------------------------------------
 
 def gemm(a, w, bias=None, act: int = 0, residual=None, out=None):
-    """out[M,N] = epilogue(a[M,K] @ w[N,K]^T) — nn.Linear with fused bias/QuickGELU/residual."""
+    """out[M,N] = epilogue(a[M,K] @ w[N,K]^T) — nn.Linear with fused bias/QuickGELU/residual.  K a multiple of 8 (K % 64 != 0 runs
+    the K-tail instantiations: the columns beyond K are never read)."""
     require_cuda(a, w)
     M, K = a.shape
     N = w.shape[0]
@@ -448,7 +449,7 @@ class low_latency:
 
 def gemm_bn(a, w, scale, shift, relu: bool = True, out=None):
     """relu?(bn(a @ w.T)) with eval-mode BatchNorm folded to fp32 per-column scale / shift — conv + bn (+ relu) of the ResNet
-    tower in one launch (clip/model.py:43-52)."""
+    tower in one launch (clip/model.py:43-52).  K a multiple of 8."""
     require_cuda(a, w, scale, shift)
     a, w = _f16c(a), _f16c(w)
     M, K = a.shape
@@ -462,14 +463,14 @@ def gemm_bn(a, w, scale, shift, relu: bool = True, out=None):
 
 def gemm_bn_res_relu(a, w, scale, shift, residual, out=None):
     """relu(bn(a @ w.T) + residual): conv3 + bn3 + identity add + ReLU of a bottleneck in one launch where the fused epilogue
-    applies (N % 64 == 0, aligned operands), otherwise GEMM followed by bn_act — the same values either way."""
+    applies (N % 64 == 0, K % 8 == 0, aligned operands), otherwise GEMM followed by bn_act — the same values either way."""
     require_cuda(a, w, scale, shift, residual)
     a, w, residual = _f16c(a), _f16c(w), _f16c(residual)
     M, K = a.shape
     N = w.shape[0]
     if out is None:
         out = torch.empty(M, N, dtype=torch.float16, device=a.device)
-    if N % 64 == 0 and K % 64 == 0 and not ((a.data_ptr() | w.data_ptr() | out.data_ptr() | residual.data_ptr() | scale.data_ptr() | shift.data_ptr()) & 15):
+    if N % 64 == 0 and K % 8 == 0 and not ((a.data_ptr() | w.data_ptr() | out.data_ptr() | residual.data_ptr() | scale.data_ptr() | shift.data_ptr()) & 15):
         check(_lib.load().pclip_gemm_bn_res_f16(ptr(a), K, ptr(w), w.shape[1], ptr(out), N, M, N, K, ptr(scale), ptr(shift), ptr(residual),
                                                 stream()), "pclip_gemm_bn_res_f16")
         return out
@@ -482,8 +483,8 @@ _zero_line = {}
 
 def conv3x3_bn(x, w, scale, shift, B: int, H: int, W: int, Cin: int, relu: bool = True):
     """relu?(bn(conv3x3(x))) (stride 1, pad 1) on NHWC rows x [B*H*W, Cin] with w [Cout, 9*Cin] in (ky, kx, Cin) order:
-    implicit GEMM, no im2col buffer.  Cin a multiple of 64 — or 8 / 16 / 32 with the rows of w zero-padded to a multiple of 64 —
-    and Cout a multiple of 64."""
+    implicit GEMM, no im2col buffer.  Cin and Cout multiples of 8; the rows of w are zero-padded to a multiple of 64 (round_up(9 Cin, 64)
+    columns).  Cin outside {8, 16, 32, 64k} or Cout outside {32, 64k} run the convolution's tail instantiations (RN50x4 / RN50x16)."""
     require_cuda(x, w, scale, shift)
     x, w = _f16c(x), _f16c(w)
     Cout = w.shape[0]
