@@ -108,41 +108,54 @@ int pclip_fuse_probs(const float* d2i, const float* d2t, int Q, int N, int ldd, 
 
 /* Convenience: pclip_sqdist_f16 + pclip_fuse_probs with the distance rows held in `ws` (or one of the one-launch routes, pclip_classify_route).  N <= 4096 on every
  * route (PCLIP_E_INVALID beyond).  Pass ws_bytes = pclip_workspace_bytes(PCLIP_OP_CLASSIFY, Q, N, D) — that size, not a larger buffer's, keeps the route a function of the
- * shape and the routing settings, the one pclip_classify_route reports (the fused row panels run only if their scratch fits in ws_bytes). */
+ * shape and the flags, the one pclip_classify_route reports (the fused row panels run only if their scratch fits in ws_bytes).  pclip_classify_f16 = flags 0. */
 int pclip_classify_f16(const void* q, const void* zi, const void* zt, int Q, int N, int D,
                        const float* q_sq, const float* zi_sq, const float* zt_sq, float alpha,
                        float one_minus_alpha, float beta, float* p, int32_t* argmax, float* topk_p,
                        int32_t* topk_i, int k, void* ws, size_t ws_bytes, pclip_stream_t stream);
+int pclip_classify_ex_f16(const void* q, const void* zi, const void* zt, int Q, int N, int D,
+                          const float* q_sq, const float* zi_sq, const float* zt_sq, float alpha,
+                          float one_minus_alpha, float beta, float* p, int32_t* argmax, float* topk_p,
+                          int32_t* topk_i, int k, int flags, void* ws, size_t ws_bytes, pclip_stream_t stream);
 
-/* The route pclip_classify_f16 takes for a call of this shape under the current settings: 0 = two stages (pclip_sqdist_f16 + pclip_fuse_probs), 1 = one launch for
- * small class counts (N <= 16; N <= 32 with top-k), 2 = one launch for 16 < N <= 256, 3 = fused row panels (argmax only, Q N large).  The routes agree with the
- * reference's p to 1e-5 and with each other up to fp32 summation order: a query whose top two classes are closer than ~1e-6 in p may get either of them depending
- * on the route, i.e. on the batch it is classified in.  Callers that need one arithmetic for every batch size force the two stages (pclip_classify_mid_config(0),
- * pclip_classify_panel_config(0), env PCLIP_CLASSIFY_SMALL=0).  ws_bytes: the workspace the call would pass. */
+/* Routing flags of one classification call (0 = the default routing).  Unknown bits and the contradictory pairs NO_MID | FORCE_MID, NO_PANELS | FORCE_PANELS and
+ * PANEL_TWO_PASS | PANEL_FORCE_SECOND are refused (PCLIP_E_INVALID).
+ *   NO_SMALL          no one-launch kernel for small class counts
+ *   NO_MID            no one-launch kernel for mid-sized class counts; FORCE_MID: it takes every shape it can run (tests), not only 16 < N <= 256 with Q N <= 2e6
+ *   NO_PANELS         no fused row panels; FORCE_PANELS: they take every argmax-only shape they can run (tests), not only those with half a 256-query panel per CU
+ *   PANEL_TWO_PASS    the row panels walk the class tiles twice always instead of one pass + candidates (pclip_classify_panel_stats)
+ *   PANEL_FORCE_SECOND  candidates computed but every panel sent through the second pass (tests)
+ *   PANEL_EXACT       the row panels keep torch.cdist's sqrt -> square round trip (bit-identical distances; a third slower)
+ * NO_SMALL | NO_MID | NO_PANELS: the two stages, torch.cdist's arithmetic, for every shape. */
+#define PCLIP_CLASSIFY_NO_SMALL 0x1
+#define PCLIP_CLASSIFY_NO_MID 0x2
+#define PCLIP_CLASSIFY_FORCE_MID 0x4
+#define PCLIP_CLASSIFY_NO_PANELS 0x8
+#define PCLIP_CLASSIFY_FORCE_PANELS 0x10
+#define PCLIP_CLASSIFY_PANEL_TWO_PASS 0x20
+#define PCLIP_CLASSIFY_PANEL_FORCE_SECOND 0x40
+#define PCLIP_CLASSIFY_PANEL_EXACT 0x80
+
+/* The route pclip_classify_ex_f16 takes for a call of this shape and these flags: 0 = two stages (pclip_sqdist_f16 + pclip_fuse_probs), 1 = one launch for
+ * small class counts (N <= 16; N <= 32 with top-k), 2 = one launch for 16 < N <= 256, 3 = fused row panels (argmax only, Q N large); PCLIP_E_INVALID for bad flags.
+ * The routes agree with the reference's p to 1e-5 and with each other up to fp32 summation order: a query whose top two classes are closer than ~1e-6 in p may get
+ * either of them depending on the route, i.e. on the batch it is classified in.  Callers that need one arithmetic for every batch size force the two stages
+ * (flags NO_SMALL | NO_MID | NO_PANELS).  ws_bytes: the workspace the call would pass.  pclip_classify_route = flags 0. */
 int pclip_classify_route(int Q, int N, int D, float alpha, float one_minus_alpha, float beta, int has_zt, int want_p, int want_argmax, int topk, size_t ws_bytes);
+int pclip_classify_route_ex(int Q, int N, int D, float alpha, float one_minus_alpha, float beta, int has_zt, int want_p, int want_argmax, int topk, int flags,
+                            size_t ws_bytes);
 
 /* The fused row-panel classification walks the class tiles ONCE where it can prove the result (csrc/pclip_classify_panel.hip: per group of 16 classes the nearest
  * class of each bank is kept as a candidate, everybody else is bounded through the group's second smallest distances; a panel whose rows all satisfy
  * max bound < best candidate is finished from the candidates — the very argmax of the second pass — and only the others walk the tiles again).
- * pclip_classify_panel_passes: 0 = that (default; env PCLIP_CLASSIFY_PANEL_PASSES), 1 = always two passes (round 5's first form), 2 = candidates computed but every panel
- * sent through the second pass (tests); returns the previous mode, a negative argument only queries.  pclip_classify_panel_stats: out3[0] = panels classified,
- * out3[1] = panels that needed a second pass, out3[2] = class tiles those second passes walked (a second pass covers only the tiles that hold a bound the proof
- * could not beat), since the last reset (host pointer to three ints; synchronises the device). */
-int pclip_classify_panel_passes(int mode);
+ * pclip_classify_panel_stats: out3[0] = panels classified, out3[1] = panels that needed a second pass, out3[2] = class tiles those second passes walked (a second
+ * pass covers only the tiles that hold a bound the proof could not beat), since the last reset (host pointer to three ints; synchronises the device). */
 int pclip_classify_panel_stats(int* out3, int reset);
-
-/* One-launch classification for mid-sized class counts (csrc/pclip_classify_mid.hip; utils.py:225-244 + main.py:190): pclip_classify_f16 takes it by itself for
- * 16 < N <= 256 with both banks, D % 128 == 0, p and / or argmax (no top-k), Q N <= 2e6.  mode 1 = that routing (default; env PCLIP_CLASSIFY_MID), 2 = every shape the kernel can
- * run (tests), 0 = off (two stages), < 0 = query only.  Returns the previous setting (-1 = not decided yet). */
-int pclip_classify_mid_config(int mode);
 
 /* Test entry of the fused large-N classification (csrc/pclip_classify_panel.hip; pclip_classify_f16 takes that path by itself for N > 32 when only the argmax is
  * asked for): the distances it forms for its first tile — dump [2][256][128] fp32 = d2 of query rows 0..255 x classes 0..127, visual bank then textual bank —
- * with exact != 0 (torch.cdist's sqrt -> square round trip kept: PCLIP_CLASSIFY_PANEL_EXACT=1) they must be the bits pclip_sqdist_f16 writes (utils.py:230-233),
+ * with exact != 0 (torch.cdist's sqrt -> square round trip kept, as PCLIP_CLASSIFY_PANEL_EXACT) they must be the bits pclip_sqdist_f16 writes (utils.py:230-233),
  * with exact == 0 (the product's arithmetic: max(v, 0), a third faster) within one fp32 ulp of them.  ws as for pclip_classify_f16. */
-/* Routing of pclip_classify_f16's argmax-only calls with N > 32: mode 1 = fused row-panel kernel where the call has at least half a 256-query panel per CU (default; env
- * PCLIP_CLASSIFY_PANEL), 2 = for every shape it can run (tests), 0 = the two stages, < 0 = query only.  Returns the previous setting (-1 = not decided yet). */
-int pclip_classify_panel_config(int mode);
 int pclip_classify_panel_dump_f16(const void* q, const void* zi, const void* zt, int Q, int N, int D, float* dump, int exact,
                                   void* ws, size_t ws_bytes, pclip_stream_t stream);
 
@@ -456,8 +469,8 @@ int pclip_preprocess_u8(const void* const* srcs, const int32_t* desc, int B, int
                         float mean2, float std0, float std1, float std2, void* out, int out_f16, void* ws, pclip_stream_t stream);
 
 /* ---- workspace sizing -------------------------------------------------------------------- */
-/* PCLIP_OP_CLASSIFY: the two-stage distance rows (the least pclip_classify_f16 accepts), or the fused row panels' scratch where that is larger and the routing may
- * send the shape there (forced routing at small Q) — so depends on pclip_classify_panel_config as well as on the shape. */
+/* PCLIP_OP_CLASSIFY: the two-stage distance rows (the least pclip_classify_f16 accepts), or the fused row panels' scratch where that is larger and
+ * PCLIP_CLASSIFY_FORCE_PANELS could send the shape there (small Q) — a function of the shape alone. */
 #define PCLIP_OP_SQDIST 1
 #define PCLIP_OP_CLASSIFY 2
 #define PCLIP_OP_ADAPTER_FC 3

@@ -11,6 +11,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpclip.so")
 
 OP_SQDIST, OP_CLASSIFY, OP_ADAPTER_FC = 1, 2, 3
+# routing flags of pclip_classify_ex_f16 / pclip_classify_route_ex (include/pclip.h)
+CLASSIFY_NO_SMALL, CLASSIFY_NO_MID, CLASSIFY_FORCE_MID, CLASSIFY_NO_PANELS, CLASSIFY_FORCE_PANELS = 0x1, 0x2, 0x4, 0x8, 0x10
+CLASSIFY_PANEL_TWO_PASS, CLASSIFY_PANEL_FORCE_SECOND, CLASSIFY_PANEL_EXACT = 0x20, 0x40, 0x80
 
 
 class PclipError(RuntimeError):
@@ -38,14 +41,14 @@ _SIGS = {
     "pclip_fuse_probs": [_P, _P, c_int, c_int, c_int, c_float, c_float, c_float, _P, _P, _P, _P, c_int, _P],
     "pclip_classify_f16": [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_float, c_float, c_float, _P, _P, _P,
                            _P, c_int, _P, c_size_t, _P],
-    "pclip_classify_panel_config": [c_int],
-    "pclip_classify_panel_passes": [c_int],
+    "pclip_classify_ex_f16": [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_float, c_float, c_float, _P, _P, _P,
+                              _P, c_int, c_int, _P, c_size_t, _P],
     "pclip_classify_panel_stats": [_P, c_int],
     "pclip_classify_panel_dump_f16": [_P, _P, _P, c_int, c_int, c_int, _P, c_int, _P, c_size_t, _P],
     "pclip_gemm_timing": [_P, c_int],
     "pclip_gemm_timing_count": [],
     "pclip_classify_route": [c_int, c_int, c_int, c_float, c_float, c_float, c_int, c_int, c_int, c_int, c_size_t],
-    "pclip_classify_mid_config": [c_int],
+    "pclip_classify_route_ex": [c_int, c_int, c_int, c_float, c_float, c_float, c_int, c_int, c_int, c_int, c_int, c_size_t],
     "pclip_hp_sweep": [_P, _P, _P, c_int, c_int, c_int, _P, _P, c_int, _P, c_int, _P, _P],
     "pclip_adapter_fc_f16": [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_float, c_float, c_int, _P, _P, _P,
                              c_size_t, _P],

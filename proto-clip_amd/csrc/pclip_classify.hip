@@ -4,16 +4,15 @@
 //  — are produced once by the MFMA contraction and then consumed by cheap VALU passes.
 #include "pclip_gemm.h"
 #include "pclip_classify_small.h"
-#include <stdlib.h>
 
 // fused row-panel classification for large class counts (pclip_classify_panel.hip)
 size_t pclip_classify_panel_workspace(int Q, int N, int D);
-bool pclip_classify_panel_applies(int Q, int N, int D, float alpha, float one_minus_alpha, float beta);
-bool pclip_classify_mid_applies(int Q, int N, int D, bool has_zt, bool topk);
+bool pclip_classify_panel_applies(int Q, int N, int D, float alpha, float one_minus_alpha, float beta, bool force);
+bool pclip_classify_mid_applies(int Q, int N, int D, bool has_zt, bool topk, bool force);
 int pclip_classify_mid_launch(const void* q, const void* zi, const void* zt, int Q, int N, int D, float alpha, float oma, float beta, float* p, int32_t* argmax,
                               hipStream_t s);
 int pclip_classify_panel_launch(const void* q, const void* zi, const void* zt, int Q, int N, int D, const float* q_sq, const float* zi_sq, const float* zt_sq,
-                                float alpha, float oma, float beta, int32_t* argmax, float* dump, bool dump_exact, void* ws, hipStream_t s);
+                                float alpha, float oma, float beta, int32_t* argmax, float* dump, int passes, bool exact, void* ws, hipStream_t s);
 
 namespace {
 
@@ -453,6 +452,34 @@ inline int padded_ld(int N) { return (N + 63) / 64 * 64; }
 // what every route of pclip_classify_f16 can work in: the norms and the two stages' distance rows
 inline size_t classify_rows_bytes(int Q, int N) { return carve_sq(nullptr, Q, N).bytes + 2 * align_up((size_t)Q * padded_ld(N) * 4, 256); }
 
+constexpr int ALL_FLAGS = PCLIP_CLASSIFY_NO_SMALL | PCLIP_CLASSIFY_NO_MID | PCLIP_CLASSIFY_FORCE_MID | PCLIP_CLASSIFY_NO_PANELS | PCLIP_CLASSIFY_FORCE_PANELS |
+                          PCLIP_CLASSIFY_PANEL_TWO_PASS | PCLIP_CLASSIFY_PANEL_FORCE_SECOND | PCLIP_CLASSIFY_PANEL_EXACT;
+inline bool flags_valid(int f) {
+    auto both = [f](int a, int b) { return (f & a) && (f & b); };
+    return !(f & ~ALL_FLAGS) && !both(PCLIP_CLASSIFY_NO_MID, PCLIP_CLASSIFY_FORCE_MID) && !both(PCLIP_CLASSIFY_NO_PANELS, PCLIP_CLASSIFY_FORCE_PANELS) &&
+           !both(PCLIP_CLASSIFY_PANEL_TWO_PASS, PCLIP_CLASSIFY_PANEL_FORCE_SECOND);
+}
+
+enum Route { TWO_STAGES = 0, SMALL = 1, MID = 2, PANELS = 3 };
+// THE routing of pclip_classify_ex_f16, which launches what this returns and pclip_classify_route_ex reports (valid flags assumed).  k: top-k width, topk_out:
+// top-k outputs asked for (k > 0 alone keeps the mid-N kernel off, as it has no top-k).  The routes differ in fp32 summation order (pclip.h).
+Route classify_route(int Q, int N, int D, float alpha, float oma, float beta, bool has_zt, bool want_p, bool want_argmax, int k, bool topk_out, int flags,
+                     size_t ws_bytes) {
+    if (Q <= 0 || N <= 0) return TWO_STAGES;
+    // mid-sized class counts (16 < N <= 256, Q N <= 2e6; forced: any N <= 256), p and / or argmax: one launch, norms in-kernel (pclip_classify_mid.hip)
+    if (!(flags & PCLIP_CLASSIFY_NO_MID) && (want_p || want_argmax) &&
+        pclip_classify_mid_applies(Q, N, D, has_zt, topk_out || k > 0, flags & PCLIP_CLASSIFY_FORCE_MID))
+        return MID;
+    // small class counts: one launch
+    if (!(flags & PCLIP_CLASSIFY_NO_SMALL) && N <= 32 && D > 0 && D % 32 == 0 && k >= 0 && k <= N && k <= 16 && (!topk_out || k > 0)) return SMALL;
+    // large class counts, argmax only: the fused row-panel kernel (pclip_classify_panel.hip) — no distance rows in HBM — if its scratch fits
+    if (!(flags & PCLIP_CLASSIFY_NO_PANELS) && has_zt && want_argmax && !want_p && !topk_out &&
+        pclip_classify_panel_applies(Q, N, D, alpha, oma, beta, flags & PCLIP_CLASSIFY_FORCE_PANELS) &&
+        ws_bytes >= carve_sq(nullptr, Q, N).bytes + pclip_classify_panel_workspace(Q, N, D))
+        return PANELS;
+    return TWO_STAGES;
+}
+
 }  // namespace
 
 #define DISPATCH_NV(N, CALL)                                   \
@@ -470,15 +497,13 @@ extern "C" size_t pclip_workspace_bytes(int op, int Q, int N, int D) {
         case PCLIP_OP_SQDIST: return sq;
         case PCLIP_OP_CLASSIFY: {
             const size_t rows = classify_rows_bytes(Q, N);
-            // A shape the routing may hand to the fused row panels also gets their scratch (interleaved banks, candidate records), so that a caller passing this
-            // size gets the route of the shape and the routing settings, never one that depends on how large a buffer it happens to hold.  The default routing sends
-            // only large Q there, where the distance rows are the larger by far; forced routing (pclip_classify_panel_config(2)) at small Q is what pays for the max.
-            // (pclip_classify_f16 itself requires the rows only: with less than the panels' scratch it takes the two stages.)
-            if (pclip_classify_panel_applies(Q, N, D, 0.5f, 0.5f, 1.f)) {
-                const size_t panel = sq + pclip_classify_panel_workspace(Q, N, D);
-                return panel > rows ? panel : rows;
-            }
-            return rows;
+            // A shape PCLIP_CLASSIFY_FORCE_PANELS could hand to the fused row panels also gets their scratch (interleaved banks, candidate records), so that a caller
+            // passing this size gets the route of the shape and its flags, never one that depends on how large a buffer it happens to hold.  The default routing sends
+            // only large Q there, where the distance rows are the larger by far; forced routing at small Q is what pays for the max.
+            // (pclip_classify_ex_f16 itself requires the rows only: with less than the panels' scratch it takes the two stages.)
+            if (!pclip_classify_panel_applies(Q, N, D, 0.5f, 0.5f, 1.f, true)) return rows;
+            const size_t panel = sq + pclip_classify_panel_workspace(Q, N, D);
+            return panel > rows ? panel : rows;
         }
         case PCLIP_OP_ADAPTER_FC: {
             // h1 [Q, D/4] fp16, h1n [Q, D/4] fp16, h2 [Q, D] fp16  (N is the hidden width here)
@@ -510,14 +535,11 @@ extern "C" int pclip_sqdist_f16(const void* q, const void* zi, const void* zt, i
         using CB = pgemm::Cfg<256, 256, 2, 4>;
         const int tm = ceil_div(Q, CB::BM), tn = ceil_div(N, CB::BN), per_bank = tm * tn, ntiles = per_bank * (zt ? 2 : 1);
         static int cus = 0;
-        static int big_ok = -1;
         if (!cus) {
             cus = pclip_device_cus();
             if (cus <= 0) cus = 256;
-            const char* e = getenv("PCLIP_SQDIST_BIG");
-            big_ok = e ? atoi(e) : 1;
         }
-        if (big_ok && ntiles >= 3 * cus && D >= 128 && Q % 4 == 0 && N % 4 == 0 && Q >= 4 && N >= 4) {
+        if (ntiles >= 3 * cus && D >= 128 && Q % 4 == 0 && N % 4 == 0 && Q >= 4 && N >= 4) {
             static DevOnce attr;
             if (!attr.done()) {
                 if (hipFuncSetAttribute((const void*)sqdist_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CB::LDS_BYTES + 4096) != hipSuccess) {
@@ -563,44 +585,38 @@ extern "C" int pclip_fuse_probs(const float* d2i, const float* d2t, int Q, int N
     return pclip_check_launch("fuse_probs");
 }
 
-extern "C" int pclip_classify_f16(const void* q, const void* zi, const void* zt, int Q, int N, int D,
-                                  const float* q_sq, const float* zi_sq, const float* zt_sq, float alpha,
-                                  float one_minus_alpha, float beta, float* p, int32_t* argmax, float* topk_p,
-                                  int32_t* topk_i, int k, void* ws, size_t ws_bytes, pclip_stream_t stream) {
+extern "C" int pclip_classify_ex_f16(const void* q, const void* zi, const void* zt, int Q, int N, int D,
+                                     const float* q_sq, const float* zi_sq, const float* zt_sq, float alpha,
+                                     float one_minus_alpha, float beta, float* p, int32_t* argmax, float* topk_p,
+                                     int32_t* topk_i, int k, int flags, void* ws, size_t ws_bytes, pclip_stream_t stream) {
     PCLIP_REQUIRE(ws != nullptr, "pclip_classify_f16: workspace required");
     PCLIP_REQUIRE(N <= 4096, "pclip_classify_f16: N=%d classes (<= 4096: the fusion kernels hold a class row in registers, the row panels walk 32 class tiles)", N);
+    PCLIP_REQUIRE(flags_valid(flags), "pclip_classify_ex_f16: flags 0x%x: unknown bits or a contradictory pair", flags);
     const size_t need = classify_rows_bytes(Q, N);
     if (ws_bytes < need) { pclip_set_error("pclip_classify_f16: workspace %zu < %zu", ws_bytes, need); return PCLIP_E_WORKSPACE; }
     if (Q == 0) return PCLIP_OK;
-    // mid-sized class counts (32 < N <= 256; tests / probes: any N <= 256), p and / or argmax: one launch, norms in-kernel (pclip_classify_mid.hip).  PCLIP_CLASSIFY_MID=0: off.
-    if (q && zi && (p || argmax) && pclip_classify_mid_applies(Q, N, D, zt != nullptr, topk_p || topk_i || k > 0))
-        return pclip_classify_mid_launch(q, zi, zt, Q, N, D, alpha, one_minus_alpha, beta, p, argmax, (hipStream_t)stream);
-    {   // small class counts: one launch (env PCLIP_CLASSIFY_SMALL=0 switches it off)
-        static int mode = -1, cus = 0;
-        if (mode < 0) {
-            const char* e = getenv("PCLIP_CLASSIFY_SMALL");
-            mode = e ? atoi(e) : 1;
-            cus = pclip_device_cus();
+    PCLIP_REQUIRE(q && zi, "pclip_classify_f16: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    SqWs w = carve_sq(ws, Q, N);
+    switch (classify_route(Q, N, D, alpha, one_minus_alpha, beta, zt != nullptr, p != nullptr, argmax != nullptr, k, topk_p || topk_i, flags, ws_bytes)) {
+        case MID: return pclip_classify_mid_launch(q, zi, zt, Q, N, D, alpha, one_minus_alpha, beta, p, argmax, s);
+        case SMALL: {
+            int cus = pclip_device_cus();
             if (cus <= 0) cus = 256;
-        }
-        const int nt = N <= 16 ? 1 : 2;
-        if (mode > 0 && N > 0 && N <= 32 && D > 0 && D % 32 == 0 && q && zi && k >= 0 && k <= N && k <= 16 &&
-            ((!topk_p && !topk_i) || k > 0)) {
-            hipStream_t s = (hipStream_t)stream;
 #define PCLIP_SMALL(NT)                                                                                                                   \
     return zt ? launch_classify_small<NT, true>(q, zi, zt, Q, N, D, alpha, one_minus_alpha, beta, p, argmax, topk_p, topk_i, k, cus, s) \
               : launch_classify_small<NT, false>(q, zi, zt, Q, N, D, alpha, one_minus_alpha, beta, p, argmax, topk_p, topk_i, k, cus, s)
-            if (nt == 1) { PCLIP_SMALL(1); }
+            if (N <= 16) { PCLIP_SMALL(1); }
             PCLIP_SMALL(2);
 #undef PCLIP_SMALL
         }
-    }
-    SqWs w = carve_sq(ws, Q, N);
-    // large class counts, argmax only: the fused row-panel kernel (pclip_classify_panel.hip) — no distance rows in HBM.  PCLIP_CLASSIFY_PANEL=0: two stages.
-    if (zt && argmax && !p && !topk_p && !topk_i && q && zi && pclip_classify_panel_applies(Q, N, D, alpha, one_minus_alpha, beta) &&
-        ws_bytes >= w.bytes + pclip_classify_panel_workspace(Q, N, D)) {
-        // (norms that were not supplied are formed by the kernel's own preparation launch: the arithmetic of pclip_row_sqnorm_f16)
-        return pclip_classify_panel_launch(q, zi, zt, Q, N, D, q_sq, zi_sq, zt_sq, alpha, one_minus_alpha, beta, argmax, nullptr, false, (char*)ws + w.bytes, (hipStream_t)stream);
+        case PANELS: {
+            // (norms that were not supplied are formed by the kernel's own preparation launch: the arithmetic of pclip_row_sqnorm_f16)
+            const int passes = flags & PCLIP_CLASSIFY_PANEL_TWO_PASS ? 1 : flags & PCLIP_CLASSIFY_PANEL_FORCE_SECOND ? 2 : 0;
+            return pclip_classify_panel_launch(q, zi, zt, Q, N, D, q_sq, zi_sq, zt_sq, alpha, one_minus_alpha, beta, argmax, nullptr, passes,
+                                               flags & PCLIP_CLASSIFY_PANEL_EXACT, (char*)ws + w.bytes, s);
+        }
+        case TWO_STAGES: break;
     }
     const int ldd = padded_ld(N);
     float* d2i = (float*)((char*)ws + w.bytes);
@@ -610,20 +626,22 @@ extern "C" int pclip_classify_f16(const void* q, const void* zi, const void* zt,
     return pclip_fuse_probs(d2i, d2t, Q, N, ldd, alpha, one_minus_alpha, beta, p, argmax, topk_p, topk_i, k, stream);
 }
 
-// Which kernels pclip_classify_f16 takes for a call of this shape under the current settings (the routes differ in fp32 summation order — the same
-// query can get a different argmax at a near-tie of p (margin < 1e-6) depending on the batch it travels in — so callers can ask): 0 two stages (pclip_sqdist_f16 +
-// pclip_fuse_probs: torch.cdist's arithmetic operation for operation), 1 one launch for N <= 16 / top-k up to N = 32 (classify_small), 2 one launch for 16 < N <= 256
-// (classify_mid), 3 fused row panels (argmax only, large Q N; distances without cdist's sqrt round trip unless PCLIP_CLASSIFY_PANEL_EXACT=1).
+extern "C" int pclip_classify_f16(const void* q, const void* zi, const void* zt, int Q, int N, int D,
+                                  const float* q_sq, const float* zi_sq, const float* zt_sq, float alpha,
+                                  float one_minus_alpha, float beta, float* p, int32_t* argmax, float* topk_p,
+                                  int32_t* topk_i, int k, void* ws, size_t ws_bytes, pclip_stream_t stream) {
+    return pclip_classify_ex_f16(q, zi, zt, Q, N, D, q_sq, zi_sq, zt_sq, alpha, one_minus_alpha, beta, p, argmax, topk_p, topk_i, k, 0, ws, ws_bytes, stream);
+}
+
+extern "C" int pclip_classify_route_ex(int Q, int N, int D, float alpha, float one_minus_alpha, float beta, int has_zt, int want_p, int want_argmax, int topk,
+                                       int flags, size_t ws_bytes) {
+    PCLIP_REQUIRE(flags_valid(flags), "pclip_classify_route_ex: flags 0x%x: unknown bits or a contradictory pair", flags);
+    return classify_route(Q, N, D, alpha, one_minus_alpha, beta, has_zt != 0, want_p != 0, want_argmax != 0, topk, topk != 0, flags, ws_bytes);
+}
+
 extern "C" int pclip_classify_route(int Q, int N, int D, float alpha, float one_minus_alpha, float beta, int has_zt, int want_p, int want_argmax, int topk,
                                     size_t ws_bytes) {
-    if (Q <= 0 || N <= 0) return 0;
-    if ((want_p || want_argmax) && pclip_classify_mid_applies(Q, N, D, has_zt != 0, topk > 0)) return 2;
-    static const int small_mode = getenv("PCLIP_CLASSIFY_SMALL") ? atoi(getenv("PCLIP_CLASSIFY_SMALL")) : 1;
-    if (small_mode > 0 && N <= 32 && D > 0 && D % 32 == 0 && topk >= 0 && topk <= N && topk <= 16) return 1;
-    if (has_zt && want_argmax && !want_p && topk == 0 && pclip_classify_panel_applies(Q, N, D, alpha, one_minus_alpha, beta) &&
-        ws_bytes >= carve_sq(nullptr, Q, N).bytes + pclip_classify_panel_workspace(Q, N, D))
-        return 3;
-    return 0;
+    return pclip_classify_route_ex(Q, N, D, alpha, one_minus_alpha, beta, has_zt, want_p, want_argmax, topk, 0, ws_bytes);
 }
 
 // Test entry: the distances the fused row-panel kernel forms for its first tile (query rows 0 .. 255 x classes 0 .. 127 of both banks, [2][256][128] fp32): exact != 0
@@ -639,7 +657,7 @@ extern "C" int pclip_classify_panel_dump_f16(const void* q, const void* zi, cons
     if ((e = pclip_row_sqnorm_f16(q, Q, D, w.q_sq, stream))) return e;
     if ((e = pclip_row_sqnorm_f16(zi, N, D, w.zi_sq, stream))) return e;
     if ((e = pclip_row_sqnorm_f16(zt, N, D, w.zt_sq, stream))) return e;
-    return pclip_classify_panel_launch(q, zi, zt, Q, N, D, w.q_sq, w.zi_sq, w.zt_sq, 0.5f, 0.5f, 1.f, nullptr, dump, exact != 0, (char*)ws + w.bytes, (hipStream_t)stream);
+    return pclip_classify_panel_launch(q, zi, zt, Q, N, D, w.q_sq, w.zi_sq, w.zt_sq, 0.5f, 0.5f, 1.f, nullptr, dump, 0, exact != 0, (char*)ws + w.bytes, (hipStream_t)stream);
 }
 
 extern "C" int pclip_hp_sweep(const float* d2i, const float* d2t, const int32_t* labels, int Q, int N, int ldd,

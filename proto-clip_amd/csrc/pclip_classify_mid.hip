@@ -20,7 +20,6 @@
 // softmax (tools/mid_probe.py, profiles/r06_mid_probe.txt).
 #include "pclip_gemm.h"
 #include "pclip_classify_small.h"
-#include <stdlib.h>
 #include <type_traits>
 
 namespace {
@@ -346,21 +345,14 @@ int launch_mid(const void* q, const void* zi, const void* zt, int Q, int N, int 
 
 }  // namespace
 
-static int g_mid_mode = -1;                     // -1: PCLIP_CLASSIFY_MID / default (1), 0 off, 1 routed by size, 2 every shape the kernel can run
-extern "C" int pclip_classify_mid_config(int mode) {
-    const int before = g_mid_mode;
-    if (mode >= 0) g_mid_mode = mode > 2 ? 1 : mode;
-    return before;
-}
-
 // Shapes the one-launch mid-N kernel takes: both banks, p and / or argmax (top-k goes to the other routes), N <= 256, D a multiple of 128 up to 2048.  Routed
 // by size: a workgroup streams both banks per 16 queries, so the kernel's time grows with Q / (16 x 2 CUs) bank passes where the two stages amortise the banks
-// over 128 x 128 tiles — beyond Q N ~ 2e6 the two stages (or, from 2e6 x tiles - 1e6, the fused row panels) take over (tools/small_bench.py).
-bool pclip_classify_mid_applies(int Q, int N, int D, bool has_zt, bool topk) {
-    if (g_mid_mode < 0) { const char* e = getenv("PCLIP_CLASSIFY_MID"); g_mid_mode = e ? atoi(e) : 1; if (g_mid_mode < 0 || g_mid_mode > 2) g_mid_mode = 1; }
-    if (!g_mid_mode || !has_zt || topk) return false;
+// over 128 x 128 tiles — beyond Q N ~ 2e6 the two stages (or, from 2e6 x tiles - 1e6, the fused row panels) take over (tools/small_bench.py).  force
+// (PCLIP_CLASSIFY_FORCE_MID): every shape the kernel can run.
+bool pclip_classify_mid_applies(int Q, int N, int D, bool has_zt, bool topk, bool force) {
+    if (!has_zt || topk) return false;
     if (!(N >= 1 && N <= 256 && D >= 128 && D % 128 == 0 && D <= 2048 && Q >= 1)) return false;
-    if (g_mid_mode == 2) return true;
+    if (force) return true;
     // N <= 16 stays with classify_small (ONE tile of bank fragments per wave: EuroSAT 6.4 vs 8.6 us, N = 10 / D = 1024 / Q = 8100: 9.6 vs 14.2); from two tiles on this
     // kernel measures faster (N = 17, D = 512, Q = 300: 5.5 vs 8.5 us; N = 32, Q = 4000: 5.9 vs 9.8; N = 24, D = 1024, Q = 20 000: 31.3 vs 37.2) — tools/mid_probe.py
     return N > 16 && (double)Q * (double)N <= 2.0e6;

@@ -5,7 +5,7 @@
 //   pass 2: the same distances again -> p = alpha e_i / S_i + (1 - alpha) e_t / S_t -> running (best p, class) per query
 // No distance leaves the chip; the 2 MB of prototypes stay L2-resident.  The second contraction costs as many FLOPs again (2 x 102 GFLOP for ImageNet); what it
 // buys is the 800 MB round trip and the second launch.
-// ONE pass where the result can be proven (default since round 5's second half; pclip_classify_panel_passes): pass 1 also leaves, per (row, lane-slot, tile) group of
+// ONE pass where the result can be proven (default since round 5's second half; PCLIP_CLASSIFY_PANEL_TWO_PASS walks twice always): pass 1 also leaves, per (row, lane-slot, tile) group of
 // 16 classes, a 32-byte record in the workspace — per bank the nearest class with BOTH its distances, and the group's second smallest distance.  The nearest classes
 // are the candidates; every other class of a group is bounded through the second smallest distances (p is monotone in both).  When the largest bound of a row is
 // below its best candidate's p, the candidates' argmax is the row's argmax — the bits pass 2 would produce — and a panel all of whose rows satisfy that skips pass 2.
@@ -18,7 +18,6 @@
 // agrees with pclip_fuse_probs to fp32 rounding and the argmax wherever the top-2 margin exceeds that.
 #include "pclip_gemm.h"
 #include "pclip_proto_dev.h"
-#include <stdlib.h>
 #include <type_traits>
 
 typedef int int2_t __attribute__((ext_vector_type(2)));
@@ -380,12 +379,6 @@ size_t pclip_classify_panel_workspace(int Q, int N, int D) {
     return align_up(rows2 * D * 2, 256) + align_up(rows2 * 4, 256) + align_up(Qp * 4, 256) + grid * (rows2 / 256) * (8 * 256 * 32) + 256;
 }
 
-static int g_panel_passes = -1;                // -1: PCLIP_CLASSIFY_PANEL_PASSES / default 0; 0 one pass + candidates (second pass where the proof fails), 1 always two passes, 2 tests
-extern "C" int pclip_classify_panel_passes(int mode) {
-    const int before = g_panel_passes;
-    if (mode >= 0) g_panel_passes = mode > 2 ? 0 : mode;
-    return before;
-}
 __device__ int g_panel_stats[3];               // panels classified | panels that took a second pass | class tiles those second passes walked (since the last reset)
 extern "C" int pclip_classify_panel_stats(int* out3, int reset) {
     int z[3] = {0, 0, 0};
@@ -394,39 +387,30 @@ extern "C" int pclip_classify_panel_stats(int* out3, int reset) {
     return PCLIP_OK;
 }
 
-static int g_panel_mode = -1;                  // -1: PCLIP_CLASSIFY_PANEL / default (on), decided at the first call
-extern "C" int pclip_classify_panel_config(int mode) {
-    const int before = g_panel_mode;
-    if (mode >= 0) g_panel_mode = mode > 2 ? 1 : mode;
-    return before;
-}
-
-bool pclip_classify_panel_applies(int Q, int N, int D, float alpha, float one_minus_alpha, float beta) {
-    if (g_panel_mode < 0) { const char* e = getenv("PCLIP_CLASSIFY_PANEL"); g_panel_mode = e ? atoi(e) : 1; if (g_panel_mode < 0 || g_panel_mode > 2) g_panel_mode = 1; }
+bool pclip_classify_panel_applies(int Q, int N, int D, float alpha, float one_minus_alpha, float beta, bool force) {
     // Routing by measurement (tools/fused_routing_probe.py, profiles/r05_fused_routing.txt): up to one panel per CU the fused kernel's time is ~12 + 17 us per class tile
     // whatever Q is (a CU walks its panel's tiles alone), the two stages cost ~22 us + 8e-6 us per (query, class) — fused from Q N >= 2e6 tiles - 1e6 (ImageNet: Q >= 15 k;
     // Food-101's 30 k queries: 32 vs 58 us; SUN397: 79 vs 107; below that the chip is mostly idle and the two stages win: FewSOL-198, Q = 666: 26 vs 50 us);
-    // mode 2 forces the fused kernel for every shape it can run (tests)
+    // force (PCLIP_CLASSIFY_FORCE_PANELS) takes the fused kernel for every shape it can run
     const double tiles = (double)(2 * ((N + 127) / 128 * 128) / 256);
-    const bool enough = g_panel_mode == 2 || (double)Q * (double)N >= 2.0e6 * tiles - 1.0e6;
+    const bool enough = force || (double)Q * (double)N >= 2.0e6 * tiles - 1.0e6;
     // the candidate proof bounds a class through p's monotonicity in both distances: both mixing weights and beta must be non-negative (a user's --alpha outside
     // [0, 1] takes the two stages)
     const bool monotone = alpha >= 0.f && one_minus_alpha >= 0.f && beta >= 0.f;
     // N <= 4096: at most 32 class tiles of 128 — the kernel walks its tiles through a 32-bit mask (pclip_classify_f16 refuses a larger N on every route)
-    return g_panel_mode > 0 && enough && monotone && N > 32 && N <= 4096 && D >= 128 && D % 64 == 0 && D <= 4096 && Q >= 1 && (long)256 * D * 2 < 0x7fffffffL;
+    return enough && monotone && N > 32 && N <= 4096 && D >= 128 && D % 64 == 0 && D <= 4096 && Q >= 1 && (long)256 * D * 2 < 0x7fffffffL;
 }
 
-// q_sq / zi_sq / zt_sq: device arrays or null (computed by the preparation launch with pclip_row_sqnorm_f16's arithmetic).  dump != nullptr: test mode (distances of panel 0 / tile 0, no argmax; dump_exact:
-// with / without the sqrt round trip).
+// q_sq / zi_sq / zt_sq: device arrays or null (computed by the preparation launch with pclip_row_sqnorm_f16's arithmetic).  dump != nullptr: test mode (distances of panel 0 / tile 0, no argmax).
+// passes: 0 one pass + candidates (second pass where the proof fails), 1 always two passes, 2 candidates computed, second pass forced (tests).  exact: with / without the sqrt round trip.
 int pclip_classify_panel_launch(const void* q, const void* zi, const void* zt, int Q, int N, int D, const float* q_sq, const float* zi_sq, const float* zt_sq,
-                                float alpha, float oma, float beta, int32_t* argmax, float* dump, bool dump_exact, void* ws, hipStream_t s) {
+                                float alpha, float oma, float beta, int32_t* argmax, float* dump, int passes, bool exact, void* ws, hipStream_t s) {
     const int rows2 = 2 * ((N + 127) / 128 * 128), Qp = (Q + 255) / 256 * 256;
     char* b = (char*)ws;
     half_t* zz = (half_t*)b; b += align_up((size_t)rows2 * D * 2, 256);
     float* zz_sq = (float*)b; b += align_up((size_t)rows2 * 4, 256);
     float* q_sqp = (float*)b; b += align_up((size_t)Qp * 4, 256);
     float* rec = (float*)b;
-    if (g_panel_passes < 0) { const char* e = getenv("PCLIP_CLASSIFY_PANEL_PASSES"); g_panel_passes = e ? atoi(e) : 0; if (g_panel_passes < 0 || g_panel_passes > 2) g_panel_passes = 0; }
     static int* stats_dev[64];                                      // the counters' device address, looked up once per device
     int dev = 0;
     int* stats = nullptr;
@@ -446,9 +430,7 @@ int pclip_classify_panel_launch(const void* q, const void* zi, const void* zt, i
     constexpr int LDS = CP::LDS_BYTES + 8192 + 64 + 2048;              // K-tile ring | norm strips + per-row constants | tile mask | the candidates' best per row
     // d2 = max(||q||^2 + ||z||^2 - 2 q.z, 0) by default: without torch.cdist's sqrt -> square round trip (<= 1 fp32 ulp from the two-stage path's distances, whose
     // correctly rounded sqrtf costs twelve VALU instructions per element: 371 vs 250 us on the ImageNet split — the arithmetic this kernel is bound by);
-    // PCLIP_CLASSIFY_PANEL_EXACT=1 keeps the round trip (bit-identical distances)
-    static const bool exact_env = getenv("PCLIP_CLASSIFY_PANEL_EXACT") && getenv("PCLIP_CLASSIFY_PANEL_EXACT")[0] == '1';
-    const bool exact = dump ? dump_exact : exact_env;
+    // exact (PCLIP_CLASSIFY_PANEL_EXACT) keeps the round trip (bit-identical distances)
     const float w = beta * 1.4426950408889634f;
 #define PCLIP_PANEL(EX, DU, CA)                                                                                                                  \
     do {                                                                                                                                         \
@@ -460,9 +442,9 @@ int pclip_classify_panel_launch(const void* q, const void* zi, const void* zt, i
             }                                                                                                                                    \
             attr.set();                                                                                                                          \
         }                                                                                                                                        \
-        classify_panel_kernel<EX, DU, CA><<<DU ? 1 : grid, 512, LDS, s>>>((const half_t*)q, zz, Q, rows2, D, q_sqp, zz_sq, alpha, oma, w, argmax, dump, DU ? 1 : npanels, rec, stats, g_panel_passes); \
+        classify_panel_kernel<EX, DU, CA><<<DU ? 1 : grid, 512, LDS, s>>>((const half_t*)q, zz, Q, rows2, D, q_sqp, zz_sq, alpha, oma, w, argmax, dump, DU ? 1 : npanels, rec, stats, passes); \
     } while (0)
-    const bool cand = g_panel_passes != 1;
+    const bool cand = passes != 1;
     if (dump && exact) PCLIP_PANEL(true, true, false);
     else if (dump) PCLIP_PANEL(false, true, false);
     else if (exact && cand) PCLIP_PANEL(true, false, true);

@@ -1,6 +1,7 @@
 """Tensor-level wrappers over the C ABI (include/pclip.h).  PyTorch is used only to own device memory
 and streams; every arithmetic step below is a libpclip kernel.  All functions require CUDA (ROCm)
 tensors and raise PclipError otherwise — there is deliberately no CPU path."""
+import contextvars
 import math
 import os
 
@@ -200,13 +201,14 @@ def classify(q, zi, zt, alpha: float, beta: float, want_p=False, want_argmax=Tru
     tp = torch.empty(Q, topk, dtype=torch.float32, device=dev) if topk else None
     ti = torch.empty(Q, topk, dtype=torch.int32, device=dev) if topk else None
     # the library is told this shape's own workspace size, not the cached buffer's (which grows with whatever ran before on the stream): the route it
-    # takes — the fused row panels only if their scratch fits in that size — is then a function of the shape alone, the one `classify_route` reports
+    # takes — the fused row panels only if their scratch fits in that size — is then a function of the shape and the context's routing flags alone, the one
+    # `classify_route` reports
     nws = _lib.workspace_bytes(_lib.OP_CLASSIFY, Q, N, D)
     ws = _workspace(nws, dev)
     a32, oma32 = float(np.float32(alpha)), float(np.float32(1 - float(alpha)))
-    check(_lib.load().pclip_classify_f16(ptr(q), ptr(zi), ptr(zt), Q, N, D, ptr(q_sq), ptr(zi_sq), ptr(zt_sq), a32,
-                                         oma32, float(np.float32(beta)), ptr(p), ptr(am), ptr(tp), ptr(ti), topk,
-                                         ptr(ws), nws, stream()), "pclip_classify_f16")
+    check(_lib.load().pclip_classify_ex_f16(ptr(q), ptr(zi), ptr(zt), Q, N, D, ptr(q_sq), ptr(zi_sq), ptr(zt_sq), a32,
+                                            oma32, float(np.float32(beta)), ptr(p), ptr(am), ptr(tp), ptr(ti), topk,
+                                            _classify_flags.get(), ptr(ws), nws, stream()), "pclip_classify_ex_f16")
     return p, am, tp, ti
 
 
@@ -227,68 +229,66 @@ CLASSIFY_ROUTES = ("two stages", "one launch, small N", "one launch, mid N", "fu
 
 
 def classify_route(Q: int, N: int, D: int, alpha: float, beta: float, want_p=False, want_argmax=True, topk: int = 0, has_zt: bool = True) -> str:
-    """The kernels `classify` takes for a call of this shape under the current settings (pclip_classify_route).  The routes differ in fp32 summation order only —
-    at a near-tie of p (top-2 margin < ~1e-6) the argmax may depend on the route, i.e. on the batch size; `classify_two_stage()` pins one arithmetic."""
+    """The kernels `classify` takes for a call of this shape under the current context's routing (pclip_classify_route_ex).  The routes differ in fp32 summation
+    order only — at a near-tie of p (top-2 margin < ~1e-6) the argmax may depend on the route, i.e. on the batch size; `classify_two_stage()` pins one arithmetic."""
     a32, oma32 = float(np.float32(alpha)), float(np.float32(1 - float(alpha)))
-    r = _lib.load().pclip_classify_route(Q, N, D, a32, oma32, float(np.float32(beta)), int(has_zt), int(bool(want_p)), int(bool(want_argmax)), topk,
-                                         _lib.workspace_bytes(_lib.OP_CLASSIFY, Q, N, D))
+    r = _lib.load().pclip_classify_route_ex(Q, N, D, a32, oma32, float(np.float32(beta)), int(has_zt), int(bool(want_p)), int(bool(want_argmax)), topk,
+                                            _classify_flags.get(), _lib.workspace_bytes(_lib.OP_CLASSIFY, Q, N, D))
     return CLASSIFY_ROUTES[r]
 
 
-class classify_mid:
-    """`with ops.classify_mid(mode):` — routing of the one-launch mid-N kernel (32 < N <= 256): 0 off (two stages), 1 by size (default), 2 every shape it can run."""
+# The routing flags (pclip_classify_ex_f16) of the `classify` calls made in this context — per thread and per asyncio task.  Each context manager below replaces
+# only its own bits and restores the previous word on exit, so they nest: `classify_panel_passes` inside `classify_fused` keeps both.
+_classify_flags = contextvars.ContextVar("pclip_classify_flags", default=0)
+_MID = _lib.CLASSIFY_NO_MID | _lib.CLASSIFY_FORCE_MID
+_PANELS = _lib.CLASSIFY_NO_PANELS | _lib.CLASSIFY_FORCE_PANELS
+_PASSES = _lib.CLASSIFY_PANEL_TWO_PASS | _lib.CLASSIFY_PANEL_FORCE_SECOND
+
+
+class _classify_routing:
+    mask = bits = 0
+
+    def __enter__(self):
+        self._token = _classify_flags.set(_classify_flags.get() & ~self.mask | self.bits)
+        return self
+
+    def __exit__(self, *exc):
+        _classify_flags.reset(self._token)
+        return False
+
+
+class classify_mid(_classify_routing):
+    """`with ops.classify_mid(mode):` — routing of the one-launch mid-N kernel (16 < N <= 256): 0 off (two stages), 1 by size (default), 2 every shape it can run."""
     def __init__(self, mode: int):
         self.mode = mode
-
-    def __enter__(self):
-        self.before = _lib.load().pclip_classify_mid_config(self.mode)
-        return self
-
-    def __exit__(self, *exc):
-        _lib.load().pclip_classify_mid_config(self.before if self.before >= 0 else 1)
-        return False
+        self.mask = _MID if mode >= 0 else 0
+        self.bits = {0: _lib.CLASSIFY_NO_MID, 2: _lib.CLASSIFY_FORCE_MID}.get(mode, 0)
 
 
-class classify_two_stage:
+class classify_two_stage(_classify_routing):
     """`with ops.classify_two_stage():` — classification through pclip_sqdist_f16 + pclip_fuse_probs instead of the fused row-panel kernel / the one-launch mid-N
     kernel (their reference)."""
-    def __enter__(self):
-        self.before = _lib.load().pclip_classify_panel_config(0)
-        self.before_mid = _lib.load().pclip_classify_mid_config(0)
-        return self
-
-    def __exit__(self, *exc):
-        _lib.load().pclip_classify_panel_config(self.before if self.before >= 0 else 1)
-        _lib.load().pclip_classify_mid_config(self.before_mid if self.before_mid >= 0 else 1)
-        return False
+    mask, bits = _MID | _PANELS, _lib.CLASSIFY_NO_MID | _lib.CLASSIFY_NO_PANELS
 
 
-class classify_fused:
+class classify_fused(_classify_routing):
     """`with ops.classify_fused():` — the fused row-panel kernel for EVERY argmax-only call it can run (by default only calls with enough panels to fill the chip;
     the one-launch mid-N kernel, which would take N <= 256 first, is switched off inside)."""
-    def __enter__(self):
-        self.before = _lib.load().pclip_classify_panel_config(2)
-        self.before_mid = _lib.load().pclip_classify_mid_config(0)
-        return self
-
-    def __exit__(self, *exc):
-        _lib.load().pclip_classify_panel_config(self.before if self.before >= 0 else 1)
-        _lib.load().pclip_classify_mid_config(self.before_mid if self.before_mid >= 0 else 1)
-        return False
+    mask, bits = _MID | _PANELS, _lib.CLASSIFY_NO_MID | _lib.CLASSIFY_FORCE_PANELS
 
 
-class classify_panel_passes:
+class classify_panel_passes(_classify_routing):
     """`with ops.classify_panel_passes(mode):` — 0 one pass + candidates with proof (default), 1 always two passes, 2 candidates computed, second pass forced (tests)."""
     def __init__(self, mode: int):
         self.mode = mode
+        self.mask = _PASSES if mode >= 0 else 0
+        self.bits = {1: _lib.CLASSIFY_PANEL_TWO_PASS, 2: _lib.CLASSIFY_PANEL_FORCE_SECOND}.get(mode, 0)
 
-    def __enter__(self):
-        self.prev = _lib.load().pclip_classify_panel_passes(self.mode)
-        return self
 
-    def __exit__(self, *exc):
-        _lib.load().pclip_classify_panel_passes(self.prev if self.prev >= 0 else 0)
-        return False
+class classify_panel_exact(_classify_routing):
+    """`with ops.classify_panel_exact():` — the fused row-panel kernel keeps torch.cdist's sqrt -> square round trip (bit-identical distances, a third slower)."""
+    def __init__(self, exact: bool = True):
+        self.mask, self.bits = _lib.CLASSIFY_PANEL_EXACT, _lib.CLASSIFY_PANEL_EXACT if exact else 0
 
 
 def classify_panel_stats(reset: bool = False, tiles: bool = False):

@@ -10,7 +10,6 @@ Acceptance rules, the same for every route (tolerances recorded with observe()):
   hp_sweep each grid point's count within (number of queries whose fp64 top-2 margin there is < tau) of the fp64 count.
 Returned class ids are compared on the host only and never used to index a device tensor."""
 import math
-import os
 
 import numpy as np
 import pytest
@@ -20,8 +19,6 @@ from conftest import assert_adapter_close, observe, ulp_diff
 from oracle import proto_oracle as po
 
 pytestmark = pytest.mark.gpu
-ROUTING_SWITCHED = any(os.environ.get(k) for k in ("PCLIP_CLASSIFY_PANEL", "PCLIP_CLASSIFY_MID", "PCLIP_CLASSIFY_SMALL", "PCLIP_CLASSIFY_PANEL_PASSES"))
-default_routing = pytest.mark.skipif(ROUTING_SWITCHED, reason="asserts the DEFAULT classification routing; a PCLIP_CLASSIFY_* switch is set")
 nrm = torch.nn.functional.normalize
 TWO, PANELS = "two stages", "fused row panels"
 
@@ -240,17 +237,31 @@ def test_hp_sweep_nv64_vs_float64(ops, N):
 _FUSED_PASSES = {}
 
 
+FUSED_ENVELOPE = [(N, D) for N in (1025, 2048, 2049, 3000, 4095, 4096) for D in (128, 512, 2112, 4096)]
+
+
 @pytest.mark.parametrize("structured", [True, False])
-@pytest.mark.parametrize("N,D", [(N, D) for N in (1025, 2048, 2049, 3000, 4095, 4096) for D in (128, 512, 2112, 4096)])
+@pytest.mark.parametrize("N,D", FUSED_ENVELOPE)
 def test_fused_row_panels_envelope_vs_float64(ops, N, D, structured):
     """Forced fused row panels, argmax only, at N past 16 class tiles (2049 .. 4096: the proof without per-tile masks, 32 tiles in the mask) and D past 2048
     (the PCLIP_PREP(8) preparation build).  Three panels, the last one ragged; one pass + proof == always two passes == second pass forced, bit for bit."""
+    fused_row_panels_envelope(ops, N, D, structured, exact=False)
+
+
+@pytest.mark.parametrize("structured", [True, False])
+@pytest.mark.parametrize("N,D", FUSED_ENVELOPE)
+def test_fused_row_panels_envelope_sqrt_round_trip_vs_float64(ops, N, D, structured):
+    """The same with torch.cdist's sqrt round trip kept in the fused kernel (classify_panel_exact)."""
+    fused_row_panels_envelope(ops, N, D, structured, exact=True)
+
+
+def fused_row_panels_envelope(ops, N, D, structured, exact):
     Q, alpha, beta = 520, 0.5, 12.0
     zi, zt, queries = banks(N, D, seed=N + D + structured, structured=structured)
     q, _ = queries(Q)
     qc, zic, ztc = q.cuda(), zi.cuda(), zt.cuda()
-    tag = f"fused panels N={N} D={D} {'structured' if structured else 'structureless'}"
-    with ops.classify_fused():
+    tag = f"fused panels N={N} D={D} {'structured' if structured else 'structureless'}{' exact' if exact else ''}"
+    with ops.classify_fused(), ops.classify_panel_exact(exact):
         assert ops.classify_route(Q, N, D, alpha, beta) == PANELS
         outs = {}
         for passes in (0, 1, 2):
@@ -265,7 +276,7 @@ def test_fused_row_panels_envelope_vs_float64(ops, N, D, structured):
     assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2]), (tag, int((outs[0] != outs[1]).sum()), int((outs[0] != outs[2]).sum()))
     observe(f"{tag}: fraction of panels through the second pass", stats[1] / stats[0], 1.0)
     if N > 2048:
-        _FUSED_PASSES[(N, D, structured)] = stats
+        _FUSED_PASSES[(N, D, structured, exact)] = stats
     p64, tau = reference(q, zi, zt, alpha, beta)
     check_argmax(outs[0], p64, tau, N, tag)
 
@@ -361,7 +372,6 @@ def test_duplicate_prototypes_across_far_tiles(ops):
         assert torch.equal(outs[0], outs[1]), alpha
 
 
-@default_routing
 def test_default_routing_at_the_envelope_edge(ops):
     """Q = 20 000, N = 4096, D = 512 without forcing anything: the product's own routing takes the fused row panels (79 panels, the last one of 32 rows)."""
     Q, N, D, alpha, beta = 20000, 4096, 512, 0.5, 12.0

@@ -13,8 +13,6 @@ from oracle import proto_oracle as po
 from proto_clip_amd import synth
 
 pytestmark = pytest.mark.gpu
-ROUTING_SWITCHED = any(os.environ.get(k) for k in ("PCLIP_CLASSIFY_PANEL", "PCLIP_CLASSIFY_MID", "PCLIP_CLASSIFY_SMALL", "PCLIP_CLASSIFY_PANEL_PASSES"))
-default_routing = pytest.mark.skipif(ROUTING_SWITCHED, reason="asserts the DEFAULT classification routing; a PCLIP_CLASSIFY_* switch is set (tools/gpu_r6_switches.sh)")
 
 
 @pytest.fixture(scope="module")
@@ -189,8 +187,8 @@ def test_P_against_reference_fixture(ops, name):
                                    (1000, 32, 1024), (77, 31, 96), (500, 37, 512), (260, 47, 512), (129, 64, 512), (50, 64, 1024)])
 @pytest.mark.parametrize("alpha,beta", [(0.5, 12.0), (1.0, 0.7), (0.0, 3.0), (0.3, -2.0)])
 def test_classify_single_launch_small_N(ops, Q, N, D, alpha, beta):
-    """N <= 64 takes the one-launch kernel (classify_small_kernel: banks in LDS, a wave per 16 queries) for N <= 32 by default and
-    for every N <= 64 with PCLIP_CLASSIFY_SMALL=2: same results as the two-stage path (distance rows + softmax pass) up to fp32
+    """N <= 64 with the mid-N kernel off: the one-launch kernel (classify_small_kernel: banks in LDS, a wave per 16 queries) for N <= 32,
+    the two stages beyond: same results as the two-stage path (distance rows + softmax pass) up to fp32
     summation order, p within 1e-5 of the oracle, top-1 / top-k identical wherever the runner-up is not within 1e-6."""
     with ops.classify_mid(0):                                                      # this is classify_small's test: the mid-N kernel (which takes N > 16 by default) is tested below
         q = po.l2norm_rows(torch.from_numpy(synth.normal((Q, D), 21, 0)).half())
@@ -253,7 +251,6 @@ def test_classify_one_launch_mid_N(ops, Q, N, D, alpha, beta):
         torch.testing.assert_close(tp.cpu(), rv, rtol=0, atol=1e-5)
 
 
-@default_routing
 def test_classify_route_is_reported(ops):
     """ops.classify_route names the kernels a call takes (the routes differ in summation order, callers can ask / pin)."""
     assert ops.classify_route(8100, 10, 512, 1.0, 0.7) == "one launch, small N"
@@ -299,11 +296,24 @@ def test_classify_mid_default_routing_and_graph_replay(ops):
             assert torch.equal(out, ops.classify(q, zi, zt, 0.5, 12.0)[1])
 
 
-@pytest.mark.parametrize("Q,N,D", [(300, 200, 512), (1000, 1000, 512), (257, 100, 1024), (5000, 198, 768), (33, 40, 128)])
+FUSED_SHAPES = [(300, 200, 512), (1000, 1000, 512), (257, 100, 1024), (5000, 198, 768), (33, 40, 128)]
+
+
+@pytest.mark.parametrize("Q,N,D", FUSED_SHAPES)
 def test_classify_fused_row_panels(ops, Q, N, D):
     """The fused large-N classification (csrc/pclip_classify_panel.hip): (i) the distances it forms (sampled tile: query rows 0..255 x classes 0..127, both banks) are the BITS
     pclip_sqdist_f16 writes when it keeps torch.cdist's sqrt round trip, and within one fp32 ulp of them in the product's faster form; (ii) its argmax is the two-stage path's — and where it is not, the two-stage p of that query ties its top
     two classes to 1e-6 (proven per query, not budgeted); (iii) against the oracle's P the same; several (alpha, beta) incl. the configurations' own."""
+    classify_fused_row_panels(ops, Q, N, D, exact=False)
+
+
+@pytest.mark.parametrize("Q,N,D", FUSED_SHAPES)
+def test_classify_fused_row_panels_sqrt_round_trip(ops, Q, N, D):
+    """test_classify_fused_row_panels with torch.cdist's sqrt round trip kept in the classification itself (classify_panel_exact)."""
+    classify_fused_row_panels(ops, Q, N, D, exact=True)
+
+
+def classify_fused_row_panels(ops, Q, N, D, exact):
     g = torch.Generator().manual_seed(Q + N + D)
     cen = torch.randn(N, D, generator=g)
     nrm = torch.nn.functional.normalize
@@ -319,9 +329,9 @@ def test_classify_fused_row_panels(ops, Q, N, D):
     for a, b in ((di[:r, :c], d2i[:r, :c]), (dt[:r, :c], d2t[:r, :c])):
         assert int((a.contiguous().view(torch.int32) - b.contiguous().view(torch.int32)).abs().max()) <= 1
     for alpha, beta in ((0.5, 12.0), (0.2, 12.0), (1.0, 0.7), (0.0, 5.0), (0.35, 1.0)):
-        with ops.classify_fused():
+        with ops.classify_fused(), ops.classify_panel_exact(exact):
             ops.classify_panel_stats(reset=True)
-            with ops.classify_panel_passes(0):             # (the default; named so that the panel counts below hold under PCLIP_CLASSIFY_PANEL_PASSES=1 too)
+            with ops.classify_panel_passes(0):
                 _, am, _, _ = ops.classify(dev(q), dev(zi), dev(zt), alpha, beta, want_p=False, want_argmax=True)
             npan, nsecond = ops.classify_panel_stats()
             # one pass + candidates + proof (default) == always two passes == candidates with the second pass forced: the same argmax, bit for bit
@@ -352,6 +362,15 @@ def test_classify_fused_exact_ties_take_the_lowest_class(ops):
     """Duplicated prototypes (classes 7 == 150 == 151 in both banks, 30 == 31 in the visual bank only) make EXACT ties of p: main.py:190's `.max(1)[1]` on the CPU returns the
     lowest class.  The fused kernel's candidate proof cannot separate a tie (bound == best) and must hand such panels to its second pass; every routing — one pass +
     candidates, always two passes, the two stages — returns the same, lowest, class, and never the duplicate."""
+    classify_fused_exact_ties(ops, exact=False)
+
+
+def test_classify_fused_exact_ties_sqrt_round_trip(ops):
+    """The same with torch.cdist's sqrt round trip kept in the fused kernel (classify_panel_exact)."""
+    classify_fused_exact_ties(ops, exact=True)
+
+
+def classify_fused_exact_ties(ops, exact):
     Q, N, D = 700, 200, 512
     g = torch.Generator().manual_seed(5)
     nrm = torch.nn.functional.normalize
@@ -366,7 +385,7 @@ def test_classify_fused_exact_ties_take_the_lowest_class(ops):
     q = nrm(cen[y] + 0.8 * torch.randn(Q, D, generator=g), dim=-1).half()
     for alpha, beta in ((0.5, 12.0), (1.0, 3.0), (0.0, 5.0)):
         outs = {}
-        with ops.classify_fused():
+        with ops.classify_fused(), ops.classify_panel_exact(exact):
             for passes in (0, 1):
                 with ops.classify_panel_passes(passes):
                     ops.classify_panel_stats(reset=True)
@@ -615,7 +634,6 @@ def test_full_size_properties_C3(ops):
     assert acc_lo < cnt[1, 1].item() / 50000 < acc_hi, cnt
 
 
-@default_routing
 @pytest.mark.parametrize("structured", [True, False])
 def test_full_size_default_routing_C3(ops, structured):
     """The DEFAULT routing of `ops.classify(argmax)` at BASELINE's full size (Q = 50 000, N = 1000, D = 512; utils.py:225-244 + main.py:190): the fused row-panel kernel

@@ -78,7 +78,6 @@ def test_sqdist_big_and_fused_classify_under_jitter(ops, slib):
     ws = torch.empty(_lib.workspace_bytes(_lib.OP_CLASSIFY, Q, N, D), dtype=torch.uint8, device="cuda")
     with ops.classify_fused():
         _, am_ref, _, _ = ops.classify(q, zi, zt, 0.5, 12.0, want_p=False, want_argmax=True)
-    slib.pclip_classify_panel_config(2)
     for _ in range(3):
         a = torch.full((Q, ldd), float("nan"), device="cuda")
         b = torch.full((Q, ldd), float("nan"), device="cuda")
@@ -86,8 +85,8 @@ def test_sqdist_big_and_fused_classify_under_jitter(ops, slib):
         assert rc == 0, slib.pclip_last_error()
         assert torch.equal(a[:, :N], d2i[:, :N]) and torch.equal(b[:, :N], d2t[:, :N])
         am = torch.full((Q,), -1, dtype=torch.int32, device="cuda")
-        rc = slib.pclip_classify_f16(_lib.ptr(q), _lib.ptr(zi), _lib.ptr(zt), Q, N, D, None, None, None, 0.5, 0.5, 12.0, None, _lib.ptr(am), None, None, 0, _lib.ptr(ws),
-                                     ws.numel(), _lib.stream())
+        rc = slib.pclip_classify_ex_f16(_lib.ptr(q), _lib.ptr(zi), _lib.ptr(zt), Q, N, D, None, None, None, 0.5, 0.5, 12.0, None, _lib.ptr(am), None, None, 0,
+                                        _lib.CLASSIFY_FORCE_PANELS, _lib.ptr(ws), ws.numel(), _lib.stream())
         assert rc == 0, slib.pclip_last_error()
         assert torch.equal(am, am_ref)
 
@@ -105,12 +104,11 @@ def test_classify_mid_under_jitter(ops, slib, Q, N, D):
     with ops.classify_mid(2):
         p_ref, am_ref, _, _ = ops.classify(q, zi, zt, 0.5, 12.0, want_p=True, want_argmax=True)
     ws = torch.empty(_lib.workspace_bytes(_lib.OP_CLASSIFY, Q, N, D), dtype=torch.uint8, device="cuda")
-    slib.pclip_classify_mid_config(2)
     for rep in range(4):
         p = torch.full((Q, N), float("nan"), device="cuda")
         am = torch.full((Q,), -1, dtype=torch.int32, device="cuda")
-        rc = slib.pclip_classify_f16(_lib.ptr(q), _lib.ptr(zi), _lib.ptr(zt), Q, N, D, None, None, None, 0.5, 0.5, 12.0, _lib.ptr(p), _lib.ptr(am), None, None, 0,
-                                     _lib.ptr(ws), ws.numel(), _lib.stream())
+        rc = slib.pclip_classify_ex_f16(_lib.ptr(q), _lib.ptr(zi), _lib.ptr(zt), Q, N, D, None, None, None, 0.5, 0.5, 12.0, _lib.ptr(p), _lib.ptr(am), None, None, 0,
+                                        _lib.CLASSIFY_FORCE_MID, _lib.ptr(ws), ws.numel(), _lib.stream())
         assert rc == 0, slib.pclip_last_error()
         assert torch.equal(p, p_ref) and torch.equal(am, am_ref), f"launch {rep}"
 
