@@ -7,6 +7,12 @@ weights of the named architecture.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
     python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR    # + the last timed step's top-1 labels as DIR/top1.npy
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full                # + self-check, GEMM roofline, clock / power, side kernels, CPU baseline
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the headline line, nothing else.  --full adds,
+after the timed steps, everything else the benchmark measures or checks: the sub-batch self-check (a failing one takes the value
+and the exit status), the instrumented GEMM step (`roofline`, `whole_path`), shader clock and power under load, the committed PMC
+summary, the C2 / C3 side kernels (`extra`, off with --no-extra) and the host CPU baseline (off with --no-cpu-baseline).
 
 One step = one pass of the hot path over one batch of B=1024 pre-processed query images per GPU
 (the reference's loader batch, main.py:505): prototype reduction from the (rank-sharded) 16 000-row
@@ -450,6 +456,8 @@ def self_launch(args):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__), "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup)]
+    if args.full:
+        cmd.append("--full")
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
     if args.dump_outputs:
@@ -483,8 +491,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the un-timed side measurements of the `extra` block")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the self-check and every un-timed side measurement (roofline, clock, extra, CPU baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the host CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the un-timed side measurements of the `extra` block")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (the top-1 class of every query) as DIR/<name>.npy, float64")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)
@@ -556,22 +566,20 @@ def run(args, hooks, out=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
 
-    check = hooks.self_check(st)   # every rank: the step contains the all-gather
-    if launched:
-        flag = torch.tensor([0 if check == "ok" else 1], device=device)
-        dist.all_reduce(flag, op=dist.ReduceOp.MAX)
-        if flag.item() and check == "ok":
-            check = "MISMATCH on another rank"
-    nogm = dict(launches=0, calls=0, total_ms=0.0, avg_us=0.0, tflops=0.0, flops=0.0)
-    gm = measure_gemm(st) if hooks.instrument else nogm          # every rank runs it: the instrumented step contains the all-gather
-    clk = measure_clock(st) if world == 1 and hooks.instrument else {"source": None}
+    full = getattr(args, "full", False)
+    check = "ok"
+    if full:
+        check = hooks.self_check(st)   # every rank: the step contains the all-gather
+        if launched:
+            flag = torch.tensor([0 if check == "ok" else 1], device=device)
+            dist.all_reduce(flag, op=dist.ReduceOp.MAX)
+            if flag.item() and check == "ok":
+                check = "MISMATCH on another rank"
+        nogm = dict(launches=0, calls=0, total_ms=0.0, avg_us=0.0, tflops=0.0, flops=0.0)
+        gm = measure_gemm(st) if hooks.instrument else nogm          # every rank runs it: the instrumented step contains the all-gather
+        clk = measure_clock(st) if world == 1 and hooks.instrument else {"source": None}
     if rank == 0:
-        traffic, traffic_file, traffic_note = pmc_traffic()
-        sclk = (clk.get("sclk_mhz") or {}).get("median")
-        power = (clk.get("power_w") or {}).get("median")
         imgs_per_s = args.steps * BATCH * world / dt
-        ref_gflop = GFLOP_PER_IMG_ENCODER + GFLOP_PER_IMG_TAIL
-        exe_gflop = gm["flops"] / 1e9 / BATCH + GFLOP_PER_IMG_ATTENTION + GFLOP_PER_IMG_TAIL     # what the HIP path executes: the last block runs on the class rows only
         line = {
             "metric": "query images/sec, ImageNet 16-shot ViT-B/16 (few-shot top-1 parity: tests/)",
             "value": imgs_per_s, "unit": "query images/sec", "n_gpus": world,
@@ -580,49 +588,65 @@ def run(args, hooks, out=None):
             "step_time_note": "ms_per_step = wall clock over the K steps between the two barriers (the contract); median / p10 / p90 = per-step HIP-event times on rank 0's launch stream inside the same loop",
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f16", "data": "synthetic",
-            "sclk_mhz_under_load": sclk, "power_w": power,
-            "clock_source": {k: clk.get(k) for k in ("source", "samples", "sclk_mhz", "power_w")},
             "config": {"workload": "C3 ImageNet 16-shot ViT-B/16 conv-3x: prototype reduce + encode_image + adapter + dual-bank classify",
                        "batch_per_gpu": BATCH, "global_batch": BATCH * world, "classes": N_CLASS, "shots": SHOTS, "embed_dim": DIM,
                        "alpha": ALPHA, "beta": BETA, "parallelism": f"dp{world} (support rows and queries sharded; all-gather of class sums)"},
-            "self_check": check,
-            "roofline": {"bound": "mfma", "kernel": "linear4w_kernel (four-wave 256 x 256 tiles, hand-scheduled asm K-loop) + linear_fast_kernel (row-split tails) + linear_small_kernel (fp16 MFMA GEMM: every encoder linear incl. patch embedding and projection, with bias / QuickGELU / residual add in its epilogue"
-                                                    + "; the LayerNorms are separate passes (the reference's rounding points); the class-row tail runs the small-M variant)",
-                         "achieved": gm["tflops"], "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": gm["tflops"] / MFMA_PEAK_TFLOPS,
-                         "frac_at_sustained_clock": (gm["tflops"] / (MFMA_PEAK_TFLOPS * sclk / 2400.0)) if sclk else None,
-                         # context, not the contract's peak: what the matrix pipe sustains on this class of operands under the 1.4 kW socket cap (register-only loops,
-                         # tools/probe/mfma_power.hip, measured on other boxes of the pool; on zero operands the same loops reach the nominal 2.5 PFLOP/s)
-                         "power_limited_reference": {"mfma_16x16x32_registers_only_tflops": 1940.0, "four_wave_k_loop_alone_tflops": 1435.0,
-                                                     "frac_of_registers_only": gm["tflops"] / 1940.0, "source": "profiles/r05_mfma_power_probe.txt, r05_gemm4w_epilogue.txt"},
-                         "traffic": traffic, "traffic_unit": f"HBM bytes per launch (profiles/{traffic_file}: {traffic_note})",
-                         "launches_per_step": gm["launches"], "avg_launch_us": gm["avg_us"],
-                         "gemm_ms_per_step": gm["total_ms"], "algorithmic_gflop_per_step": gm["flops"] / 1e9,
-                         "per_variant": gm.get("per_variant"),
-                         "timed_launches": gm.get("timed_launches"),
-                         "method": "the GEMM kernels' own measurement hook (pclip_gemm_timing): every workgroup of every GEMM launch of one instrumented step folds the device's 100 MHz counter into (min begin, max end) — the kernel's span as rocprofv3 --kernel-trace reports it, with nothing between the kernels"},
-            "whole_path": {"note": "reference-equivalent = the FLOPs the REFERENCE module spends per image (every token through all 12 blocks); executed = what the HIP path runs "
-                                   "(GEMM launches of the instrumented step + attention contractions + adapter + similarity: the last block works on the class rows only)",
-                           "reference_equivalent_gflop_per_image": ref_gflop, "reference_equivalent_tflops": imgs_per_s / world * ref_gflop / 1e3,
-                           "reference_equivalent_frac_of_mfma_peak": imgs_per_s / world * ref_gflop / 1e3 / MFMA_PEAK_TFLOPS,
-                           "executed_gflop_per_image": exe_gflop, "executed_tflops": imgs_per_s / world * exe_gflop / 1e3,
-                           "executed_frac": imgs_per_s / world * exe_gflop / 1e3 / MFMA_PEAK_TFLOPS},
         }
-        if world == 1 and not args.no_extra and hooks.instrument:
-            try:
-                line["extra"] = {"c2_kernels": c2_kernels(device), "c3_classify": c3_classify(device)}
-            except Exception as e:                       # side measurements never take the headline down
-                line["extra"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline and hooks.instrument:
-            line["cpu_baseline"] = cpu_baseline()
-        if check != "ok":
-            # a step whose rows depend on the batch around them is not the workload: no headline number, and a failing exit status behind the line
-            line["invalid_value"], line["value"] = line["value"], None
+        if full:
+            line.update(full_report(args, hooks, device, world, imgs_per_s, check, gm, clk))
         print(json.dumps(line), file=out, flush=True)
     if launched:
         dist.barrier()
         dist.destroy_process_group()
     if check != "ok":
         raise SystemExit(3)
+
+
+def full_report(args, hooks, device, world, imgs_per_s, check, gm, clk):
+    """Rank 0's --full fields of the result line: the self-check, clock / power under load, the GEMM roofline, the whole-path FLOP rates,
+    the side kernels and the CPU baseline.  A failing self-check moves the headline value to `invalid_value`."""
+    BATCH = hooks.batch
+    traffic, traffic_file, traffic_note = pmc_traffic()
+    sclk = (clk.get("sclk_mhz") or {}).get("median")
+    power = (clk.get("power_w") or {}).get("median")
+    ref_gflop = GFLOP_PER_IMG_ENCODER + GFLOP_PER_IMG_TAIL
+    exe_gflop = gm["flops"] / 1e9 / BATCH + GFLOP_PER_IMG_ATTENTION + GFLOP_PER_IMG_TAIL     # what the HIP path executes: the last block runs on the class rows only
+    line = {
+        "sclk_mhz_under_load": sclk, "power_w": power,
+        "clock_source": {k: clk.get(k) for k in ("source", "samples", "sclk_mhz", "power_w")},
+        "self_check": check,
+        "roofline": {"bound": "mfma", "kernel": "linear4w_kernel (four-wave 256 x 256 tiles, hand-scheduled asm K-loop) + linear_fast_kernel (row-split tails) + linear_small_kernel (fp16 MFMA GEMM: every encoder linear incl. patch embedding and projection, with bias / QuickGELU / residual add in its epilogue"
+                                                + "; the LayerNorms are separate passes (the reference's rounding points); the class-row tail runs the small-M variant)",
+                     "achieved": gm["tflops"], "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": gm["tflops"] / MFMA_PEAK_TFLOPS,
+                     "frac_at_sustained_clock": (gm["tflops"] / (MFMA_PEAK_TFLOPS * sclk / 2400.0)) if sclk else None,
+                     # context, not the contract's peak: what the matrix pipe sustains on this class of operands under the 1.4 kW socket cap (register-only loops,
+                     # tools/probe/mfma_power.hip, measured on other boxes of the pool; on zero operands the same loops reach the nominal 2.5 PFLOP/s)
+                     "power_limited_reference": {"mfma_16x16x32_registers_only_tflops": 1940.0, "four_wave_k_loop_alone_tflops": 1435.0,
+                                                 "frac_of_registers_only": gm["tflops"] / 1940.0, "source": "profiles/r05_mfma_power_probe.txt, r05_gemm4w_epilogue.txt"},
+                     "traffic": traffic, "traffic_unit": f"HBM bytes per launch (profiles/{traffic_file}: {traffic_note})",
+                     "launches_per_step": gm["launches"], "avg_launch_us": gm["avg_us"],
+                     "gemm_ms_per_step": gm["total_ms"], "algorithmic_gflop_per_step": gm["flops"] / 1e9,
+                     "per_variant": gm.get("per_variant"),
+                     "timed_launches": gm.get("timed_launches"),
+                     "method": "the GEMM kernels' own measurement hook (pclip_gemm_timing): every workgroup of every GEMM launch of one instrumented step folds the device's 100 MHz counter into (min begin, max end) — the kernel's span as rocprofv3 --kernel-trace reports it, with nothing between the kernels"},
+        "whole_path": {"note": "reference-equivalent = the FLOPs the REFERENCE module spends per image (every token through all 12 blocks); executed = what the HIP path runs "
+                               "(GEMM launches of the instrumented step + attention contractions + adapter + similarity: the last block works on the class rows only)",
+                       "reference_equivalent_gflop_per_image": ref_gflop, "reference_equivalent_tflops": imgs_per_s / world * ref_gflop / 1e3,
+                       "reference_equivalent_frac_of_mfma_peak": imgs_per_s / world * ref_gflop / 1e3 / MFMA_PEAK_TFLOPS,
+                       "executed_gflop_per_image": exe_gflop, "executed_tflops": imgs_per_s / world * exe_gflop / 1e3,
+                       "executed_frac": imgs_per_s / world * exe_gflop / 1e3 / MFMA_PEAK_TFLOPS},
+    }
+    if world == 1 and not args.no_extra and hooks.instrument:
+        try:
+            line["extra"] = {"c2_kernels": c2_kernels(device), "c3_classify": c3_classify(device)}
+        except Exception as e:                       # side measurements never take the headline down
+            line["extra"] = {"error": repr(e)}
+    if world == 1 and not args.no_cpu_baseline and hooks.instrument:
+        line["cpu_baseline"] = cpu_baseline()
+    if check != "ok":
+        # a step whose rows depend on the batch around them is not the workload: no headline number, and a failing exit status behind the line
+        line["invalid_value"], line["value"] = imgs_per_s, None
+    return line
 
 
 if __name__ == "__main__":

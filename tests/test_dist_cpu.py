@@ -176,7 +176,7 @@ def test_bench_step_function_two_ranks_match_one():
     assert len(one[0]) == 24 and two[0] + two[1] == one[0]
 
 
-def _bench_main_worker(rank, world, port, outdir):
+def _bench_main_worker(rank, world, port, outdir, full):
     """bench.py's OWN run(): the rank / world environment of torch.distributed.run, build_state's support-set sharding, warm-up, barrier +
     max-over-ranks timing, the self-check collective and the single JSON line — on CPU over gloo with the oracle's stages behind
     proto_clip_amd.dist.hot_path_step (the first real `--gpus 8` run must not die on host logic)."""
@@ -235,23 +235,27 @@ def _bench_main_worker(rank, world, port, outdir):
     CpuHooks.build_state, CpuHooks.step, CpuHooks.self_check = staticmethod(build_state), staticmethod(step), staticmethod(self_check)
 
     buf = io.StringIO()
-    args = argparse.Namespace(gpus=world, steps=3, warmup=1, no_cpu_baseline=True, no_extra=True, cpu_worker=None,
+    args = argparse.Namespace(gpus=world, steps=3, warmup=1, full=full, no_cpu_baseline=True, no_extra=True, cpu_worker=None,
                               dump_outputs=os.path.join(outdir, "dump"))
     bench.run(args, CpuHooks, out=buf)
-    assert calls["build"] == 1 and calls["check"] == 1 and calls["step"] == 1 + 3 + 2       # warm-up + timed + the self-check's two
+    if full:
+        assert calls["build"] == 1 and calls["check"] == 1 and calls["step"] == 1 + 3 + 2   # warm-up + timed + the self-check's two
+    else:
+        assert calls["build"] == 1 and calls["check"] == 0 and calls["step"] == 1 + 3       # warm-up + timed, nothing after them
     with open(os.path.join(outdir, f"out{rank}.txt"), "w") as f:
         f.write(buf.getvalue())
 
 
-def test_bench_main_plumbing_two_ranks(tmp_path):
+def _bench_line(tmp_path, full):
     import json
-    port = 35500 + (os.getpid() % 2000)
-    mp.spawn(_bench_main_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    port = (35500 if full else 37500) + (os.getpid() % 2000)
+    mp.spawn(_bench_main_worker, args=(2, port, str(tmp_path), full), nprocs=2, join=True)
     out0, out1 = (tmp_path / "out0.txt").read_text(), (tmp_path / "out1.txt").read_text()
     assert out1 == "" and out0.count("\n") == 1                           # ONE line, from rank 0 only
     line = json.loads(out0)
     assert line["n_gpus"] == 2 and line["rccl_world_size"] == 2 and line["steps"] == 3 and line["warmup"] == 1
-    assert line["scaling"] == "weak" and line["self_check"] == "ok" and line["higher_is_better"] is True
+    assert line["scaling"] == "weak" and line["higher_is_better"] is True
+    assert line["unit"] == "query images/sec" and line["dtype"] == "f16" and line["metric"].startswith("query images/sec")
     assert line["config"]["batch_per_gpu"] == 12 and line["config"]["global_batch"] == 24
     # value = the units ALL ranks processed / the slowest rank's time
     assert abs(line["value"] - 3 * 12 * 2 / (line["ms_per_step"] * 3 / 1e3)) < 1e-6 * line["value"]
@@ -260,3 +264,16 @@ def test_bench_main_plumbing_two_ranks(tmp_path):
     for r in range(2):
         top1 = np.load(tmp_path / "dump" / f"top1_rank{r}.npy")
         assert top1.shape == (12,) and top1.dtype == np.float64 and np.all((top1 >= 0) & (top1 < 9) & (top1 == np.round(top1)))
+    return line
+
+
+def test_bench_main_plumbing_two_ranks(tmp_path):
+    """--full: the self-check collective runs after the timed steps and its verdict is in the line."""
+    line = _bench_line(tmp_path, full=True)
+    assert line["self_check"] == "ok" and "roofline" in line and "whole_path" in line
+
+
+def test_bench_plain_run_two_ranks(tmp_path):
+    """A plain run: warm-up, timed steps, dump and the headline line; no self-check, no instrumented or side measurements."""
+    line = _bench_line(tmp_path, full=False)
+    assert not {"self_check", "roofline", "whole_path", "sclk_mhz_under_load", "clock_source"} & set(line)

@@ -1,4 +1,4 @@
-for r in 1 2; do for m in 0 1; do PCLIP_ATT_PIPE=$m python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('pipe $m', round(d['value']), round(d['ms_per_step'],3), d['sclk_mhz_under_load'])"; done; done
+for r in 1 2; do for m in 0 1; do PCLIP_ATT_PIPE=$m python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('pipe $m', round(d['value']), round(d['ms_per_step'],3), d['sclk_mhz_under_load'])"; done; done
 python - <<'PY'
 import torch, sys
 sys.path.insert(0, '.')

@@ -1,9 +1,10 @@
 # Round-6 call A: the new full-size routing tests, a baseline bench line of this round's box, and the ResNet-50 evidence: rocprofv3 --stats and
 # SQ / traffic counters of tools/rn_prof.py (RN50, batch 256, three encode_image passes).
 mkdir -p gpurun_out
+OUT=${OUT:-out}; mkdir -p $OUT                         # the bench.py --full lines and what reads them
 timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -q --timeout 600 --tb=short -k "full_size or alpha_outside or fused" 2>&1 | tail -8 > gpurun_out/r06_a_pytest.log; tail -5 gpurun_out/r06_a_pytest.log
-timeout 900 python bench.py --steps 20 --warmup 5 > gpurun_out/r06_bench_v0.json 2> gpurun_out/r06_bench_v0.err; echo "bench rc=$?"
-python -c "import json; d=json.load(open('gpurun_out/r06_bench_v0.json')); print('BENCH', d['value'] and round(d['value']), d['ms_per_step'], d['self_check'], d['roofline']['achieved'], d['roofline']['frac'], d.get('sclk_mhz_under_load'))"
+timeout 900 python bench.py --steps 20 --warmup 5 --full > $OUT/r06_bench_v0.json 2> $OUT/r06_bench_v0.err; echo "bench rc=$?"
+python -c "import json; d=json.load(open('$OUT/r06_bench_v0.json')); print('BENCH', d['value'] and round(d['value']), d['ms_per_step'], d['self_check'], d['roofline']['achieved'], d['roofline']['frac'], d.get('sclk_mhz_under_load'))"
 R=$GRAFT_REPO_ROOT; cd /tmp && export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_rn50 -o rn -- python $R/tools/rn_prof.py > $R/gpurun_out/prof_rn50.log 2>&1
 cp $R/gpurun_out/prof_rn50/rn_kernel_stats.csv $R/gpurun_out/r06_rn50_kernel_stats.csv 2>/dev/null
