@@ -170,7 +170,8 @@ int pclip_hp_sweep(const float* d2i, const float* d2t, const int32_t* labels, in
 
 /* Adapter_FC.forward (model.py:81-95): y = r16(r16(ratio*LN_D(W2 LN_{D/r}(W1 x))) + r16((1-ratio)*x)).
  * x [B,D]; w1 [H,D]; g1,b1 [H]; w2 [D,H]; g2,b2 [D]; all fp16.  l2norm_out=1 also applies the
- * following row normalise (main.py:408-409).  y_sq nullable (fp32 ||y||^2). */
+ * following row normalise (main.py:408-409).  y_sq nullable (fp32 ||y||^2).
+ * D % 64 == 0, H = D / reduction a multiple of 32 (one k-step of the MFMA, the column count of the GEMM's thinnest tile), both <= 4096. */
 int pclip_adapter_fc_f16(const void* x, int B, int D, int H, const void* w1, const void* g1, const void* b1,
                          const void* w2, const void* g2, const void* b2, float ratio, float one_minus_ratio,
                          int l2norm_out, void* y, float* y_sq, void* ws, size_t ws_bytes,
@@ -190,6 +191,14 @@ int pclip_adapter_conv_f16(const void* x, int B, int D, int three_x, const void*
                            const void* ln1b, const void* conv2, const void* ln2w, const void* ln2b,
                            const void* conv3, const void* ln3w, const void* ln3b, int l2norm_out, void* y,
                            float* y_sq, pclip_stream_t stream);
+
+/* The same at `width` W in {8, 16, 24, 32} (model.py:19 `Adapter(c_in, c_type, width=16)`); any other width is PCLIP_E_INVALID.
+ * conv1 [W], ln1w/ln1b [W*s*s], conv2 [W*W*3*3] (layout [co][ci][ky][kx]), ln2w/ln2b [W*s*s], conv3 [W], ln3w/ln3b [s*s], s = ceil(sqrt(D)), D <= 1024.
+ * width 16 IS pclip_adapter_conv_f16 (same kernels, same bits); the other widths run conv2 on the matrix pipe with W as a compile-time constant. */
+int pclip_adapter_conv_w_f16(const void* x, int B, int D, int three_x, int width, const void* conv1, const void* ln1w,
+                             const void* ln1b, const void* conv2, const void* ln2w, const void* ln2b,
+                             const void* conv3, const void* ln3w, const void* ln3b, int l2norm_out, void* y,
+                             float* y_sq, pclip_stream_t stream);
 
 /* ---- CLIP encoder building blocks: clip/model.py:155-238, 338-354 ------------------------- */
 
@@ -445,6 +454,15 @@ int pclip_adapter_conv_backward_f16(const void* x, const void* g, int B, int D, 
                                     const void* ln1b, const void* conv2, const void* ln2w, const void* ln2b, const void* conv3,
                                     const void* ln3w, float* pw1, float* pw2, float* pw3, float* pg1, float* pb1, float* pg2,
                                     float* pb2, float* pg3, float* pb3, pclip_stream_t stream);
+
+/* The same at `width` W in {8, 16, 24, 32}: pw1/pw3 [R,W], pw2 [R, W*W*9], pg1/pb1, pg2/pb2 [R, W*s*s], pg3/pb3 [R, s*s] with
+ * R = pclip_adapter_conv_w_backward_partials(B, D, three_x, width).  Width 16 IS the pair above; every other width writes one partial per
+ * input row (R = B) and needs no workspace: the forward is recomputed in LDS at every (W, D <= 1024). */
+int pclip_adapter_conv_w_backward_partials(int B, int D, int three_x, int width);
+int pclip_adapter_conv_w_backward_f16(const void* x, const void* g, int B, int D, int three_x, int width, const void* conv1,
+                                      const void* ln1w, const void* ln1b, const void* conv2, const void* ln2w, const void* ln2b,
+                                      const void* conv3, const void* ln3w, float* pw1, float* pw2, float* pw3, float* pg1, float* pb1,
+                                      float* pg2, float* pb2, float* pg3, float* pb3, pclip_stream_t stream);
 
 /* One torch.optim.AdamW step (main.py:134-135: eps 1e-4, weight_decay 0.05) on fp16 parameters with fp16 moments, every
  * intermediate rounded to fp16 where the single-tensor implementation materialises an fp16 tensor; step counts from 1. */

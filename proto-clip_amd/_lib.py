@@ -54,6 +54,7 @@ _SIGS = {
                              c_size_t, _P],
     "pclip_layernorm_blend_f16": [_P, _P, _P, c_float, _P, c_float, c_float, c_int, _P, _P, c_int, c_int, _P],
     "pclip_adapter_conv_f16": [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P],
+    "pclip_adapter_conv_w_f16": [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P],
     "pclip_gemm_f16": [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P],
     "pclip_gemm4w_f16": [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P],
     "pclip_gemm4w_var_f16": [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, _P],
@@ -92,6 +93,8 @@ _SIGS = {
     "pclip_colsum_f32": [_P, c_int, c_int, c_int, c_float, _P, c_int, _P, c_size_t, _P],
     "pclip_adapter_conv_backward_f16": [_P, _P, c_int, c_int, c_int] + [_P] * 8 + [_P] * 9 + [_P],
     "pclip_adapter_conv_backward_partials": [c_int, c_int, c_int],
+    "pclip_adapter_conv_w_backward_f16": [_P, _P, c_int, c_int, c_int, c_int] + [_P] * 8 + [_P] * 9 + [_P],
+    "pclip_adapter_conv_w_backward_partials": [c_int, c_int, c_int, c_int],
     "pclip_addscaled_rows_f32": [_P, c_int, _P, c_int, _P, c_float, c_int, c_int, _P],
     "pclip_nll_grad": [_P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, _P, _P, _P, _P, _P, _P, _P],
     "pclip_nll_rows": [_P, c_int, _P, c_int, c_int, _P, _P, _P, _P],

@@ -1319,8 +1319,8 @@ extern "C" int pclip_adapter_fc_f16(const void* x, int B, int D, int H, const vo
                                     int l2norm_out, void* y, float* y_sq, void* ws, size_t ws_bytes,
                                     pclip_stream_t stream) {
     PCLIP_REQUIRE(x && w1 && g1 && b1 && w2 && g2 && b2 && y, "pclip_adapter_fc_f16: null pointer");
-    PCLIP_REQUIRE(B >= 0 && D > 0 && H > 0 && D % 64 == 0 && H % 64 == 0 && D <= 4096 && H <= 4096,
-                  "pclip_adapter_fc_f16: D=%d and H=%d must be multiples of 64 (<= 4096)", D, H);
+    PCLIP_REQUIRE(B >= 0 && D > 0 && H > 0 && D % 64 == 0 && H % 32 == 0 && D <= 4096 && H <= 4096,
+                  "pclip_adapter_fc_f16: D=%d must be a multiple of 64 and H=%d a multiple of 32 (<= 4096)", D, H);
     if (B == 0) return PCLIP_OK;
     const size_t need = pclip_workspace_bytes(PCLIP_OP_ADAPTER_FC, B, H, D);
     PCLIP_REQUIRE(ws != nullptr, "pclip_adapter_fc_f16: workspace required");

@@ -144,18 +144,22 @@ def search_scale_step(cfg):
     return cfg
 
 
-def check_shape_envelope(N, K, D, adapter, training, eval_path=True):
+def check_shape_envelope(N, K, D, adapter, training, eval_path=True, *, width=16, reduction=4):
     """The kernels' hard limits, checked up front with one clear message instead of a PclipError from deep inside a step
-    (README 'Supported shapes'; the reference itself has none of these limits — every dataset and backbone it ships fits)."""
+    (README 'Supported shapes'; the reference itself has none of these limits — every dataset and backbone it ships fits).
+    `width` is the conv adapters' channel count, `reduction` the fc adapter's (hidden size D // reduction)."""
     problems = []
     if N > 4096:
         problems.append(f"{N} classes: the softmax / fusion / (alpha, beta)-sweep kernels hold a class row in registers (N <= 4096)")
     if eval_path and (D % 64 or D > 4096):
         problems.append(f"feature dim {D}: the fp16 distance GEMM of the evaluation path needs a multiple of 64, <= 4096")
     if adapter in ("conv-2x", "conv-3x") and D > 1024:
-        problems.append(f"conv adapter at D = {D}: its [16, s, s] stack lives in LDS (D <= 1024)")
-    if adapter == "fc" and (D % 256):
-        problems.append(f"fc adapter at D = {D}: D and D / 4 must be multiples of 64")
+        problems.append(f"conv adapter at D = {D}: its [width, s, s] stack lives in LDS (D <= 1024)")
+    if adapter in ("conv-2x", "conv-3x") and width not in ops.ADAPTER_WIDTHS:
+        problems.append(f"conv adapter at width {width}: the kernels are built for widths {ops.ADAPTER_WIDTHS}")
+    if adapter == "fc" and (D % 64 or reduction < 1 or (D // reduction) % 32 or D // reduction == 0):
+        problems.append(f"fc adapter at D = {D}, reduction = {reduction}: D must be a multiple of 64 and the hidden size "
+                        f"D // reduction = {D // max(reduction, 1)} a multiple of 32")
     if training and K > 32:
         problems.append(f"{K} shots: the prototype backward keeps a class's shots in LDS (K <= 32)")
     if training and D > 2048:
@@ -171,6 +175,7 @@ def run_proto_clip(cfg, visual_memory_keys, visual_memory_values, val_features, 
     ndim, NxK = visual_memory_keys.shape
     K = cfg["shots"]
     N = NxK // K
+    # main.make_adapter builds the adapter as the reference's main.py does: default width / reduction
     check_shape_envelope(N, K, ndim, cfg.get("adapter", "fc"), training=not cfg.get("only_test", False))
     cfg = search_scale_step(cfg)                                        # main.py:111
     qt = variant == "qt"                                               # main.qt.py: queries from the image loader

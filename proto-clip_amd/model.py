@@ -30,8 +30,9 @@ class Adapter(nn.Module):
 
     def __init__(self, c_in, c_type, width=16, dtype=None):
         super().__init__()
-        if width != 16:
-            raise PclipError("the gfx950 adapter kernel is specialised for width=16 (the reference's value)")
+        if width not in ops.ADAPTER_WIDTHS:
+            raise PclipError(f"conv adapter width {width}: the gfx950 adapter kernels are built for widths {ops.ADAPTER_WIDTHS} "
+                             "(16 is the reference's value)")
         if c_type not in ("conv-3x", "conv-2x"):
             raise PclipError(f"unknown adapter type {c_type!r}")
         self.c_in = c_in
@@ -79,3 +80,11 @@ class Adapter_FC(nn.Module):
             return pag.AdapterFcFn.apply(image_features, fc[0].weight, fc[1].weight, fc[1].bias, fc[2].weight, fc[3].weight, fc[3].bias)
         return ops.adapter_fc(image_features, fc[0].weight, fc[1].weight, fc[1].bias, fc[2].weight, fc[3].weight,
                               fc[3].bias, ratio=0.2, l2norm_out=l2norm_out)
+
+
+def adapter_shape_args(adapter):
+    """(kind, {width | reduction}) of an adapter module, as main.check_shape_envelope takes them."""
+    if isinstance(adapter, Adapter_FC):
+        lin = adapter.fc[0]
+        return "fc", {"reduction": lin.in_features // lin.out_features}
+    return adapter.c_type, {"width": adapter.conv1.out_channels}

@@ -355,18 +355,30 @@ def layernorm_blend(h, gamma, beta, x, ratio: float = 0.2, l2norm_out: bool = Fa
     return y
 
 
+ADAPTER_WIDTHS = (8, 16, 24, 32)      # conv adapter widths the kernels are instantiated for (csrc/pclip_adapter.hip: 16, pclip_adapter_w.hip: the rest)
+
+
+def _adapter_width(conv1):
+    width = int(conv1.shape[0])
+    if width not in ADAPTER_WIDTHS:
+        raise _lib.PclipError(f"conv adapter width {width}: the gfx950 adapter kernels are built for widths {ADAPTER_WIDTHS}")
+    return width
+
+
 def adapter_conv(x, three_x: bool, conv1, ln1w, ln1b, conv2, ln2w, ln2b, conv3, ln3w, ln3b,
                  l2norm_out: bool = False, want_sq: bool = False):
-    """Adapter.forward (model.py:49-78): conv-2x / conv-3x feature adapter, whole pipeline in one kernel."""
+    """Adapter.forward (model.py:49-78): conv-2x / conv-3x feature adapter, whole pipeline in one kernel.  The width is conv1's
+    channel count."""
     require_cuda(x, conv1)
     x = _f16c(x)
     B, D = x.shape
+    width = _adapter_width(conv1)
     y = torch.empty_like(x)
     sq = torch.empty(B, dtype=torch.float32, device=x.device) if want_sq else None
     f = lambda t: None if t is None else ptr(_f16c(t))
-    check(_lib.load().pclip_adapter_conv_f16(ptr(x), B, D, int(three_x), f(conv1), f(ln1w), f(ln1b), f(conv2),
-                                             f(ln2w), f(ln2b), f(conv3), f(ln3w), f(ln3b), int(l2norm_out), ptr(y),
-                                             ptr(sq), stream()), "pclip_adapter_conv_f16")
+    check(_lib.load().pclip_adapter_conv_w_f16(ptr(x), B, D, int(three_x), width, f(conv1), f(ln1w), f(ln1b), f(conv2),
+                                               f(ln2w), f(ln2b), f(conv3), f(ln3w), f(ln3b), int(l2norm_out), ptr(y),
+                                               ptr(sq), stream()), "pclip_adapter_conv_w_f16")
     return (y, sq) if want_sq else y
 
 
@@ -890,39 +902,42 @@ def l2norm_rows_backward_f32_(gx: torch.Tensor, x: torch.Tensor, gy: torch.Tenso
 
 def adapter_conv_backward(x, g, three_x: bool, conv1, ln1w, ln1b, conv2, ln2w, ln2b, conv3, ln3w, ln3b, chunk: int = 512):
     """Parameter gradients (fp32, shaped like the parameters) of the conv adapter for upstream g = dL/d(output); rows are
-    processed `chunk` at a time (per-row contributions live in scratch, then a deterministic column sum)."""
+    processed `chunk` at a time (per-row contributions live in scratch, then a deterministic column sum).  The width is
+    conv1's channel count."""
     require_cuda(x, g)
     x, g = _f16c(x), _f16c(g)
     B, D = x.shape
+    W = _adapter_width(conv1)
     s = int(math.ceil(math.sqrt(D)))
-    s2, n1 = s * s, 16 * s * s
+    s2, n1, n2 = s * s, W * s * s, W * W * 9
     dev = x.device
     f32 = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
-    out = {"conv1.weight": f32(16), "conv3.weight": f32(16), "bn1.weight": f32(n1), "bn1.bias": f32(n1), "bn3.weight": f32(s2),
+    out = {"conv1.weight": f32(W), "conv3.weight": f32(W), "bn1.weight": f32(n1), "bn1.bias": f32(n1), "bn3.weight": f32(s2),
            "bn3.bias": f32(s2)}
     if three_x:
-        out.update({"conv2.weight": f32(2304), "bn2.weight": f32(n1), "bn2.bias": f32(n1)})
+        out.update({"conv2.weight": f32(n2), "bn2.weight": f32(n1), "bn2.bias": f32(n1)})
     lib = _lib.load()
-    # rows of partial sums a launch over nb rows writes: the persistent MFMA kernel (conv-3x, D <= 576) one per workgroup — then the whole batch is
-    # ONE launch + one column sum per parameter; the per-row kernels one per input row — then the batch is walked in chunks of `chunk` rows
-    persistent = B > 0 and lib.pclip_adapter_conv_backward_partials(B, D, int(three_x)) < B
-    c = max(B, 1) if persistent else min(chunk, max(B, 1))
-    rows_of = lambda nb: lib.pclip_adapter_conv_backward_partials(nb, D, int(three_x))
+    # rows of partial sums a launch over nb rows writes: the persistent MFMA kernel (width 16, conv-3x, D <= 576) one per workgroup — then the whole
+    # batch is ONE launch + one column sum per parameter; the per-row kernels one per input row — then the batch is walked in chunks of `chunk` rows
+    # (fewer at the wider stacks: a row's contributions are up to 0.5 MB)
+    rows_of = lambda nb: lib.pclip_adapter_conv_w_backward_partials(nb, D, int(three_x), W)
+    persistent = B > 0 and rows_of(B) < B
+    c = max(B, 1) if persistent else min(max(chunk * 16 // W, 1), max(B, 1))
     rmax = max(rows_of(c), 1)
     sc = lambda n: torch.empty(rmax, n, dtype=torch.float32, device=dev)
-    pw1, pw3, pg1, pb1, pg3, pb3 = sc(16), sc(16), sc(n1), sc(n1), sc(s2), sc(s2)
-    pw2, pg2, pb2 = (sc(2304), sc(n1), sc(n1)) if three_x else (None, None, None)
+    pw1, pw3, pg1, pb1, pg3, pb3 = sc(W), sc(W), sc(n1), sc(n1), sc(s2), sc(s2)
+    pw2, pg2, pb2 = (sc(n2), sc(n1), sc(n1)) if three_x else (None, None, None)
     for lo in range(0, B, c):
         nb = min(c, B - lo)
-        check(lib.pclip_adapter_conv_backward_f16(
-            ptr(x[lo:lo + nb]), ptr(g[lo:lo + nb]), nb, D, int(three_x), ptr(conv1), ptr(ln1w), ptr(ln1b),
+        check(lib.pclip_adapter_conv_w_backward_f16(
+            ptr(x[lo:lo + nb]), ptr(g[lo:lo + nb]), nb, D, int(three_x), W, ptr(conv1), ptr(ln1w), ptr(ln1b),
             ptr(conv2) if three_x else None, ptr(ln2w) if three_x else None, ptr(ln2b) if three_x else None, ptr(conv3), ptr(ln3w),
             ptr(pw1), ptr(pw2), ptr(pw3), ptr(pg1), ptr(pb1), ptr(pg2), ptr(pb2), ptr(pg3), ptr(pb3), stream()),
-            "pclip_adapter_conv_backward_f16")
+            "pclip_adapter_conv_w_backward_f16")
         for name, part in (("conv1.weight", pw1), ("conv3.weight", pw3), ("bn1.weight", pg1), ("bn1.bias", pb1), ("bn3.weight", pg3),
                            ("bn3.bias", pb3), ("conv2.weight", pw2), ("bn2.weight", pg2), ("bn2.bias", pb2)):
             if part is not None:
                 colsum_f32(part, rows=rows_of(nb), out=out[name])
-    shapes = {"conv1.weight": (16, 1, 1, 1), "conv3.weight": (1, 16, 1, 1), "conv2.weight": (16, 16, 3, 3), "bn1.weight": (16, s, s),
-              "bn1.bias": (16, s, s), "bn2.weight": (16, s, s), "bn2.bias": (16, s, s), "bn3.weight": (1, s, s), "bn3.bias": (1, s, s)}
+    shapes = {"conv1.weight": (W, 1, 1, 1), "conv3.weight": (1, W, 1, 1), "conv2.weight": (W, W, 3, 3), "bn1.weight": (W, s, s),
+              "bn1.bias": (W, s, s), "bn2.weight": (W, s, s), "bn2.bias": (W, s, s), "bn3.weight": (1, s, s), "bn3.bias": (1, s, s)}
     return {k: v.view(shapes[k]) for k, v in out.items()}

@@ -13,7 +13,7 @@ import os
 import torch
 
 from . import ops
-from .model import Adapter, Adapter_FC
+from .model import Adapter, Adapter_FC, adapter_shape_args
 from .utils import get_model_dir_root
 
 
@@ -38,12 +38,16 @@ def load_pretrained_mb_and_adapters(config=None, memory_bank_v_path=None, memory
         if adapter_type is None:
             raise Exception("Please mention the adapter type in the args or in the config file.")
         ndim = embeddings_v.shape[1]
-        adapter = (Adapter(ndim, c_type=adapter_type, dtype=torch.half) if "conv" in adapter_type
-                   else Adapter_FC(ndim, dtype=torch.half)).cuda()
         try:
-            adapter.load_state_dict(torch.load(adapter_weights_path, map_location="cuda"))
+            state = torch.load(adapter_weights_path, map_location="cuda")
         except Exception:
             raise FileNotFoundError(f"File does not exist: {adapter_weights_path}")
+        # the conv width / the fc hidden size are the checkpoint's own (Adapter(width=...), Adapter_FC(reduction=...))
+        if "conv" in adapter_type:
+            adapter = Adapter(ndim, c_type=adapter_type, width=state["conv1.weight"].shape[0], dtype=torch.half).cuda()
+        else:
+            adapter = Adapter_FC(ndim, reduction=ndim // state["fc.0.weight"].shape[0], dtype=torch.half).cuda()
+        adapter.load_state_dict(state)
     return embeddings_v.detach(), embeddings_t.detach(), adapter
 
 
@@ -59,6 +63,9 @@ class ProtoClipClassifier:
         self.class_names = class_names
         NxK = embeddings_v.shape[0]
         self.N = NxK // shots
+        from .main import check_shape_envelope
+        kind, shape_kw = adapter_shape_args(adapter)
+        check_shape_envelope(self.N, shots, embeddings_v.shape[1], kind, training=False, **shape_kw)
         with torch.no_grad():                              # proto_clip_classifier.py:58-71
             self.z_img_proto, self.zi_sq = ops.proto_build(embeddings_v.detach(), self.N, shots, want_sq=True)
             self.z_text_proto, self.zt_sq = ops.l2norm_rows(embeddings_t.detach(), want_sq=True)

@@ -19,7 +19,7 @@ import torch
 from . import dist as pdist
 from . import ops
 from ._lib import PclipError
-from .model import Adapter, Adapter_FC
+from .model import Adapter, Adapter_FC, adapter_shape_args
 
 INFO_NCE_TEMPERATURE = 0.1      # info-nce-pytorch default (the package is not pinned by the reference)
 
@@ -104,7 +104,8 @@ class ProtoClipTrainer:
         self.N = NK // self.K
         self.D = D
         from .main import check_shape_envelope
-        check_shape_envelope(self.N, self.K, D, "fc" if isinstance(adapter, Adapter_FC) else "conv-3x", training=True, eval_path=False)
+        kind, shape_kw = adapter_shape_args(adapter)
+        check_shape_envelope(self.N, self.K, D, kind, training=True, eval_path=False, **shape_kw)
         self.alpha, self.beta = float(alpha), float(beta)
         self.losses = list(cfg.get("losses", []))
         self.keys_rows = ops.transpose(visual_memory_keys)                      # constant query source (main.py:266)
