@@ -159,6 +159,27 @@ int pclip_classify_panel_stats(int* out3, int reset);
 int pclip_classify_panel_dump_f16(const void* q, const void* zi, const void* zt, int Q, int N, int D, float* dump, int exact,
                                   void* ws, size_t ws_bytes, pclip_stream_t stream);
 
+/* ---- cosine logits: clip/model.py:356-370 `CLIP.forward`, and the zero-shot line `100. * features @ clip_weights` ---------------- */
+
+/* logits[m, t] = r16( sum_d r16(scale * a'[m, d]) * b'[t, d] ), fp32 accumulation on the matrix pipe (clip/model.py:359-367: both feature matrices
+ * normalised, `logit_scale * image_features @ text_features.t()`; main.py's zero-shot baseline on cached features: flags 0, scale 100).
+ * a [M, D], b [T, D] fp16 rows lda / ldb >= D halves apart; a' / b' = the rows as given, or L2-normalised with the arithmetic of pclip_l2norm_rows_f16
+ * (bit-identical to calling it first) under PCLIP_LOGITS_NORMALIZE_A / _B.  `scale` multiplies in fp32 as passed: the reference casts its 0-dim
+ * logit_scale.exp() to fp16 first (its result is r16(r16(s) * x)), so a caller that reproduces it passes the fp16-rounded value.
+ * Any M >= 1, T >= 1; D % 64 == 0, D <= 4096; lda, ldb, ldl multiples of 8 halves, 16-byte aligned bases.  Nothing at a column >= D, a row >= M of a or a
+ * row >= T of b is read; nothing at a column >= T or a row >= M of logits is written.
+ * Outputs, each nullable, at least one: logits [M, ldl >= T] fp16; argmax [M] (lowest index among equal logits); topk_v (fp16) / topk_i [M, k],
+ * 1 <= k <= min(16, T), descending, ascending index among equal values (k = 0: both NULL).  argmax / top-k are taken over the ROUNDED fp16 logits — what a
+ * reduction of the written matrix gives — and need T <= 4096; with logits == NULL the matrix never reaches memory.
+ * A row's logits do not depend on M or the rows that travel with it, a column's not on T (one k order on every route), bit for bit.
+ * ws: pclip_workspace_bytes(PCLIP_OP_LOGITS, M, T, D) bytes with PCLIP_LOGITS_NORMALIZE_B (PCLIP_E_WORKSPACE if smaller), unused otherwise.
+ * Everything outside this envelope is PCLIP_E_INVALID before any launch. */
+int pclip_cosine_logits_f16(const void* a, int lda, int M, const void* b, int ldb, int T, int D, float scale, int flags,
+                            void* logits, int ldl, int32_t* argmax, void* topk_v, int32_t* topk_i, int k,
+                            void* ws, size_t ws_bytes, pclip_stream_t stream);
+#define PCLIP_LOGITS_NORMALIZE_A 0x1
+#define PCLIP_LOGITS_NORMALIZE_B 0x2
+
 /* (alpha, beta) grid, main.py:142-146, 187-199, 419-430: from the two distance matrices evaluate all
  * na*nb pairs and accumulate correct[ia*nb + ib] += #{q : argmax_n p == labels[q]} (int32, the
  * caller zeroes it; lowest-index tie rule).  Replaces 3*na*nb `P` calls + host syncs. */
@@ -492,6 +513,7 @@ int pclip_preprocess_u8(const void* const* srcs, const int32_t* desc, int B, int
 #define PCLIP_OP_SQDIST 1
 #define PCLIP_OP_CLASSIFY 2
 #define PCLIP_OP_ADAPTER_FC 3
+#define PCLIP_OP_LOGITS 4 /* Q = M, N = T */
 size_t pclip_workspace_bytes(int op, int Q, int N, int D);
 
 #ifdef __cplusplus

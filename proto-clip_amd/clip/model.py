@@ -436,7 +436,16 @@ class CLIP(nn.Module):
         return ops.gemm(eot, projT)                                              # @ text_projection, 352
 
     def forward(self, image, text):
-        raise NotImplementedError("contrastive forward (clip/model.py:356-370) is not on the Proto-CLIP hot path")
+        """(logits_per_image [n_img, n_txt], logits_per_text = its transpose view), fp16 (clip/model.py:356-370): both feature matrices L2-normalised in fp16,
+        the image side scaled by logit_scale.exp() and rounded, one cosine-logit kernel.  logit_scale stays fp32 under convert_weights, but as a 0-dim operand
+        of an fp16 tensor the reference casts it to fp16 before the multiplication: the scale is the fp16-rounded value (14.2890625 for ln(1 / 0.07))."""
+        with torch.no_grad():
+            image_features = self.encode_image(image)
+            text_features = self.encode_text(text)
+            scale = float(self.logit_scale.exp().half())
+            logits_per_image, _, _, _ = ops.cosine_logits(image_features, text_features, scale, normalize_a=True, normalize_b=True)
+            logits_per_image = logits_per_image.contiguous()           # (dense as the reference's, whatever the prompt count: a copy only where n_txt % 8 != 0)
+            return logits_per_image, logits_per_image.t()
 
 
 def convert_weights(model: nn.Module):

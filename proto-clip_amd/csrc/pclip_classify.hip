@@ -509,6 +509,10 @@ extern "C" size_t pclip_workspace_bytes(int op, int Q, int N, int D) {
             // h1 [Q, D/4] fp16, h1n [Q, D/4] fp16, h2 [Q, D] fp16  (N is the hidden width here)
             return 2 * align_up((size_t)Q * N * 2, 256) + align_up((size_t)Q * D * 2, 256);
         }
+        case PCLIP_OP_LOGITS: {
+            // pclip_cosine_logits_f16 (Q = M rows of a, N = T rows of b): the normalised rows of b, dense [T, D] fp16 (PCLIP_LOGITS_NORMALIZE_B; nothing otherwise)
+            return align_up((size_t)N * D * 2, 256);
+        }
         default: return 0;
     }
 }

@@ -225,6 +225,60 @@ def proto_classify(mem, N: int, K: int, q, zt, alpha: float, beta: float, per_sh
     return (zi,) + tuple(classify(q, zi, zt, alpha, beta, want_p=want_p, want_argmax=want_argmax, topk=topk))
 
 
+def _f16_rows(t: torch.Tensor, what: str) -> torch.Tensor:
+    """A 2-D fp16 operand whose rows may be strided (a column slice of a wider buffer): taken as it is when the kernel can address it
+    (unit column stride, row stride a multiple of 8 halves, 16-byte aligned), copied otherwise."""
+    if t.dtype != torch.float16:
+        raise _lib.PclipError(f"{what}: expected a float16 tensor, got {t.dtype}")
+    if t.dim() != 2:
+        raise _lib.PclipError(f"{what}: expected a 2-D tensor, got shape {tuple(t.shape)}")
+    bad_cols = t.shape[1] > 1 and t.stride(1) != 1
+    bad_rows = t.shape[0] > 1 and (t.stride(0) < t.shape[1] or t.stride(0) % 8)                      # (a single row has no row stride to speak of)
+    if bad_cols or bad_rows or t.data_ptr() % 16:
+        return t.clone(memory_format=torch.contiguous_format)                                       # (.contiguous() would hand a dense but misaligned view back)
+    return t
+
+
+def cosine_logits(a, b, scale: float, normalize_a: bool = False, normalize_b: bool = False, want_logits: bool = True,
+                  want_argmax: bool = False, topk: int = 0, out: torch.Tensor = None):
+    """logits[m, t] = r16(sum_d r16(scale * a'[m, d]) * b'[t, d]) — clip/model.py:359-367 and the zero-shot `100. * features @ clip_weights`.
+    a [M, D], b [T, D] fp16 (row-strided views are read in place); a' / b' are the rows, L2-normalised as `l2norm_rows` does when asked.  `scale` is applied
+    in fp32 as given (CLIP.forward passes the fp16-rounded logit scale, as the reference's arithmetic does).  Returns (logits [M, T] fp16 | None,
+    argmax [M] int32 | None, topk_v [M, k] fp16 | None, topk_i [M, k] int32 | None); without `want_logits` the matrix is never written.
+    out: optional [M, >= T] fp16 buffer (row stride a multiple of 8) that receives the logits in its first T columns.
+    The logits returned are the first T columns of the buffer the kernel wrote, whose row stride is T rounded up to 8 halves: a dense tensor when T % 8 == 0,
+    a strided view otherwise (`CLIP.forward` and `utils.clip_logits` return `.contiguous()` of it)."""
+    require_cuda(a, b, out)
+    a, b = _f16_rows(a, "cosine_logits: a"), _f16_rows(b, "cosine_logits: b")
+    (M, D), (T, Db) = a.shape, b.shape
+    if D != Db:
+        raise _lib.PclipError(f"cosine_logits: a has {D} columns, b has {Db}")
+    if M < 1 or T < 1:
+        raise _lib.PclipError(f"cosine_logits: empty operand (M={M}, T={T})")
+    dev = a.device
+    lda, ldb = (a.stride(0) if M > 1 else D), (b.stride(0) if T > 1 else D)
+    logits, ldl = None, 0
+    if want_logits:
+        if out is None:
+            ldl = (T + 7) // 8 * 8
+            out = torch.empty(M, ldl, dtype=torch.float16, device=dev)
+        else:
+            if out.dtype != torch.float16 or out.dim() != 2 or out.shape[0] != M or out.shape[1] < T or out.stride(1) != 1:
+                raise _lib.PclipError(f"cosine_logits: out must be a float16 [M={M}, >= T={T}] tensor with unit column stride")
+            ldl = out.stride(0) if M > 1 else (T + 7) // 8 * 8
+        logits = out[:, :T]
+    k = int(topk)
+    am = torch.empty(M, dtype=torch.int32, device=dev) if want_argmax else None
+    tv = torch.empty(M, k, dtype=torch.float16, device=dev) if k else None
+    ti = torch.empty(M, k, dtype=torch.int32, device=dev) if k else None
+    flags = (_lib.LOGITS_NORMALIZE_A if normalize_a else 0) | (_lib.LOGITS_NORMALIZE_B if normalize_b else 0)
+    nws = _lib.workspace_bytes(_lib.OP_LOGITS, M, T, D) if normalize_b else 0
+    ws = _workspace(nws, dev) if nws else None
+    check(_lib.load().pclip_cosine_logits_f16(ptr(a), lda, M, ptr(b), ldb, T, D, float(np.float32(scale)), flags, ptr(out if want_logits else None), ldl,
+                                              ptr(am), ptr(tv), ptr(ti), k, ptr(ws), nws, stream()), "pclip_cosine_logits_f16")
+    return logits, am, tv, ti
+
+
 CLASSIFY_ROUTES = ("two stages", "one launch, small N", "one launch, mid N", "fused row panels")
 
 

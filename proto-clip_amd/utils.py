@@ -103,6 +103,39 @@ def cls_acc(output, target, topk=1):
     return 100 * acc / target.shape[0]
 
 
+def _clip_weight_rows(features, clip_weights, layout=None):
+    """The [N, D] prompt rows of a zero-shot classifier.  layout "dn": `clip_classifier`'s [D, N] (the reference's `features @ clip_weights` layout, one
+    transpose here); "nd": [N, D] rows, taken as they are; None: told from the shape, a square [D, D] tensor read as the reference's [D, N]."""
+    _as_f16_rows(features, "features")
+    _as_f16_rows(clip_weights, "clip_weights")
+    if layout not in (None, "dn", "nd"):
+        raise PclipError(f"layout={layout!r}: expected 'dn' ([D, N], as clip_classifier returns), 'nd' ([N, D] rows) or None")
+    if features.dim() != 2 or clip_weights.dim() != 2:
+        raise PclipError(f"features {tuple(features.shape)} and clip_weights {tuple(clip_weights.shape)} must be 2-D")
+    D = features.shape[1]
+    if layout is None:
+        if D not in clip_weights.shape:
+            raise PclipError(f"clip_weights {tuple(clip_weights.shape)} matches neither [D={D}, N] nor [N, D]")
+        layout = "dn" if clip_weights.shape[0] == D else "nd"
+    if clip_weights.shape[0 if layout == "dn" else 1] != D:
+        raise PclipError(f"clip_weights {tuple(clip_weights.shape)} is not {'[D, N]' if layout == 'dn' else '[N, D]'} with D={D}")
+    return ops.transpose(clip_weights) if layout == "dn" else clip_weights
+
+
+def clip_logits(features, clip_weights, scale=100., layout=None):
+    """The zero-shot CLIP baseline `100. * features @ clip_weights` (reference main.py / Tip-Adapter's zero-shot line): fp16 [Q, N] logits (dense) of cached,
+    normalised features [Q, D] against `clip_classifier`'s weights, rounded where the reference's fp16 tensors round.  layout: see `_clip_weight_rows`
+    ("dn" / "nd" say which way a square or ambiguous `clip_weights` lies)."""
+    return ops.cosine_logits(features, _clip_weight_rows(features, clip_weights, layout), scale)[0].contiguous()
+
+
+def clip_zero_shot(features, clip_weights, scale=100., topk=0, layout=None):
+    """`clip_logits(...).argmax(1)` (int64 [Q], lowest index among equal logits) without materialising the logits; with topk > 0 also
+    `.topk(topk)` -> (argmax, values [Q, k] fp16, indices [Q, k] int64)."""
+    _, am, tv, ti = ops.cosine_logits(features, _clip_weight_rows(features, clip_weights, layout), scale, want_logits=False, want_argmax=True, topk=topk)
+    return (am.long(), tv, ti.long()) if topk else am.long()
+
+
 def get_target_inds(info):
     """Episode ground-truth labels [n_class, k_query, 1] int64 on the GPU from info = (n_class, k_support, k_query)
     (reference utils.py:112-122; no caller in the reference — kept for API completeness)."""
