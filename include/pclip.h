@@ -180,6 +180,37 @@ int pclip_cosine_logits_f16(const void* a, int lda, int M, const void* b, int ld
 #define PCLIP_LOGITS_NORMALIZE_A 0x1
 #define PCLIP_LOGITS_NORMALIZE_B 0x2
 
+/* ---- cross-entropy over cosine logits, for training (clip/model.py:356-370 gives the logits; the loss is CLIP's) -------------------- */
+
+/* s[m, t] = scale * cos[m, t], cos = the fp32 matrix-pipe accumulation of a'[m, :] . b'[t, :] (a' / b' as in pclip_cosine_logits_f16 under
+ * PCLIP_CE_NORMALIZE_A / _B).  Unlike the inference kernel NOTHING is rounded to fp16 here: neither the scaled operand nor the logit.
+ *   labelled (labels [M] int32, or int64 under PCLIP_CE_LABELS_I64):  loss = mean_m ( lse_t s[m, :] - s[m, y_m] )
+ *   PCLIP_CE_SYMMETRIC (M == T, labels NULL, targets on the diagonal): loss = 1/2 ( mean_m (lse_t s[m, :] - s[m, m]) + mean_t (lse_m s[:, t] - s[t, t]) )
+ * A label is only ever compared with a column index, never used as one: a label outside [0, T) reads nothing; its row's term is lse alone (no target logit)
+ * and its gradient the plain softmax.
+ * Outputs (fp32, all required but lse_col): lse_row [M], lse_col [T] (symmetric only, NULL otherwise), row_loss [M] (the terms whose mean is the loss; the
+ * symmetric one is half the sum of row m's and column m's term), loss [1].  The [M, T] matrix never reaches memory; no floating-point atomics: two calls
+ * give the same bits, and in labelled mode a row's lse and loss term do not depend on the rows that travel with it.
+ * Any M, T >= 1; D % 64 == 0, D <= 2048; lda, ldb multiples of 8 halves >= D, 16-byte aligned bases; ws: pclip_workspace_bytes(PCLIP_OP_COSINE_CE, M, T, D)
+ * (PCLIP_E_WORKSPACE if smaller).  Everything else is PCLIP_E_INVALID before any launch. */
+int pclip_cosine_ce_f16(const void* a, int lda, int M, const void* b, int ldb, int T, int D, float scale, int flags, const void* labels,
+                        float* lse_row, float* lse_col, float* row_loss, float* loss, void* ws, size_t ws_bytes, pclip_stream_t stream);
+/* The gradients of the above (clip/model.py:356-370 has no backward of its own: torch autograd keeps the [M, T] logits and their softmax; this recomputes them
+ * tile by tile).  G[m, t] = weight * ( exp(s - lse_row[m]) + [symmetric] exp(s - lse_col[t]) - kappa [t is m's target] ), kappa = 1 labelled, 2 symmetric;
+ * weight = 1 / M for the labelled mean, 1 / (2 M) for the symmetric loss (times the upstream gradient, if the caller folds it in).
+ *   direction 0: grad [M, D] fp32 (dense) = dL/da = scale G b', chained in fp32 through the normalisation under PCLIP_CE_NORMALIZE_A;
+ *   direction 1: grad [T, D] fp32 (dense) = dL/db = scale G^T a', chained under PCLIP_CE_NORMALIZE_B.
+ * dscale (nullable, [1] fp32) = sum G o cos, the same value from either direction.  The exp tile is rounded to fp16 (unit 2^-11) for the second matrix
+ * product; weight, scale and the target term are applied in fp32.  Deterministic; in labelled mode a row of dL/da does not depend on the other rows of a.
+ * Same envelope as the forward; ws: pclip_workspace_bytes(PCLIP_OP_COSINE_CE_BACKWARD, M, T, D). */
+int pclip_cosine_ce_backward_f16(const void* a, int lda, int M, const void* b, int ldb, int T, int D, float scale, int flags, const void* labels,
+                                 const float* lse_row, const float* lse_col, float weight, int direction, float* grad, float* dscale,
+                                 void* ws, size_t ws_bytes, pclip_stream_t stream);
+#define PCLIP_CE_NORMALIZE_A 0x1
+#define PCLIP_CE_NORMALIZE_B 0x2
+#define PCLIP_CE_SYMMETRIC 0x4
+#define PCLIP_CE_LABELS_I64 0x8
+
 /* (alpha, beta) grid, main.py:142-146, 187-199, 419-430: from the two distance matrices evaluate all
  * na*nb pairs and accumulate correct[ia*nb + ib] += #{q : argmax_n p == labels[q]} (int32, the
  * caller zeroes it; lowest-index tie rule).  Replaces 3*na*nb `P` calls + host syncs. */
@@ -514,6 +545,8 @@ int pclip_preprocess_u8(const void* const* srcs, const int32_t* desc, int B, int
 #define PCLIP_OP_CLASSIFY 2
 #define PCLIP_OP_ADAPTER_FC 3
 #define PCLIP_OP_LOGITS 4 /* Q = M, N = T */
+#define PCLIP_OP_COSINE_CE 5          /* Q = M, N = T: normalised rows of b, per-panel column partials, target logits: O(T D + panels T + M) */
+#define PCLIP_OP_COSINE_CE_BACKWARD 6 /* Q = M, N = T: the walked operand normalised and transposed, for either direction: O(max(M, T) D) */
 size_t pclip_workspace_bytes(int op, int Q, int N, int D);
 
 #ifdef __cplusplus

@@ -166,5 +166,49 @@ class InfoNceFn(torch.autograd.Function):
         return cast(ga, ctx.dtypes[0]), cast(gb, ctx.dtypes[1])
 
 
+class CosineCeFn(torch.autograd.Function):
+    """Cross-entropy over the cosine logits scale * a' @ b'^T (ops.cosine_cross_entropy): labelled, or CLIP's symmetric loss.  Saves the operands and the
+    lse vectors — nothing of size M T; the backward recomputes logit tiles (pclip_cosine_ce_backward_f16).  a, b: fp16, or fp32 (cast once; the gradient
+    comes back fp32).  scale: a Python float, or a 0-dim tensor that then receives a gradient (its VALUE is read on the host: one sync, and no graph capture)."""
+
+    @staticmethod
+    def forward(ctx, a, b, scale, labels, symmetric, normalize_a, normalize_b):
+        a16 = a if a.dtype == torch.float16 else ops.cast_f16(a.float().contiguous())
+        b16 = b if b.dtype == torch.float16 else ops.cast_f16(b.float().contiguous())
+        ctx.scale = float(scale.detach()) if isinstance(scale, torch.Tensor) else float(scale)
+        ctx.mode = (bool(symmetric), bool(normalize_a), bool(normalize_b))
+        ctx.refs = tuple((t.dtype, t.shape) if isinstance(t, torch.Tensor) else None for t in (a, b, scale))      # what each gradient is cast back to
+        loss, lse_row, lse_col = ops.cosine_cross_entropy(a16, b16, ctx.scale, labels, *ctx.mode)
+        ctx.save_for_backward(a16, b16, lse_row, lse_col, labels)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        a16, b16, lse_row, lse_col, labels = ctx.saved_tensors
+        symmetric, na, nb = ctx.mode
+        need_a, need_b, need_s = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        ga, gb, gs = ops.cosine_cross_entropy_backward(a16, b16, ctx.scale, lse_row, lse_col, labels, symmetric, na, nb,
+                                                       want_a=need_a, want_b=need_b, want_scale=need_s)
+        g = g.float()
+
+        def cast(t, ref):
+            if t is None:
+                return None
+            t = (t * g).reshape(ref[1])
+            return ops.cast_f16(t.contiguous()) if ref[0] == torch.float16 else t.to(ref[0])
+        return (cast(ga, ctx.refs[0]) if need_a else None, cast(gb, ctx.refs[1]) if need_b else None, cast(gs, ctx.refs[2]) if need_s else None,
+                None, None, None, None)
+
+
+def cosine_cross_entropy(a, b, scale, labels=None, symmetric=False, normalize_a=False, normalize_b=False):
+    """The loss of `CosineCeFn` with a tape where one is wanted, the bare forward under torch.no_grad() or for constants."""
+    if wants_grad(a, b, scale if isinstance(scale, torch.Tensor) else None):
+        return CosineCeFn.apply(a, b, scale, labels, symmetric, normalize_a, normalize_b)
+    a16 = a if a.dtype == torch.float16 else ops.cast_f16(a.detach().float().contiguous())
+    b16 = b if b.dtype == torch.float16 else ops.cast_f16(b.detach().float().contiguous())
+    s = float(scale.detach()) if isinstance(scale, torch.Tensor) else float(scale)
+    return ops.cosine_cross_entropy(a16.detach(), b16.detach(), s, labels, symmetric, normalize_a, normalize_b)[0]
+
+
 def wants_grad(*tensors) -> bool:
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)

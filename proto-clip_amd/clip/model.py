@@ -447,6 +447,14 @@ class CLIP(nn.Module):
             logits_per_image = logits_per_image.contiguous()           # (dense as the reference's, whatever the prompt count: a copy only where n_txt % 8 != 0)
             return logits_per_image, logits_per_image.t()
 
+    def contrastive_loss(self, image_features, text_features):
+        """CLIP's symmetric contrastive loss of matching image / text features (the outputs of encode_image / encode_text, or trained copies of them) under
+        this model's temperature: `utils.clip_contrastive_loss` with logit_scale.exp() in fp32 — NOT the fp16-rounded value `forward` reproduces.
+        logit_scale is frozen by default; after `model.logit_scale.requires_grad_(True)` its gradient arrives through torch's own exp node.  The encoders
+        have no backward: features that come from them are constants."""
+        from ..utils import clip_contrastive_loss
+        return clip_contrastive_loss(image_features, text_features, self.logit_scale.float().exp())
+
 
 def convert_weights(model: nn.Module):
     """fp16 for Linear/conv/attention/projection parameters, fp32 elsewhere (clip/model.py:373-394)."""

@@ -513,6 +513,8 @@ extern "C" size_t pclip_workspace_bytes(int op, int Q, int N, int D) {
             // pclip_cosine_logits_f16 (Q = M rows of a, N = T rows of b): the normalised rows of b, dense [T, D] fp16 (PCLIP_LOGITS_NORMALIZE_B; nothing otherwise)
             return align_up((size_t)N * D * 2, 256);
         }
+        case PCLIP_OP_COSINE_CE: return pclip_cosine_ce_workspace(0, Q, N, D);
+        case PCLIP_OP_COSINE_CE_BACKWARD: return pclip_cosine_ce_workspace(1, Q, N, D);
         default: return 0;
     }
 }

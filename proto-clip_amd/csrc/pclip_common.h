@@ -18,6 +18,7 @@ typedef float float16_t __attribute__((ext_vector_type(16)));
 // ---- error plumbing (host) -------------------------------------------------------------------
 void pclip_set_error(const char* fmt, ...);
 int pclip_check_launch(const char* what);
+size_t pclip_cosine_ce_workspace(int backward, int M, int T, int D);   // pclip_cosine_ce.hip, behind pclip_workspace_bytes
 #define PCLIP_REQUIRE(cond, ...)              \
     do {                                      \
         if (!(cond)) {                        \

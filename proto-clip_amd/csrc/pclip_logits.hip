@@ -44,23 +44,6 @@ __device__ __forceinline__ half_t scale_r16(float s, half_t v) {
     return (half_t)p;
 }
 
-// y = r16(x / r16(||x||)) on the registers of one row: the arithmetic of l2norm_rows_kernel (pclip_proto.hip)
-template <int NCH>
-__device__ __forceinline__ void normalise_row(RowRegs<NCH>& r) {
-    const float ss = row_sq<NCH>(r);
-    const RowDiv dn(r16(sqrtf(ss)));
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        if (dn.fast) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) r.v[c][j] = (half_t)dn.div_fast((float)r.v[c][j]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) r.v[c][j] = (half_t)((float)r.v[c][j] / dn.d);
-        }
-    }
-}
-
 // rows of `b` normalised into the workspace (dense [R, D])
 template <int NCH>
 __global__ __launch_bounds__(256) void logits_norm_rows_kernel(const half_t* __restrict__ x, int ldx, half_t* __restrict__ y, int R, int D) {

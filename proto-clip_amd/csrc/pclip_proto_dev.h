@@ -43,6 +43,23 @@ __device__ __forceinline__ float load_row_sq(const half_t* xr, int D, int lane, 
     return row_sq<NCH>(r);
 }
 
+// y = r16(x / r16(||x||)) on the registers of one row: the arithmetic of l2norm_rows_kernel (pclip_proto.hip); pclip_logits.hip and pclip_cosine_ce.hip normalise their operands with it
+template <int NCH>
+__device__ __forceinline__ void normalise_row(RowRegs<NCH>& r) {
+    const float ss = row_sq<NCH>(r);
+    const RowDiv dn(r16(sqrtf(ss)));
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        if (dn.fast) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) r.v[c][j] = (half_t)dn.div_fast((float)r.v[c][j]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) r.v[c][j] = (half_t)((float)r.v[c][j] / dn.d);
+        }
+    }
+}
+
 // ---- shared tail: fp32 class sum -> z=r16(sum/cnt) -> fp16 / fp32 normalised prototype ----------
 // Executed by ONE wave; acc[c][j] holds this lane's slice of the class sum.
 template <int NCH>

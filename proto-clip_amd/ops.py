@@ -279,6 +279,82 @@ def cosine_logits(a, b, scale: float, normalize_a: bool = False, normalize_b: bo
     return logits, am, tv, ti
 
 
+def _cosine_ce_args(what, a, b, labels, symmetric, normalize_a, normalize_b):
+    """The operands of the two cosine cross-entropy calls as the kernels take them: (a, b, lda, ldb, M, T, D, labels, flags)."""
+    require_cuda(a, b, labels)
+    a, b = _f16_rows(a, f"{what}: a"), _f16_rows(b, f"{what}: b")
+    (M, D), (T, Db) = a.shape, b.shape
+    if D != Db:
+        raise _lib.PclipError(f"{what}: a has {D} columns, b has {Db}")
+    if M < 1 or T < 1:
+        raise _lib.PclipError(f"{what}: empty operand (M={M}, T={T})")
+    flags = (_lib.CE_NORMALIZE_A if normalize_a else 0) | (_lib.CE_NORMALIZE_B if normalize_b else 0)
+    if symmetric:
+        if labels is not None:
+            raise _lib.PclipError(f"{what}: symmetric mode takes no labels (the targets are the diagonal)")
+        flags |= _lib.CE_SYMMETRIC
+    else:
+        if labels is None or labels.dtype not in (torch.int32, torch.int64) or labels.dim() != 1 or labels.shape[0] != M:
+            raise _lib.PclipError(f"{what}: labels must be an int32 / int64 tensor of {M} entries (or symmetric=True)")
+        labels = labels.contiguous()
+        flags |= _lib.CE_LABELS_I64 if labels.dtype == torch.int64 else 0
+    return a, b, (a.stride(0) if M > 1 else D), (b.stride(0) if T > 1 else D), M, T, D, labels, flags
+
+
+def cosine_cross_entropy(a, b, scale: float, labels=None, symmetric: bool = False, normalize_a: bool = False, normalize_b: bool = False, want_rows: bool = False):
+    """Cross-entropy over s = scale * a' @ b'^T without the [M, T] matrix (the logits of clip/model.py:356-370, for training): a [M, D], b [T, D] fp16,
+    a' / b' the rows or their `l2norm_rows`; s stays fp32 — nothing is rounded to fp16 as the inference kernel `cosine_logits` does.
+    labels [M] int32 / int64: loss = mean_m (lse_t s[m, :] - s[m, y_m]); a label outside [0, T) is never used as an index: its row's term is the lse alone.
+    symmetric (M == T, no labels): CLIP's loss, 1/2 (mean of the row terms + mean of the column terms), targets on the diagonal.
+    Returns (loss 0-dim fp32, lse_row [M] fp32, lse_col [T] fp32 | None), and the per-row loss terms [M] as a fourth value with `want_rows`."""
+    a, b, lda, ldb, M, T, D, labels, flags = _cosine_ce_args("cosine_cross_entropy", a, b, labels, symmetric, normalize_a, normalize_b)
+    dev = a.device
+    lse_row = torch.empty(M, dtype=torch.float32, device=dev)
+    lse_col = torch.empty(T, dtype=torch.float32, device=dev) if symmetric else None
+    rows = torch.empty(M, dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    nws = _lib.workspace_bytes(_lib.OP_COSINE_CE, M, T, D)
+    ws = _workspace(nws, dev)
+    check(_lib.load().pclip_cosine_ce_f16(ptr(a), lda, M, ptr(b), ldb, T, D, float(np.float32(scale)), flags, ptr(labels), ptr(lse_row), ptr(lse_col),
+                                          ptr(rows), ptr(loss), ptr(ws), nws, stream()), "pclip_cosine_ce_f16")
+    return (loss, lse_row, lse_col, rows) if want_rows else (loss, lse_row, lse_col)
+
+
+def cosine_cross_entropy_backward(a, b, scale: float, lse_row, lse_col=None, labels=None, symmetric: bool = False, normalize_a: bool = False,
+                                  normalize_b: bool = False, want_a: bool = True, want_b: bool = True, want_scale: bool = True, grad: float = 1.0,
+                                  mean_over: int = None):
+    """The gradients of `cosine_cross_entropy` from its lse vectors: (dL/da [M, D] fp32 | None, dL/db [T, D] fp32 | None, dL/dscale 0-dim fp32 | None).
+    Logit tiles are recomputed and fed to a second matrix product; the exp tile is rounded to fp16 on the way, the weights and the scale act in fp32.
+    With normalize_a / normalize_b the gradient is chained in fp32 through the normalisation (the fp16 rounding of the normalised rows taken as the identity).
+    grad: the upstream gradient as a number; mean_over: the row count the loss was averaged over when the rows are a slice of a larger batch (default M) —
+    in labelled mode a row of dL/da has the same bits in any batch with the same `grad / mean_over`."""
+    a, b, lda, ldb, M, T, D, labels, flags = _cosine_ce_args("cosine_cross_entropy_backward", a, b, labels, symmetric, normalize_a, normalize_b)
+    require_cuda(lse_row, lse_col)
+    for name, t, n in (("lse_row", lse_row, M), ("lse_col", lse_col, T)):
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != n or not t.is_contiguous()):
+            raise _lib.PclipError(f"cosine_cross_entropy_backward: {name} must be a contiguous float32 tensor of {n} entries")
+    if lse_row is None or (lse_col is None) == bool(symmetric):
+        raise _lib.PclipError("cosine_cross_entropy_backward: lse_row is required, lse_col goes with symmetric mode and only with it")
+    dev = a.device
+    weight = float(grad) / ((mean_over or M) * (2 if symmetric else 1))
+    nws = _lib.workspace_bytes(_lib.OP_COSINE_CE_BACKWARD, M, T, D)
+    ws = _workspace(nws, dev)
+    ds = torch.empty((), dtype=torch.float32, device=dev) if want_scale else None
+    walks = [(0, M, want_a or (want_scale and not want_b)), (1, T, want_b)]          # (dscale is a by-product of a gradient walk: of dL/da's if no other runs)
+    grads, ds_left = [], ds
+    for direction, rows, run in walks:
+        if not run:
+            grads.append(None)
+            continue
+        g = torch.empty(rows, D, dtype=torch.float32, device=dev)
+        check(_lib.load().pclip_cosine_ce_backward_f16(ptr(a), lda, M, ptr(b), ldb, T, D, float(np.float32(scale)), flags, ptr(labels), ptr(lse_row), ptr(lse_col),
+                                                       float(np.float32(weight)), direction, ptr(g), ptr(ds_left), ptr(ws), nws, stream()),
+              "pclip_cosine_ce_backward_f16")
+        ds_left = None
+        grads.append(g)
+    return (grads[0] if want_a else None), grads[1], ds
+
+
 CLASSIFY_ROUTES = ("two stages", "one launch, small N", "one launch, mid N", "fused row panels")
 
 

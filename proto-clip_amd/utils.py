@@ -103,9 +103,10 @@ def cls_acc(output, target, topk=1):
     return 100 * acc / target.shape[0]
 
 
-def _clip_weight_rows(features, clip_weights, layout=None):
+def _clip_weight_rows(features, clip_weights, layout=None, taped=False):
     """The [N, D] prompt rows of a zero-shot classifier.  layout "dn": `clip_classifier`'s [D, N] (the reference's `features @ clip_weights` layout, one
-    transpose here); "nd": [N, D] rows, taken as they are; None: told from the shape, a square [D, D] tensor read as the reference's [D, N]."""
+    transpose here); "nd": [N, D] rows, taken as they are; None: told from the shape, a square [D, D] tensor read as the reference's [D, N].
+    taped: the transpose is torch's view, which autograd follows (the training losses), not the kernel's copy."""
     _as_f16_rows(features, "features")
     _as_f16_rows(clip_weights, "clip_weights")
     if layout not in (None, "dn", "nd"):
@@ -119,7 +120,9 @@ def _clip_weight_rows(features, clip_weights, layout=None):
         layout = "dn" if clip_weights.shape[0] == D else "nd"
     if clip_weights.shape[0 if layout == "dn" else 1] != D:
         raise PclipError(f"clip_weights {tuple(clip_weights.shape)} is not {'[D, N]' if layout == 'dn' else '[N, D]'} with D={D}")
-    return ops.transpose(clip_weights) if layout == "dn" else clip_weights
+    if layout == "dn":
+        return clip_weights.t() if taped else ops.transpose(clip_weights)
+    return clip_weights
 
 
 def clip_logits(features, clip_weights, scale=100., layout=None):
@@ -134,6 +137,21 @@ def clip_zero_shot(features, clip_weights, scale=100., topk=0, layout=None):
     `.topk(topk)` -> (argmax, values [Q, k] fp16, indices [Q, k] int64)."""
     _, am, tv, ti = ops.cosine_logits(features, _clip_weight_rows(features, clip_weights, layout), scale, want_logits=False, want_argmax=True, topk=topk)
     return (am.long(), tv, ti.long()) if topk else am.long()
+
+
+def clip_logits_loss(features, clip_weights, labels, scale=100., layout=None):
+    """Cross-entropy of the zero-shot logits `scale * features @ clip_weights` against `labels`, with gradients for the features, the weights and a tensor
+    `scale` (a text-initialised classifier or an adapter trained on cached features: the linear-probe / CLIP-Adapter baseline).  The operands are taken as
+    they are (cached features and `clip_classifier` weights are normalised already); `layout` as in `clip_logits`.  The [Q, N] logits are never written and,
+    unlike `clip_logits`, nothing is rounded to fp16 on the way to the loss.  Under torch.no_grad() the loss comes back without a tape."""
+    return pag.cosine_cross_entropy(features, _clip_weight_rows(features, clip_weights, layout, taped=True), scale, labels=labels)
+
+
+def clip_contrastive_loss(image_features, text_features, logit_scale):
+    """CLIP's symmetric contrastive loss on a batch of matching image / text features [n, D]: both sides L2-normalised, targets on the diagonal,
+    1/2 (image -> text + text -> image) cross-entropy over `logit_scale * i' @ t'^T`.  logit_scale is the ALREADY exponentiated scale, a float or a 0-dim
+    tensor (which then receives a gradient).  No [n, n] tensor is written, forward or backward."""
+    return pag.cosine_cross_entropy(image_features, text_features, logit_scale, symmetric=True, normalize_a=True, normalize_b=True)
 
 
 def get_target_inds(info):
