@@ -516,6 +516,33 @@ int pclip_adapter_conv_w_backward_f16(const void* x, const void* g, int B, int D
                                       const void* conv3, const void* ln3w, float* pw1, float* pw2, float* pw3, float* pg1, float* pb1,
                                       float* pg2, float* pb2, float* pg3, float* pb3, pclip_stream_t stream);
 
+/* ---- backward through the transformer towers (autograd of clip/model.py:171-190; fine-tuning a tail of either tower) ---------- */
+
+/* Gradient of pclip_attention_f16 (nn.MultiheadAttention's core inside ResidualAttentionBlock.attention, clip/model.py:183-185): qkv
+ * [B, L, 3*H*64] and dqkv in that layout, dout [B, L, H*64], all fp16.  S and P are recomputed from qkv (the forward saves nothing):
+ * dV = P^T dO, dP = dO V^T, dS = P o (dP - rowsum(dO o O)), dQ = dS K / 8, dK = dS^T Q / 8.  Products on MFMA with fp32 accumulation, softmax
+ * statistics, dP and the rowsum term in fp32, P and dS rounded to fp16 as they enter their products, every output rounded once (the rounding
+ * points are listed in csrc/pclip_attention_bwd.hip).  One workgroup per (sequence, head), no atomics: two calls give the same bits.
+ * dh must be 64 and 1 <= L <= 288; dqkv must not alias an input; operands 16-byte aligned. */
+int pclip_attention_backward_f16(const void* qkv, const void* dout, void* dqkv, int B, int L, int H, int dh, int causal,
+                                 pclip_stream_t stream);
+
+/* QuickGELU backward (clip/model.py:164-166, `x * torch.sigmoid(1.702 * x)`): du = r16(dy * s (1 + t (1 - s))), t = 1.702 u,
+ * s = sigmoid(t), in fp32 from the fp16 pre-activation u and the fp16 dy; n elements, 16-byte aligned. */
+int pclip_quick_gelu_backward_f16(const void* u, const void* dy, void* du, size_t n, pclip_stream_t stream);
+
+/* Column sums of an fp16 matrix x [R, C] (row stride ldx) in fp32 — the bias gradients of the linears (clip/model.py:176-181: c_fc, c_proj,
+ * in_proj, out_proj).  part [nslice][C]: slice i holds the sum of rows [i * ceil(R / nslice), ...) added in row order; reduce with
+ * pclip_colsum_f32.  Fixed order: deterministic. */
+int pclip_colsum_f16(const void* x, int ldx, int R, int C, float* part, int nslice, pclip_stream_t stream);
+
+/* Backward of CLIP's LayerNorm subclass (clip/model.py:155-161: fp32 computation on fp16 tensors, fp32 weight and bias): x, dy, dx fp16, gamma
+ * fp32, statistics fp32.  dx = r16(residual + dLN), `residual` (optional fp16, row stride ldr) being the gradient that reaches x on the residual
+ * stream past the LayerNorm (clip/model.py:188-189) — one rounding for the sum.  part [nblk][2][D] fp32: partial (dgamma | dbeta) sums as in
+ * pclip_layernorm_backward_f16. */
+int pclip_layernorm_backward_g32_f16(const void* x, int ldx, const float* gamma, const void* dy, int lddy, const void* residual, int ldr,
+                                     int R, int D, float eps, void* dx, int lddx, float* part, int nblk, pclip_stream_t stream);
+
 /* One torch.optim.AdamW step (main.py:134-135: eps 1e-4, weight_decay 0.05) on fp16 parameters with fp16 moments, every
  * intermediate rounded to fp16 where the single-tensor implementation materialises an fp16 tensor; step counts from 1. */
 int pclip_adamw_f16(void* p, const void* g, void* m, void* v, size_t n, double lr, double beta1, double beta2, double eps,

@@ -110,6 +110,10 @@ _SIGS = {
     "pclip_l2norm_rows_backward_f32": [_P, _P, _P, c_int, c_int, c_float, c_int, _P],
     "pclip_proto_backward_f16": [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P],
     "pclip_layernorm_backward_f16": [_P, c_int, _P, _P, c_int, c_int, c_int, c_float, c_float, _P, c_int, _P, c_int, _P],
+    "pclip_attention_backward_f16": [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P],
+    "pclip_quick_gelu_backward_f16": [_P, _P, _P, c_size_t, _P],
+    "pclip_colsum_f16": [_P, c_int, c_int, c_int, _P, c_int, _P],
+    "pclip_layernorm_backward_g32_f16": [_P, c_int, _P, _P, c_int, _P, c_int, c_int, c_int, c_float, _P, c_int, _P, c_int, _P],
     "pclip_adamw_f16": [_P, _P, _P, _P, c_size_t, c_double, c_double, c_double, c_double, c_double, c_int, _P],
     "pclip_preprocess_u8": [_P, _P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, _P, c_int, _P, _P],
     "pclip_workspace_bytes": [c_int, c_int, c_int, c_int],

@@ -212,3 +212,180 @@ def cosine_cross_entropy(a, b, scale, labels=None, symmetric=False, normalize_a=
 
 def wants_grad(*tensors) -> bool:
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+# ---- fine-tuning the transformer towers: a differentiable tail of residual blocks + final LayerNorm + projection ---------------------------------
+# (clip/model.py:171-190 per block, 233-236 / 348-352 for the heads.)  The taped forward issues the SAME kernel calls as clip.model._run_blocks'
+# batch path, so its features equal the untaped ones bit for bit, and keeps the tensors the backward reads (copies where the residual stream is
+# updated in place).  The backward is a sequence of library kernels: pclip_gemm_f16 for dX = dY W (W^T cached per weight version) and dW = dY^T X
+# (transposed operands, the token count padded to a multiple of 8 with zero rows), pclip_colsum_f16 for the bias gradients,
+# pclip_quick_gelu_backward_f16 on the recomputed c_fc pre-activation, pclip_layernorm_backward_g32_f16 (which also adds the gradient that passes
+# the LayerNorm on the residual stream: one rounding per add) and pclip_attention_backward_f16.  The activation-gradient stream is fp16; parameter
+# gradients arrive in the parameter's dtype.
+
+TOWER_MAX_L = 288      # the attention backward's envelope (the forward's resident-K/V kernels)
+
+def _block_params(blk):
+    """The 12 parameters of a residual block in the order TowerTailFn takes them."""
+    return [blk.ln_1.weight, blk.ln_1.bias, blk.attn.in_proj_weight, blk.attn.in_proj_bias, blk.attn.out_proj.weight, blk.attn.out_proj.bias,
+            blk.ln_2.weight, blk.ln_2.bias, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias, blk.mlp.c_proj.weight, blk.mlp.c_proj.bias]
+
+
+def _pad_rows8(t):
+    """Zero rows up to a multiple of 8: the contraction length of dW = dY^T X (pclip_gemm_f16 needs K % 8 == 0)."""
+    pad = (-t.shape[0]) % 8
+    return t if pad == 0 else torch.cat([t, t.new_zeros(pad, t.shape[1])], dim=0)
+
+
+def _weight_grad(dy, x):
+    """dW [N, K] = dY^T X for y = x W^T: pclip_gemm_f16 on the two transposed operands."""
+    return ops.gemm(ops.transpose(_pad_rows8(dy)), ops.transpose(_pad_rows8(x)))
+
+
+def _bias_grad(dy):
+    return ops.cast_f16(ops.colsum_f16(dy))
+
+
+class TowerTailFn(torch.autograd.Function):
+    """x [B*L, W] (the residual stream entering the first taped block; a constant) -> features [B, E] through `len(blocks)` residual blocks, the
+    row pick (class token / EOT row), the final LayerNorm and the projection.  Arguments after the bookkeeping: the 12 parameters of every taped
+    block (block order, each in _block_params' order), then ln.weight, ln.bias, proj."""
+
+    @staticmethod
+    def forward(ctx, x, h0, meta, *params):
+        B, L, heads, causal, select, sel_rows, first_token, cache = meta
+        nb = (len(params) - 3) // 12
+        W = x.shape[1]
+        ctx.meta, ctx.nb = meta, nb
+        tape = []
+        h = None
+        if nb > 0:
+            h = h0 if h0 is not None else ops.layernorm(x, params[0], params[1])
+        for i in range(nb):
+            ln1w, ln1b, win, bin_, wout, bout, ln2w, ln2b, wfc, bfc, wpr, bpr = params[12 * i:12 * i + 12]
+            last = i == nb - 1
+            rec = {"x_in": x.clone(), "h1": h, "picked": False}
+            if select is not None and last and first_token and not causal:
+                kv = ops.gemm(h, win[W:3 * W], bin_[W:3 * W])
+                q = ops.gemm(select(h), win[0:W], bin_[0:W])
+                a, x = ops.attention_first_queries(q, kv, B, L, 1, heads), select(x)
+                rec.update(q=q, kv=kv, picked=True)
+            else:
+                qkv = ops.gemm(h, win, bin_)
+                a = ops.attention(qkv, B, L, heads, causal=causal)
+                rec.update(qkv=qkv)
+                if select is not None and last:
+                    a, x = select(a), select(x)
+                    rec.update(picked=True)
+            ops.gemm(a, wout, bout, residual=x, out=x)
+            h = ops.layernorm(x, ln2w, ln2b)
+            rec.update(a=a, x_mid=x.clone(), h2=h)
+            f = ops.gemm(h, wfc, bfc, act=1)
+            rec.update(f=f)
+            ops.gemm(f, wpr, bpr, residual=x, out=x)
+            if not last:
+                h = ops.layernorm(x, params[12 * (i + 1)], params[12 * (i + 1) + 1])
+            tape.append(rec)
+        if select is not None and nb == 0:
+            x = select(x)
+        lnw, lnb, proj = params[-3:]
+        y = ops.layernorm(x, lnw, lnb)
+        projT = cache.get("tail_projT", proj, lambda t: t.t().contiguous())
+        ctx.tape, ctx.x_out, ctx.y = tape, x, y
+        ctx.save_for_backward(*params)
+        return ops.gemm(y, projT)
+
+    @staticmethod
+    def backward(ctx, g):
+        B, L, heads, causal, select, sel_rows, first_token, cache = ctx.meta
+        params = ctx.saved_tensors
+        nb = ctx.nb
+        grads = [None] * len(params)
+        lnw, lnb, proj = params[-3:]
+        g = g.contiguous()
+        if g.dtype != torch.float16:
+            g = ops.cast_f16(g.float())
+        # features = y proj: dproj = y^T g, dy = g proj^T
+        grads[-1] = ops.gemm(ops.transpose(_pad_rows8(ctx.y)), ops.transpose(_pad_rows8(g)))
+        dy = ops.gemm(g, proj)
+        gx, dg, db = ops.layernorm_backward_f32(ctx.x_out, lnw, dy)
+        grads[-3], grads[-2] = dg, db
+        W = ctx.x_out.shape[1]
+
+        def wT(key, w):
+            return cache.get(key, w, lambda t: t.t().contiguous())
+
+        for i in range(nb - 1, -1, -1):
+            ln1w, ln1b, win, bin_, wout, bout, ln2w, ln2b, wfc, bfc, wpr, bpr = params[12 * i:12 * i + 12]
+            rec = ctx.tape[i]
+            o = 12 * i
+            # x_out = x_mid + c_proj(f), f = QuickGELU(u), u = c_fc(h2), h2 = ln_2(x_mid)
+            grads[o + 10], grads[o + 11] = _weight_grad(gx, rec["f"]), _bias_grad(gx)
+            df = ops.gemm(gx, wT(("tail_wT", i, "pr"), wpr))
+            u = ops.gemm(rec["h2"], wfc, bfc)                                  # the pre-activation, recomputed (the forward's epilogue keeps only f)
+            du = ops.quick_gelu_backward(u, df)
+            del u, df
+            grads[o + 8], grads[o + 9] = _weight_grad(du, rec["h2"]), _bias_grad(du)
+            dh2 = ops.gemm(du, wT(("tail_wT", i, "fc"), wfc))
+            del du
+            gx, grads[o + 6], grads[o + 7] = ops.layernorm_backward_f32(rec["x_mid"], ln2w, dh2, residual=gx)
+            # x_mid = x_in + out_proj(a)
+            grads[o + 4], grads[o + 5] = _weight_grad(gx, rec["a"]), _bias_grad(gx)
+            da = ops.gemm(gx, wT(("tail_wT", i, "out"), wout))
+            if rec["picked"]:                                                  # only B rows left the block: zeros on the others
+                full = torch.zeros(B * L, W, dtype=torch.float16, device=gx.device)
+                full[sel_rows] = da
+                da = full
+                full = torch.zeros(B * L, W, dtype=torch.float16, device=gx.device)
+                full[sel_rows] = gx
+                gx = full
+            if "qkv" in rec:
+                qkv = rec["qkv"]
+            else:                                                              # class-token form: queries of the other rows are never read (their dO is zero)
+                qkv = torch.zeros(B * L, 3 * W, dtype=torch.float16, device=gx.device)
+                qkv[:, W:] = rec["kv"]
+                qkv[sel_rows, :W] = rec["q"]
+            dqkv = ops.attention_backward(qkv, da, B, L, heads, causal=causal)
+            del qkv, da
+            grads[o + 2], grads[o + 3] = _weight_grad(dqkv, rec["h1"]), _bias_grad(dqkv)
+            dh1 = ops.gemm(dqkv, wT(("tail_wT", i, "in"), win))
+            del dqkv
+            gx, grads[o + 0], grads[o + 1] = ops.layernorm_backward_f32(rec["x_in"], ln1w, dh1, residual=gx)
+        out = []
+        for p, gr, need in zip(params, grads, ctx.needs_input_grad[3:]):
+            out.append(gr.reshape(p.shape) if need else None)
+        return (None, None, None) + tuple(out)
+
+
+def tower_plan(tower_name, blocks, prefix_params, head_params):
+    """Index of the first block that owns a trainable parameter (len(blocks) when only the heads train), or None when nothing of the tower trains.
+    Raises for a trainable parameter in the frozen prefix (`prefix_params`: (name, parameter) pairs of the stem / embeddings)."""
+    first = None
+    for i, blk in enumerate(blocks):
+        if any(p.requires_grad for p in blk.parameters()):
+            first = i
+            break
+    heads = any(p.requires_grad for _, p in head_params)
+    for name, p in prefix_params:
+        if p.requires_grad:
+            raise PclipError(f"{tower_name}: parameter {name} requires grad but lies in the frozen prefix of the tower (only a tail of residual "
+                             "blocks, the final LayerNorm and the projection are differentiable)")
+    if first is None:
+        return len(blocks) if heads else None
+    return first
+
+
+def run_tower_tail(x, h0, blocks, first, B, L, heads, causal, select, sel_rows, first_token, ln, proj, cache, what):
+    """The taped tail: blocks[first:] + ln + proj on the residual stream x [B*L, W] (h0: ln_1 of blocks[first] when the caller already has it)."""
+    if ops.splitk_active(B) or ops.splitk_active(B * L):
+        raise PclipError(f"{what}: a differentiable pass inside ops.low_latency() is not supported (the split-K linears have no backward); "
+                         f"leave the context or freeze the tower (B={B}, L={L})")
+    if L > TOWER_MAX_L and first < len(blocks):
+        raise PclipError(f"{what}: sequences of L={L} tokens exceed the attention backward's envelope (L <= {TOWER_MAX_L}); "
+                         "this tower can only run frozen")
+    params = [p for blk in blocks[first:] for p in _block_params(blk)] + [ln.weight, ln.bias, proj]
+    for p in params:
+        if p.requires_grad and p.dtype not in (torch.float16, torch.float32):
+            raise PclipError(f"{what}: unsupported parameter dtype {p.dtype}")
+    meta = (B, L, heads, causal, select, sel_rows, first_token, cache)
+    return TowerTailFn.apply(x, h0, meta, *params)

@@ -179,6 +179,15 @@ class VisionTransformer(nn.Module):
         outs = [self._forward_chunk(x[i:i + self.chunk]) for i in range(0, x.shape[0], self.chunk)]
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
 
+    def _tape_from(self):
+        """Index of the first residual block with a trainable parameter (layers: only ln_post / proj train), None when the tower is frozen."""
+        from ..autograd import tower_plan
+        prefix = [("visual.conv1.weight", self.conv1.weight), ("visual.class_embedding", self.class_embedding),
+                  ("visual.positional_embedding", self.positional_embedding), ("visual.ln_pre.weight", self.ln_pre.weight),
+                  ("visual.ln_pre.bias", self.ln_pre.bias)]
+        heads = [("visual.ln_post.weight", self.ln_post.weight), ("visual.ln_post.bias", self.ln_post.bias), ("visual.proj", self.proj)]
+        return tower_plan("visual tower", self.transformer.resblocks, prefix, heads)
+
     def _forward_chunk(self, img):
         B, P, W = img.shape[0], self.patch_size, self.width
         G = self.input_resolution // P
@@ -210,6 +219,18 @@ class VisionTransformer(nn.Module):
             x = ops.vit_assemble_tokens(patch, cls16, pos16, B, G * G, W)   # clip/model.py:225-226
             x = ops.layernorm(x, self.ln_pre.weight, self.ln_pre.bias)      # 227
         pick_cls = lambda t: t.view(B, L, W)[:, 0, :].contiguous()          # x[:, 0, :], 233 (taken before the last block's tail)
+        first = self._tape_from() if torch.is_grad_enabled() else None
+        if first is not None:                                               # fine-tuning: blocks[first:] + ln_post + proj on the tape
+            from ..autograd import run_tower_tail
+            what = f"encode_image (visual tower, blocks {first}..{len(blocks) - 1} + heads trainable)"
+            if first == len(blocks):                                        # only the heads train: the stack keeps its class-row shortcut
+                x, _ = _run_blocks(x, blocks, B, L, self.heads, causal=False, select=pick_cls, first_token=True, h0=h0)
+                return run_tower_tail(x, None, blocks, first, B, L, self.heads, False, None, None, False, self.ln_post, self.proj, self._cache, what)
+            if first > 0:
+                x, _ = _run_blocks(x, blocks[:first], B, L, self.heads, causal=False, h0=h0)
+                h0 = None
+            rows = torch.arange(B, device=x.device) * L
+            return run_tower_tail(x, h0, blocks, first, B, L, self.heads, False, pick_cls, rows, True, self.ln_post, self.proj, self._cache, what)
         x, d = _run_blocks(x, blocks, B, L, self.heads, causal=False, select=pick_cls, first_token=True, h0=h0)   # 229-231
         if d is None:                                                       # ln_post(x[:, 0, :]), 233
             cls = ops.layernorm(x, self.ln_post.weight, self.ln_post.bias)
@@ -410,17 +431,60 @@ class CLIP(nn.Module):
         return self.visual.conv1.weight.dtype
 
     def encode_image(self, image):
+        """[n, 3, R, R] -> [n, embed_dim] fp16 (clip/model.py:338-339).  A constant, unless grad mode is on and a parameter of the visual tower
+        requires grad (`unfreeze`): then the tail of the tower from the first trainable block on is recorded for autograd (autograd.TowerTailFn;
+        the same kernels, the same bits)."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.visual.parameters()):
+            if isinstance(self.visual, ModifiedResNet):
+                name = next(n for n, p in self.visual.named_parameters() if p.requires_grad)
+                raise PclipError(f"encode_image: parameter visual.{name} requires grad, but the ModifiedResNet tower has no backward "
+                                 "(only the transformer towers can be fine-tuned)")
+            return self.visual(image)
         with torch.no_grad():
             return self.visual(image)
 
     def encode_text(self, text):
         """text [n, context_length] int64 -> [n, embed_dim] fp16 (clip/model.py:341-354).  Unlike the
         reference's per-class calls (utils.py:264-266, n = #templates) any n is efficient here."""
-        with torch.no_grad():
-            outs = [self._encode_text_chunk(text[i:i + self.text_chunk]) for i in range(0, text.shape[0], self.text_chunk)]
+        first = self._text_tape_from() if torch.is_grad_enabled() else None
+        with torch.set_grad_enabled(first is not None):
+            outs = [self._encode_text_chunk(text[i:i + self.text_chunk], first) for i in range(0, text.shape[0], self.text_chunk)]
             return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
 
-    def _encode_text_chunk(self, text):
+    def _text_tape_from(self):
+        """As VisionTransformer._tape_from for the text tower (ln_final / text_projection are its heads)."""
+        from ..autograd import tower_plan
+        prefix = [("token_embedding.weight", self.token_embedding.weight), ("positional_embedding", self.positional_embedding)]
+        heads = [("ln_final.weight", self.ln_final.weight), ("ln_final.bias", self.ln_final.bias), ("text_projection", self.text_projection)]
+        return tower_plan("text tower", self.transformer.resblocks, prefix, heads)
+
+    def unfreeze(self, visual_blocks=0, text_blocks=0, heads=True):
+        """Make a tail of the transformer towers trainable: the last `visual_blocks` / `text_blocks` residual blocks and, with `heads`, ln_post / proj
+        and ln_final / text_projection.  Returns the list of those parameters, ready for an optimizer; encode_image / encode_text then record their
+        tail for autograd whenever grad mode is on.  (Everything before the first trainable block stays frozen: conv1, the embeddings, ln_pre.)"""
+        if isinstance(self.visual, ModifiedResNet):                         # no backward: the tower stays frozen, the text side may train
+            if visual_blocks:
+                raise PclipError(f"unfreeze: visual_blocks={visual_blocks}, but the ModifiedResNet tower has no backward (only transformer towers)")
+            vis = []
+        else:
+            nv = len(self.visual.transformer.resblocks)
+            if not 0 <= visual_blocks <= nv:
+                raise PclipError(f"unfreeze: visual_blocks={visual_blocks} outside 0..{nv}")
+            vis = [p for blk in list(self.visual.transformer.resblocks)[nv - visual_blocks:] for p in blk.parameters()]
+            if heads:
+                vis += [self.visual.ln_post.weight, self.visual.ln_post.bias, self.visual.proj]
+        nt = len(self.transformer.resblocks)
+        if not 0 <= text_blocks <= nt:
+            raise PclipError(f"unfreeze: text_blocks={text_blocks} outside 0..{nt}")
+        txt = [p for blk in list(self.transformer.resblocks)[nt - text_blocks:] for p in blk.parameters()]
+        if heads:
+            txt += [self.ln_final.weight, self.ln_final.bias, self.text_projection]
+        params = vis + txt
+        for p in params:
+            p.requires_grad_(True)
+        return params
+
+    def _encode_text_chunk(self, text, first=None):
         B, L = text.shape
         W = self.transformer.width
         emb16 = self._cache.get("tok", self.token_embedding.weight, lambda t: t.half().contiguous())
@@ -428,6 +492,23 @@ class CLIP(nn.Module):
         projT = self._cache.get("tprojT", self.text_projection, lambda t: t.t().contiguous())
         x = ops.text_embed(text, emb16, pos16)                                   # 342-344
         pick_eot = lambda t: ops.gather_eot(t, text, B, L, W)                    # x[arange, text.argmax(-1)], 350
+        if first is not None:                                                    # fine-tuning: blocks[first:] + ln_final + text_projection on the tape
+            from ..autograd import run_tower_tail
+            blocks = self.transformer.resblocks
+            what = f"encode_text (text tower, blocks {first}..{len(blocks) - 1} + heads trainable)"
+            with torch.no_grad():
+                if first == len(blocks):
+                    x, _ = _run_blocks(x, blocks, B, L, self.transformer_heads, causal=True, select=pick_eot)
+                elif first > 0:
+                    x, _ = _run_blocks(x, blocks[:first], B, L, self.transformer_heads, causal=True)
+            if first == len(blocks):
+                return run_tower_tail(x, None, blocks, first, B, L, self.transformer_heads, True, None, None, False, self.ln_final,
+                                      self.text_projection, self._cache, what)
+            pos = torch.arange(L, device=x.device).expand(B, L)                  # the FIRST maximum, gather_eot's tie rule
+            eot = torch.where(text == text.max(dim=-1, keepdim=True).values, pos, pos.new_full((), L)).min(dim=-1).values
+            rows = torch.arange(B, device=x.device) * L + eot
+            return run_tower_tail(x, None, blocks, first, B, L, self.transformer_heads, True, pick_eot, rows, False, self.ln_final,
+                                  self.text_projection, self._cache, what)
         x, d = _run_blocks(x, self.transformer.resblocks, B, L, self.transformer_heads, causal=True, select=pick_eot)   # 345-347
         if d is None:
             eot = ops.layernorm(x, self.ln_final.weight, self.ln_final.bias)     # 348 (row-wise: commutes with the gather)
@@ -450,8 +531,9 @@ class CLIP(nn.Module):
     def contrastive_loss(self, image_features, text_features):
         """CLIP's symmetric contrastive loss of matching image / text features (the outputs of encode_image / encode_text, or trained copies of them) under
         this model's temperature: `utils.clip_contrastive_loss` with logit_scale.exp() in fp32 — NOT the fp16-rounded value `forward` reproduces.
-        logit_scale is frozen by default; after `model.logit_scale.requires_grad_(True)` its gradient arrives through torch's own exp node.  The encoders
-        have no backward: features that come from them are constants."""
+        logit_scale is frozen by default; after `model.logit_scale.requires_grad_(True)` its gradient arrives through torch's own exp node.  Features of
+        a frozen model are constants; after `unfreeze` (or `requires_grad_` on a tail of a tower) encode_image / encode_text record that tail, and this
+        loss's feature gradients flow on through the blocks' backward kernels into the parameters' .grad."""
         from ..utils import clip_contrastive_loss
         return clip_contrastive_loss(image_features, text_features, self.logit_scale.float().exp())
 

@@ -1000,6 +1000,63 @@ def layernorm_backward(x, gamma, dy, eps: float = 1e-5, dy_scale: float = 1.0):
     return dx, sums[:D], sums[D:]
 
 
+def attention_backward(qkv, dout, B: int, L: int, H: int, causal: bool = False, dh: int = 64):
+    """Gradient of `attention` wrt the fused QKV buffer: qkv [B*L, 3W], dout [B*L, W] -> dqkv [B*L, 3W], fp16 (pclip_attention_backward_f16: S and P are
+    recomputed, deterministic).  L <= 288 and head dim 64, like the forward's resident kernels."""
+    require_cuda(qkv, dout)
+    qkv, dout = _f16c(qkv), _f16c(dout)
+    W = H * dh
+    if qkv.numel() != B * L * 3 * W or dout.numel() != B * L * W:
+        raise _lib.PclipError(f"attention_backward: qkv {tuple(qkv.shape)} / dout {tuple(dout.shape)} do not match B={B} L={L} H={H} dh={dh}")
+    dqkv = torch.empty_like(qkv)
+    check(_lib.load().pclip_attention_backward_f16(ptr(qkv), ptr(dout), ptr(dqkv), B, L, H, dh, int(causal), stream()),
+          "pclip_attention_backward_f16")
+    return dqkv
+
+
+def quick_gelu_backward(u, dy):
+    """du = r16(dy * QuickGELU'(u)) on the fp16 pre-activation u (clip/model.py:164-166), derivative in fp32."""
+    require_cuda(u, dy)
+    u, dy = _f16c(u), _f16c(dy)
+    if u.shape != dy.shape:
+        raise _lib.PclipError(f"quick_gelu_backward: shapes differ ({tuple(u.shape)} vs {tuple(dy.shape)})")
+    du = torch.empty_like(u)
+    check(_lib.load().pclip_quick_gelu_backward_f16(ptr(u), ptr(dy), ptr(du), u.numel(), stream()), "pclip_quick_gelu_backward_f16")
+    return du
+
+
+def colsum_f16(x: torch.Tensor) -> torch.Tensor:
+    """x.sum(0) of a 2-D fp16 matrix in fp32 (the bias gradient of a linear), in a fixed summation order."""
+    require_cuda(x)
+    x = _f16c(x)
+    R, C = x.shape
+    if R == 0:
+        return torch.zeros(C, dtype=torch.float32, device=x.device)
+    nslice = max(1, min(128, (R + 31) // 32))
+    part = torch.empty(nslice, C, dtype=torch.float32, device=x.device)
+    check(_lib.load().pclip_colsum_f16(ptr(x), x.stride(0), R, C, ptr(part), nslice, stream()), "pclip_colsum_f16")
+    return colsum_f32(part)
+
+
+def layernorm_backward_f32(x, gamma, dy, eps: float = 1e-5, residual=None):
+    """Backward of `layernorm` (fp16 x / dy, fp32 gamma, fp32 statistics): (dx fp16, dgamma fp32 [D], dbeta fp32 [D]); with `residual` (fp16, the
+    gradient that passes the LayerNorm on the residual stream) dx = r16(residual + dLN)."""
+    require_cuda(x, gamma, dy, residual)
+    x, dy = _f16c(x), _f16c(dy)
+    if gamma.dtype != torch.float32:
+        raise _lib.PclipError(f"layernorm_backward_f32: fp32 gamma expected, got {gamma.dtype}")
+    gamma = gamma.contiguous()
+    residual = None if residual is None else _f16c(residual)
+    R, D = x.shape
+    nblk = max(1, min(256, (R + 3) // 4))
+    dx = torch.empty_like(x)
+    part = torch.empty(nblk, 2, D, dtype=torch.float32, device=x.device)
+    check(_lib.load().pclip_layernorm_backward_g32_f16(ptr(x), D, ptr(gamma), ptr(dy), D, ptr(residual), D, R, D, eps, ptr(dx), D, ptr(part),
+                                                       nblk, stream()), "pclip_layernorm_backward_g32_f16")
+    sums = colsum_f32(part.view(nblk, 2 * D))
+    return dx, sums[:D], sums[D:]
+
+
 def adamw_(p, g, m, v, lr: float, step: int, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-4,
            weight_decay: float = 0.05):
     """In-place torch.optim.AdamW step on an fp16 parameter with fp16 moments (main.py:134-135)."""
