@@ -96,6 +96,21 @@ __device__ __forceinline__ float half_wave_sum(float v) { float a, b; half_wave_
 // pointing at key row k0 (a multiple of 64), L and NT counted from k0 — runs, tile for tile, the instructions the whole walk runs on
 // those keys (the masks only compare against L - 32 t): the streamed kernel (pclip_attention_long.hip) walks one LDS stage at a time
 // and gets the bits of the resident kernels.
+//
+// ROUNDING POINTS (tests/attention_fwd_ref.py derives the per-element tolerance of the forward attention from exactly these; u11 = 2^-11 an fp16
+// rounding, u24 = 2^-24 an fp32 rounding, 2^-25 the absolute error of an fp16 rounding in the subnormal range; S = q k^T / 8, P = softmax(S)):
+//   1. S^T = K Q^T: fp16 operands, 64 exact products accumulated in fp32 by four MFMAs                       64 u24 |q| |k|^T / 8
+//   2. kScale = log2(e) / 8 is a rounded fp32 constant; s kScale - mnew is ONE fma (VAR & 4: v_pk_fma_f32)      2 u24 |S|, and u24 of the result
+//   3. p = v_exp_f32(.) against the RUNNING maximum mnew, which under VAR & 1 is up to kAttDefer stale: p reaches 2^kAttDefer, exact in fp32
+//   4. the row sum: a lane's 16 / 32 probabilities of the pair one after the other (VAR & 2: two interleaved chains), the half-waves added, lrun += psum;
+//      with 5. and 7. inside (L + 16) u24 relative
+//   5. a rescale: alpha = v_exp_f32(mrun - mnew) — the exponents are fp32 differences that telescope over a row (the maximum only rises) — times lrun
+//      and times every o: the SAME alpha on both sides of the final quotient
+//   6. p -> fp16 as the B operand of O^T = V^T P^T: relative u11, absolute 2^-25 in the subnormal range — at the unnormalised scale, where it stays:
+//      the pair that last set the maximum added exp2(0) = 1 to lrun and every later alpha is <= 1, so lrun >= 1 at the end.  Masked keys: exp2(-inf) = 0.
+//      O^T accumulates in fp32 over the L keys                                                                  L u24 P |V|
+//   7. attn_store_tile: inv = 1.f / lrun, o * inv in fp32, then the ONE fp16 rounding of the output             u11 |O| + 2^-25
+// Which maximum a probability was taken against and when the state was rescaled is exact algebra on the softmax: it adds no term.
 template <bool DEEP = false, int VAR = 0, bool VBAR = false>
 __device__ __forceinline__ void attn_key_tiles(const half_t* Ks, const half_t* Vs, const half8_t (&qf)[4], int q, int qb, int L, int causal,
                                                int NT, int hi, int ql, const int (&voff)[2], float16_t (&o)[2],
