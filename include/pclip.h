@@ -548,6 +548,47 @@ int pclip_layernorm_backward_g32_f16(const void* x, int ldx, const float* gamma,
 int pclip_adamw_f16(void* p, const void* g, void* m, void* v, size_t n, double lr, double beta1, double beta2, double eps,
                     double weight_decay, int step, pclip_stream_t stream);
 
+/* ---- mixed-precision AdamW for the tower parameters (proto_clip_amd/optim.py: TowerAdamW; csrc/pclip_tower_optim.hip lists every rounding) ---- */
+/* fp32 master weights and moments, gradient unscaling with overflow detection, clipping by the global norm and a GradScaler-style dynamic loss
+ * scale in three launches for any number of tensors: no host synchronisation, no atomics (deterministic), capturable in a hipGraph.
+ *
+ * table: ntensors rows of PCLIP_TOWER_ROW_BYTES, eight 64-bit words each:
+ *   0 parameter pointer (fp16 or fp32)      1 gradient pointer (fp16 or fp32; NULL = a zero gradient)
+ *   2 master weights (fp32; an fp32 parameter is its own master: word 2 == word 0)      3 m (fp32)      4 v (fp32)
+ *   5 element count (>= 1)                  6 index of the tensor's first chunk (prefix sum of ceil(n / PCLIP_TOWER_CHUNK), row 0: 0)
+ *   7 PCLIP_TOWER_* flags
+ * nchunks: the chunks of all tensors.  PCLIP_TOWER_ALIGNED promises that words 0 .. 4 are all 16-byte aligned (16-byte loads and stores);
+ * without it every access is a single element.  Both give the same bits.
+ * state: PCLIP_TOWER_STATE_BYTES, 8-byte aligned:
+ *   +0 double b1^t   +8 double b2^t   (running products, 1.0 before the first step, one multiplication per taken step)
+ *   +16 double total (sum of squares of the scaled gradients, this step)
+ *   +24 float loss scale   +28 int growth tracker   +32 int steps taken   +36 int found_inf (this step)
+ *   +40 float grad_norm (unscaled)   +44 float clip_coef   +48 float inv_scale_used   +52 float bc1   +56 float sqrt(bc2)
+ *   +60 float clip_coef * inv_scale_used */
+#define PCLIP_TOWER_CHUNK 4096
+#define PCLIP_TOWER_ROW_BYTES 64
+#define PCLIP_TOWER_STATE_BYTES 64
+#define PCLIP_TOWER_PARAM_F16 0x1 /* parameter is fp16 (else fp32) */
+#define PCLIP_TOWER_GRAD_F16 0x2  /* gradient is fp16 (else fp32) */
+#define PCLIP_TOWER_ALIGNED 0x4
+#define PCLIP_TOWER_DECAY 0x8     /* weight decay applies */
+
+/* Launch 1: partials [nchunks] = fp32 sum of squares of each chunk's raw (scaled) gradients in a fixed order; an Inf / NaN gradient makes its
+ * partial non-finite. */
+int pclip_tower_grad_sumsq(const void* table, int ntensors, int nchunks, float* partials, pclip_stream_t stream);
+
+/* Launch 2 (one workgroup): adds the partials in chunk order in double; writes found_inf, grad_norm = sqrt(total) / scale, clip_coef =
+ * min(1, max_norm / (grad_norm + 1e-6)) (1 when max_norm <= 0), inv_scale_used, bc1, sqrt(bc2); advances the step count and b^t on a clean step only;
+ * with `dynamic` applies torch.amp.GradScaler's rule (overflow: scale *= backoff, tracker = 0; else tracker += 1 and at growth_interval
+ * scale *= growth, tracker = 0). */
+int pclip_tower_optim_finish(const float* partials, int nchunks, void* state, float max_norm, double beta1, double beta2, float growth,
+                             float backoff, int growth_interval, int dynamic, pclip_stream_t stream);
+
+/* Launch 3: the AdamW update in fp32 from the state block's outputs (nothing when found_inf); hyper [ntensors][2] = {lr, weight_decay} per
+ * tensor.  Stores master, m, v and the parameter (half(master) for an fp16 parameter). */
+int pclip_tower_adamw(const void* table, const float* hyper, int ntensors, int nchunks, const void* state, double beta1, double beta2,
+                      double eps, pclip_stream_t stream);
+
 /* ---- image pre-processing (clip/clip.py:77-84 `_transform`; datasets/imagenet.py:8-23 `get_random_train_tfm`) ------------- */
 
 /* A batch of decoded RGB images (uint8, HWC, device memory; srcs = device array of B pointers) -> normalised CHW tensors

@@ -16,6 +16,9 @@ CE_NORMALIZE_A, CE_NORMALIZE_B, CE_SYMMETRIC, CE_LABELS_I64 = 0x1, 0x2, 0x4, 0x8
 # routing flags of pclip_classify_ex_f16 / pclip_classify_route_ex (include/pclip.h)
 CLASSIFY_NO_SMALL, CLASSIFY_NO_MID, CLASSIFY_FORCE_MID, CLASSIFY_NO_PANELS, CLASSIFY_FORCE_PANELS = 0x1, 0x2, 0x4, 0x8, 0x10
 CLASSIFY_PANEL_TWO_PASS, CLASSIFY_PANEL_FORCE_SECOND, CLASSIFY_PANEL_EXACT = 0x20, 0x40, 0x80
+# pclip_tower_grad_sumsq / pclip_tower_optim_finish / pclip_tower_adamw: chunk length, table row / state block sizes, row flags
+TOWER_CHUNK, TOWER_ROW_BYTES, TOWER_STATE_BYTES = 4096, 64, 64
+TOWER_PARAM_F16, TOWER_GRAD_F16, TOWER_ALIGNED, TOWER_DECAY = 0x1, 0x2, 0x4, 0x8
 
 
 class PclipError(RuntimeError):
@@ -115,6 +118,9 @@ _SIGS = {
     "pclip_colsum_f16": [_P, c_int, c_int, c_int, _P, c_int, _P],
     "pclip_layernorm_backward_g32_f16": [_P, c_int, _P, _P, c_int, _P, c_int, c_int, c_int, c_float, _P, c_int, _P, c_int, _P],
     "pclip_adamw_f16": [_P, _P, _P, _P, c_size_t, c_double, c_double, c_double, c_double, c_double, c_int, _P],
+    "pclip_tower_grad_sumsq": [_P, c_int, c_int, _P, _P],
+    "pclip_tower_optim_finish": [_P, c_int, _P, c_float, c_double, c_double, c_float, c_float, c_int, c_int, _P],
+    "pclip_tower_adamw": [_P, _P, c_int, c_int, _P, c_double, c_double, c_double, _P],
     "pclip_preprocess_u8": [_P, _P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, _P, c_int, _P, _P],
     "pclip_workspace_bytes": [c_int, c_int, c_int, c_int],
 }

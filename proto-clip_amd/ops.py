@@ -1069,6 +1069,40 @@ def adamw_(p, g, m, v, lr: float, step: int, beta1: float = 0.9, beta2: float = 
     return p
 
 
+def _tower_tables(what, table, ntensors, nchunks, state=None, partials=None, hyper=None):
+    require_cuda(table, state, partials, hyper)
+    if table is not None and (table.dtype != torch.int64 or not table.is_contiguous() or table.numel() < 8 * ntensors):
+        raise _lib.PclipError(f"{what}: table must be a contiguous int64 tensor of {ntensors} rows of 8 words")
+    if state is not None and (state.dtype != torch.uint8 or not state.is_contiguous() or state.numel() < _lib.TOWER_STATE_BYTES or state.data_ptr() % 8):
+        raise _lib.PclipError(f"{what}: state must be a contiguous, 8-byte aligned uint8 tensor of {_lib.TOWER_STATE_BYTES} bytes")
+    if partials is not None and (partials.dtype != torch.float32 or not partials.is_contiguous() or partials.numel() < nchunks):
+        raise _lib.PclipError(f"{what}: partials must be a contiguous fp32 tensor of at least {nchunks} elements")
+    if hyper is not None and (hyper.dtype != torch.float32 or not hyper.is_contiguous() or hyper.numel() < 2 * ntensors):
+        raise _lib.PclipError(f"{what}: hyper must be a contiguous fp32 tensor of {ntensors} (lr, weight_decay) pairs")
+
+
+def tower_grad_sumsq(table, ntensors: int, nchunks: int, partials):
+    """Launch 1 of the tower optimizer (optim.TowerAdamW): per-chunk fp32 sums of squares of the raw gradients the table points at."""
+    _tower_tables("tower_grad_sumsq", table, ntensors, nchunks, partials=partials)
+    check(_lib.load().pclip_tower_grad_sumsq(ptr(table), ntensors, nchunks, ptr(partials), stream()), "pclip_tower_grad_sumsq")
+    return partials
+
+
+def tower_optim_finish(partials, nchunks: int, state, max_norm: float, beta1: float, beta2: float, growth: float = 2.0, backoff: float = 0.5,
+                       growth_interval: int = 2000, dynamic: bool = True):
+    """Launch 2: overflow flag, unscaled gradient norm, clip coefficient, bias corrections and the loss-scale update, into the state block."""
+    _tower_tables("tower_optim_finish", None, 0, nchunks, state=state, partials=partials)
+    check(_lib.load().pclip_tower_optim_finish(ptr(partials), nchunks, ptr(state), max_norm, beta1, beta2, growth, backoff, growth_interval,
+                                               int(dynamic), stream()), "pclip_tower_optim_finish")
+    return state
+
+
+def tower_adamw_(table, hyper, ntensors: int, nchunks: int, state, beta1: float, beta2: float, eps: float):
+    """Launch 3: the fp32 AdamW update of every tensor in the table, in place (nothing when the state block reports an overflow)."""
+    _tower_tables("tower_adamw_", table, ntensors, nchunks, state=state, hyper=hyper)
+    check(_lib.load().pclip_tower_adamw(ptr(table), ptr(hyper), ntensors, nchunks, ptr(state), beta1, beta2, eps, stream()), "pclip_tower_adamw")
+
+
 def l2norm_rows_f32(x: torch.Tensor, eps: float = 1e-12) -> torch.Tensor:
     """F.normalize(x, dim=-1) on fp32 rows."""
     require_cuda(x)
