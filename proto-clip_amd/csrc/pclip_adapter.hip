@@ -1234,7 +1234,7 @@ __global__ __launch_bounds__(256, 1) void adapter_conv3x_bwd_mfma_kernel(
 }  // namespace
 
 static bool adapter_mfma_enabled() {
-    static const bool on = !(getenv("PCLIP_ADAPTER_MFMA") && getenv("PCLIP_ADAPTER_MFMA")[0] == '0');     // A/B switch: 0 = the VALU kernels
+    static const bool on = pclip_env_on("PCLIP_ADAPTER_MFMA");     // A/B switch: 0 = the VALU kernels
     return on;
 }
 static int adapter_bwd_workgroups(int B, int D, int three_x) {
@@ -1243,8 +1243,7 @@ static int adapter_bwd_workgroups(int B, int D, int three_x) {
     while (s * s < D) ++s;
     const int NT = (s * s + 63) / 64;
     if (!three_x || NT > TWO_WG_MAX || !adapter_mfma_enabled()) return B;
-    int cus = pclip_device_cus();
-    if (cus <= 0) cus = 256;
+    const int cus = pclip_cus();
     return B < cus ? B : cus;
 }
 extern "C" int pclip_adapter_conv_backward_partials(int B, int D, int three_x) { return adapter_bwd_workgroups(B, D, three_x); }
@@ -1264,23 +1263,17 @@ extern "C" int pclip_adapter_conv_backward_f16(const void* x, const void* g, int
     const int s2 = s * s, hp = (s + 2) * (s + 2);
     const size_t lds = (size_t)(1024 + 1024 + 4 + 64) * 4 + (three_x ? (size_t)2 * 8 * hp * 4 + (size_t)CW * s2 * 2 + (size_t)2 * 8 * 9 * CW * 4 : 0);
     hipStream_t st = (hipStream_t)stream;
-    static DevOnce attr[2];
+    static DevOnce attr;
     const int R = adapter_bwd_workgroups(B, D, three_x);
     if (three_x && (s2 + 63) / 64 <= TWO_WG_MAX && adapter_mfma_enabled()) {                 // persistent MFMA kernel: R partial rows
         const int NT = (s2 + 63) / 64, NPX = (NT + 3) / 4, HK = (hp + 31) & ~31, PADP = s + 3;
         const size_t lds_m = (size_t)(2 * HK + 2 * PADP) * 32 + (size_t)256 * NPX * 6 + 128 * 4 + (size_t)2 * CW * s2 * 4;
         static DevOnce attr_m;
-        const void* fns[] = {(const void*)adapter_conv3x_bwd_mfma_kernel<1>, (const void*)adapter_conv3x_bwd_mfma_kernel<2>, (const void*)adapter_conv3x_bwd_mfma_kernel<3>,
-                             (const void*)adapter_conv3x_bwd_mfma_kernel<4>, (const void*)adapter_conv3x_bwd_mfma_kernel<5>, (const void*)adapter_conv3x_bwd_mfma_kernel<6>,
-                             (const void*)adapter_conv3x_bwd_mfma_kernel<7>, (const void*)adapter_conv3x_bwd_mfma_kernel<8>, (const void*)adapter_conv3x_bwd_mfma_kernel<9>};
-        if (!attr_m.done()) {
-            for (const void* f : fns)
-                if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-                    pclip_set_error("pclip_adapter_conv_backward_f16: cannot raise the dynamic LDS limit");
-                    return PCLIP_E_LAUNCH;
-                }
-            attr_m.set();
-        }
+        if (int e = pclip_raise_lds(attr_m, {(const void*)adapter_conv3x_bwd_mfma_kernel<1>, (const void*)adapter_conv3x_bwd_mfma_kernel<2>, (const void*)adapter_conv3x_bwd_mfma_kernel<3>,
+                                             (const void*)adapter_conv3x_bwd_mfma_kernel<4>, (const void*)adapter_conv3x_bwd_mfma_kernel<5>, (const void*)adapter_conv3x_bwd_mfma_kernel<6>,
+                                             (const void*)adapter_conv3x_bwd_mfma_kernel<7>, (const void*)adapter_conv3x_bwd_mfma_kernel<8>, (const void*)adapter_conv3x_bwd_mfma_kernel<9>},
+                                    160 * 1024, "pclip_adapter_conv_backward_f16"))
+            return e;
 #define PCLIP_ADAPTER_BWD(N)                                                                                                                  \
         case N: adapter_conv3x_bwd_mfma_kernel<N><<<R, 256, lds_m, st>>>((const half_t*)x, (const half_t*)g, B, D, s, (const half_t*)conv1,    \
                     (const half_t*)ln1w, (const half_t*)ln1b, (const half_t*)conv2, (const half_t*)ln2w, (const half_t*)ln2b,                  \
@@ -1294,13 +1287,7 @@ extern "C" int pclip_adapter_conv_backward_f16(const void* x, const void* g, int
         return pclip_check_launch("adapter_conv_backward (mfma)");
     }
     if (three_x) {
-        if (!attr[1].done()) {
-            if (hipFuncSetAttribute((const void*)adapter_conv_backward_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-                pclip_set_error("pclip_adapter_conv_backward_f16: cannot raise the dynamic LDS limit");
-                return PCLIP_E_LAUNCH;
-            }
-            attr[1].set();
-        }
+        if (int e = pclip_raise_lds(attr, {(const void*)adapter_conv_backward_kernel<true>}, 160 * 1024, "pclip_adapter_conv_backward_f16")) return e;
         adapter_conv_backward_kernel<true><<<B, 256, lds, st>>>((const half_t*)x, (const half_t*)g, D, s, (const half_t*)conv1, (const half_t*)ln1w,
             (const half_t*)ln1b, (const half_t*)conv2, (const half_t*)ln2w, (const half_t*)ln2b, (const half_t*)conv3, (const half_t*)ln3w,
             pw1, pw2, pw3, pg1, pb1, pg2, pb2, pg3, pb3);
@@ -1310,9 +1297,6 @@ extern "C" int pclip_adapter_conv_backward_f16(const void* x, const void* g, int
     }
     return pclip_check_launch("adapter_conv_backward");
 }
-
-namespace {
-}  // namespace
 
 extern "C" int pclip_adapter_fc_f16(const void* x, int B, int D, int H, const void* w1, const void* g1, const void* b1,
                                     const void* w2, const void* g2, const void* b2, float ratio, float one_minus_ratio,
@@ -1363,8 +1347,7 @@ extern "C" int pclip_adapter_conv_f16(const void* x, int B, int D, int three_x, 
         // persistent workgroups, two per CU (register budget of __launch_bounds__(256, 2)); LDS: a1 halo image + u + the reduction scratch
         const int NT = (s2 + 63) / 64, NPX = (NT + 3) / 4;
         const size_t lds_m = (size_t)((hp * 32 + 15) & ~15) + (size_t)(256 * NPX + 8) * 4;
-        int cus = pclip_device_cus();
-        if (cus <= 0) cus = 256;
+        const int cus = pclip_cus();
         const int wgs = NT <= TWO_WG_MAX ? 2 * cus : cus;
         const int grid = B < wgs ? B : wgs;
 #define PCLIP_ADAPTER_LAUNCH(N)                                                                                                               \
@@ -1380,10 +1363,7 @@ extern "C" int pclip_adapter_conv_f16(const void* x, int B, int D, int three_x, 
 #undef PCLIP_ADAPTER_LAUNCH
     } else if (three_x) {
         static DevOnce attr;
-        if (!attr.done()) {
-            (void)hipFuncSetAttribute((const void*)adapter_conv_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            attr.set();
-        }
+        if (int e = pclip_raise_lds(attr, {(const void*)adapter_conv_kernel<true>}, 96 * 1024, "pclip_adapter_conv_f16")) return e;
         adapter_conv_kernel<true><<<B, 256, lds, st>>>((const half_t*)x, D, s, (const half_t*)conv1, (const half_t*)ln1w,
                                                        (const half_t*)ln1b, (const half_t*)conv2, (const half_t*)ln2w,
                                                        (const half_t*)ln2b, (const half_t*)conv3, (const half_t*)ln3w,

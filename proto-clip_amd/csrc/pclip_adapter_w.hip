@@ -483,14 +483,6 @@ __global__ __launch_bounds__(256) void adapter_conv_w_backward_kernel(
 
 constexpr size_t kLdsMax = 160 * 1024;
 
-template <class K>
-bool raise_lds_limit(K kernel, DevOnce& once) {
-    if (once.done()) return true;
-    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) != hipSuccess) return false;
-    once.set();
-    return true;
-}
-
 bool width_ok(int width) { return width == 8 || width == 16 || width == 24 || width == 32; }
 int side_of(int D) {
     int s = 1;
@@ -505,9 +497,8 @@ int launch_forward(const void* x, int B, int D, const void* conv1, const void* l
     const size_t lds = (size_t)(1024 + 1024 + 4) * 4 + (THREE_X ? (size_t)2 * W * hp + (size_t)2 * W * s2 : 0);
     if (lds > kLdsMax) { pclip_set_error("pclip_adapter_conv_w_f16: %zu bytes of LDS at width %d, D=%d", lds, W, D); return PCLIP_E_INVALID; }
     static DevOnce once;
-    if (!raise_lds_limit(adapter_conv_w_kernel<W, THREE_X>, once)) { pclip_set_error("pclip_adapter_conv_w_f16: cannot raise the dynamic LDS limit"); return PCLIP_E_LAUNCH; }
-    int cus = pclip_device_cus();
-    if (cus <= 0) cus = 256;
+    if (int e = pclip_raise_lds(once, {(const void*)adapter_conv_w_kernel<W, THREE_X>}, (int)kLdsMax, "pclip_adapter_conv_w_f16")) return e;
+    const int cus = pclip_cus();
     const int grid = B < 2 * cus ? B : 2 * cus;                   // persistent over rows; two workgroups share a CU where their LDS allows it
     adapter_conv_w_kernel<W, THREE_X><<<grid, 256, lds, st>>>((const half_t*)x, B, D, s, (const half_t*)conv1, (const half_t*)ln1w, (const half_t*)ln1b,
         (const half_t*)conv2, (const half_t*)ln2w, (const half_t*)ln2b, (const half_t*)conv3, (const half_t*)ln3w, (const half_t*)ln3b, l2norm_out, (half_t*)y, y_sq);
@@ -522,7 +513,7 @@ int launch_backward(const void* x, const void* g, int B, int D, const void* conv
     const size_t lds = (size_t)(1024 + 1024 + 4 + 4 * W) * 4 + (THREE_X ? (size_t)2 * 2 * W * hp : 0);
     if (lds > kLdsMax) { pclip_set_error("pclip_adapter_conv_w_backward_f16: %zu bytes of LDS at width %d, D=%d", lds, W, D); return PCLIP_E_INVALID; }
     static DevOnce once;
-    if (!raise_lds_limit(adapter_conv_w_backward_kernel<W, THREE_X>, once)) { pclip_set_error("pclip_adapter_conv_w_backward_f16: cannot raise the dynamic LDS limit"); return PCLIP_E_LAUNCH; }
+    if (int e = pclip_raise_lds(once, {(const void*)adapter_conv_w_backward_kernel<W, THREE_X>}, (int)kLdsMax, "pclip_adapter_conv_w_backward_f16")) return e;
     adapter_conv_w_backward_kernel<W, THREE_X><<<B, 256, lds, st>>>((const half_t*)x, (const half_t*)g, D, s, (const half_t*)conv1, (const half_t*)ln1w,
         (const half_t*)ln1b, (const half_t*)conv2, (const half_t*)ln2w, (const half_t*)ln2b, (const half_t*)conv3, (const half_t*)ln3w, pw1, pw2, pw3, pg1, pb1,
         pg2, pb2, pg3, pb3);

@@ -18,7 +18,7 @@ template <int NW, int VAR, bool QF = false>   // waves per workgroup (__launch_b
 __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(const half_t* __restrict__ qp, int ldq, long q_batch,
                                                            const half_t* __restrict__ kvp, int ldkv, int k_off, int v_off,
                                                            half_t* __restrict__ out, int L, int Lq, int H, int causal, int NT,
-                                                           int LV) {
+                                                           int /* former V leading dimension: V is kept row-major, always 0 */) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int LP = NT * 32;
     half_t* Ks = reinterpret_cast<half_t*>(smem);             // [LP][64], 16-byte chunks XOR-swizzled by swz_key(row)
@@ -236,7 +236,6 @@ extern "C" int pclip_attention_q_f16(const void* q, int ldq, long q_batch_stride
                   "pclip_attention_q_f16: strides / offsets must be multiples of 8 halves");
     if (B == 0) return PCLIP_OK;
     const int NT = ceil_div(L, 32), LP = NT * 32;
-    const int LV = 0;                                       // (unused: V is kept row-major now)
     // mode 1 only: the persistent double-buffered kernel, one workgroup per CU (short sequences: as many as the LDS holds, at
     // most two: the register budget of the deep-prefetch loop).  Measured: 8 % faster than one workgroup per
     // item in isolation on N(0,1) data (348 vs 377 us, ViT-B/16 B = 1024), no faster inside the encoder (40.3 vs 40.2 ms per
@@ -247,14 +246,9 @@ extern "C" int pclip_attention_q_f16(const void* q, int ldq, long q_batch_stride
     const size_t plds = (2 * (size_t)(KR + LP) + KR) * ATT_DH * 2;          // two K/V buffers + the query rows
     if (Lq == L && g_att_mode != 0 && NT <= 8 && plds <= 160 * 1024 && cus > 0 && g_att_mode == 1) {
         static DevOnce pipe_attr;
-        if (!pipe_attr.done()) {
-            if (hipFuncSetAttribute((const void*)attention_pipe_kernel<4, 2, PCLIP_ATT_VAR_SHORT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute((const void*)attention_pipe_kernel<8, 2, PCLIP_ATT_VAR_LONG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-                pclip_set_error("pclip_attention_f16: cannot raise the dynamic LDS limit");
-                return PCLIP_E_LAUNCH;
-            }
-            pipe_attr.set();
-        }
+        if (int e = pclip_raise_lds(pipe_attr, {(const void*)attention_pipe_kernel<4, 2, PCLIP_ATT_VAR_SHORT>, (const void*)attention_pipe_kernel<8, 2, PCLIP_ATT_VAR_LONG>},
+                                    160 * 1024, "pclip_attention_f16"))
+            return e;
         int per_cu = NT <= 4 ? (int)((160 * 1024) / plds) : 1;
         per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);
         long grid = (long)cus * per_cu;
@@ -272,32 +266,26 @@ extern "C" int pclip_attention_q_f16(const void* q, int ldq, long q_batch_stride
     // The softmax variant follows the SEQUENCE (more than four key tiles: the long form), not the kernel: the one-query form of the
     // last vision block (Lq = 1, four waves) must produce the bits of the full attention over the same keys.
     static DevOnce attr_set;
-    if (!attr_set.done()) {
-        const void* fns[] = {(const void*)attention_kernel<8, PCLIP_ATT_VAR_LONG>, (const void*)attention_kernel<4, PCLIP_ATT_VAR_LONG>,
-                             (const void*)attention_kernel<4, PCLIP_ATT_VAR_SHORT>, (const void*)attention_kernel<8, PCLIP_ATT_VAR_LONG, true>,
-                             (const void*)attention_kernel<4, PCLIP_ATT_VAR_SHORT, true>};
-        for (const void* f : fns)
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess) {
-                pclip_set_error("pclip_attention_f16: cannot raise the dynamic LDS limit");
-                return PCLIP_E_LAUNCH;
-            }
-        attr_set.set();
-    }
+    if (int e = pclip_raise_lds(attr_set, {(const void*)attention_kernel<8, PCLIP_ATT_VAR_LONG>, (const void*)attention_kernel<4, PCLIP_ATT_VAR_LONG>,
+                                           (const void*)attention_kernel<4, PCLIP_ATT_VAR_SHORT>, (const void*)attention_kernel<8, PCLIP_ATT_VAR_LONG, true>,
+                                           (const void*)attention_kernel<4, PCLIP_ATT_VAR_SHORT, true>},
+                                80 * 1024, "pclip_attention_f16"))
+        return e;
     // more than four query tiles (ViT-B/16: 7, ViT-L/14: 9): eight waves, one tile each, two workgroups = four waves per SIMD
     // (VGPRs capped at 128); measured 438 -> 424 us (ViT-B/16), 224 -> 200 us (ViT-L/14), bit-identical.  Short sequences
     // (ViT-B/32: 2 tiles, text: 3) keep the four-wave workgroup, whose idle waves cost less.
 #define PCLIP_ATT_LAUNCH(NW, VAR)                                                                                                         \
     attention_kernel<NW, VAR><<<B * H, NW * 64, lds, (hipStream_t)stream>>>((const half_t*)q, ldq, q_batch_stride, (const half_t*)kv, ldkv, k_off, \
-                                                                             v_off, (half_t*)out, L, Lq, H, causal, NT, LV)
-    static const bool qfirst = !(getenv("PCLIP_ATT_QFIRST") && getenv("PCLIP_ATT_QFIRST")[0] == '0');      // A/B switch
+                                                                             v_off, (half_t*)out, L, Lq, H, causal, NT, 0)
+    static const bool qfirst = pclip_env_on("PCLIP_ATT_QFIRST");      // A/B switch
     // short NON-causal sequences (ViT-B/32: 50 tokens = 2 tiles): every wave of the four-wave workgroup has at most one tile too: 71.9 -> 68.0 us (B = 1024), same bits;
     // the causal text sequences (77 tokens) lose 14 % in this form (489 -> 558 us: their waves' work is triangular) and keep the looping kernel
     if (PCLIP_ATT_QF4 && qfirst && NT <= 4 && Lq == L && !causal)
         attention_kernel<4, PCLIP_ATT_VAR_SHORT, true><<<B * H, 4 * 64, lds, (hipStream_t)stream>>>((const half_t*)q, ldq, q_batch_stride, (const half_t*)kv, ldkv, k_off,
-                                                                                                     v_off, (half_t*)out, L, Lq, H, causal, NT, LV);
+                                                                                                     v_off, (half_t*)out, L, Lq, H, causal, NT, 0);
     else if ((Lq + 31) / 32 > 4 && (Lq + 31) / 32 <= 8 && NT <= 8 && qfirst)      // NT <= 8: the kernel's counted waits assume at most four pieces per wave and operand
         attention_kernel<8, PCLIP_ATT_VAR_LONG, true><<<B * H, 8 * 64, lds, (hipStream_t)stream>>>((const half_t*)q, ldq, q_batch_stride, (const half_t*)kv, ldkv, k_off,
-                                                                                                    v_off, (half_t*)out, L, Lq, H, causal, NT, LV);
+                                                                                                    v_off, (half_t*)out, L, Lq, H, causal, NT, 0);
     else if ((Lq + 31) / 32 > 4) PCLIP_ATT_LAUNCH(8, PCLIP_ATT_VAR_LONG);
     else if (NT > 4) PCLIP_ATT_LAUNCH(4, PCLIP_ATT_VAR_LONG);
     else PCLIP_ATT_LAUNCH(4, PCLIP_ATT_VAR_SHORT);

@@ -240,14 +240,7 @@ extern "C" int pclip_attention_backward_f16(const void* qkv, const void* dout, v
     const int NT = ceil_div(L, 32), LP = NT * 32;
     const size_t lds = (size_t)LP * (4 * ABW_ROW + 3 * sizeof(float));       // 150 912 B at L = 288
     static DevOnce attr_set;
-    if (!attr_set.done()) {
-        if (hipFuncSetAttribute((const void*)attention_bwd_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)attention_bwd_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            pclip_set_error("pclip_attention_backward_f16: cannot raise the dynamic LDS limit");
-            return PCLIP_E_LAUNCH;
-        }
-        attr_set.set();
-    }
+    if (int e = pclip_raise_lds(attr_set, {(const void*)attention_bwd_kernel<4>, (const void*)attention_bwd_kernel<8>}, 160 * 1024, "pclip_attention_backward_f16")) return e;
     // up to four tiles: four waves (two workgroups per CU fit the LDS up to L = 128); more: eight waves, one workgroup per CU
     if (NT <= 4)
         attention_bwd_kernel<4><<<B * H, 4 * 64, lds, (hipStream_t)stream>>>((const half_t*)qkv, (const half_t*)dout, (half_t*)dqkv, L, H, causal, NT);

@@ -540,20 +540,10 @@ extern "C" int pclip_sqdist_f16(const void* q, const void* zi, const void* zt, i
     {   // enough 256x256 tiles to fill the chip a few times over: persistent big-tile kernel
         using CB = pgemm::Cfg<256, 256, 2, 4>;
         const int tm = ceil_div(Q, CB::BM), tn = ceil_div(N, CB::BN), per_bank = tm * tn, ntiles = per_bank * (zt ? 2 : 1);
-        static int cus = 0;
-        if (!cus) {
-            cus = pclip_device_cus();
-            if (cus <= 0) cus = 256;
-        }
+        static const int cus = pclip_cus();
         if (ntiles >= 3 * cus && D >= 128 && Q % 4 == 0 && N % 4 == 0 && Q >= 4 && N >= 4) {
             static DevOnce attr;
-            if (!attr.done()) {
-                if (hipFuncSetAttribute((const void*)sqdist_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CB::LDS_BYTES + 4096) != hipSuccess) {
-                    pclip_set_error("pclip_sqdist_f16: cannot raise the dynamic LDS limit to %d", CB::LDS_BYTES + 4096);
-                    return PCLIP_E_LAUNCH;
-                }
-                attr.set();
-            }
+            if (int e = pclip_raise_lds(attr, {(const void*)sqdist_big_kernel}, CB::LDS_BYTES + 4096, "pclip_sqdist_f16")) return e;
             sqdist_big_kernel<<<ntiles < cus ? ntiles : cus, 512, CB::LDS_BYTES + 4096, s>>>((const half_t*)q, (const half_t*)zi, (const half_t*)zt, Q, N, D,
                                                                                     q_sq, zi_sq, zt_sq, d2i, d2t, ldd, tn, per_bank, ntiles);
             return pclip_check_launch("sqdist (big tile)");
@@ -607,8 +597,7 @@ extern "C" int pclip_classify_ex_f16(const void* q, const void* zi, const void* 
     switch (classify_route(Q, N, D, alpha, one_minus_alpha, beta, zt != nullptr, p != nullptr, argmax != nullptr, k, topk_p || topk_i, flags, ws_bytes)) {
         case MID: return pclip_classify_mid_launch(q, zi, zt, Q, N, D, alpha, one_minus_alpha, beta, p, argmax, s);
         case SMALL: {
-            int cus = pclip_device_cus();
-            if (cus <= 0) cus = 256;
+            const int cus = pclip_cus();
 #define PCLIP_SMALL(NT)                                                                                                                   \
     return zt ? launch_classify_small<NT, true>(q, zi, zt, Q, N, D, alpha, one_minus_alpha, beta, p, argmax, topk_p, topk_i, k, cus, s) \
               : launch_classify_small<NT, false>(q, zi, zt, Q, N, D, alpha, one_minus_alpha, beta, p, argmax, topk_p, topk_i, k, cus, s)

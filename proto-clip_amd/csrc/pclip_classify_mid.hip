@@ -318,13 +318,8 @@ int launch_mid2(const void* q, const void* zi, const void* zt, int Q, int N, int
                 hipStream_t s) {
     const size_t lds = classify_mid_lds(D, TPW, SL, NCH > 0);
     static DevOnce attr;
-    if (!attr.done()) {
-        if (hipFuncSetAttribute((const void*)classify_mid_kernel<TPW, NCH, SL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)classify_mid_lds(NCH > 0 ? NCH * 128 : 2048, TPW, SL, NCH > 0)) != hipSuccess) {
-            pclip_set_error("pclip_classify_f16: cannot raise the dynamic LDS limit (mid-N kernel)");
-            return PCLIP_E_LAUNCH;
-        }
-        attr.set();
-    }
+    if (int e = pclip_raise_lds(attr, {(const void*)classify_mid_kernel<TPW, NCH, SL>}, (int)classify_mid_lds(NCH > 0 ? NCH * 128 : 2048, TPW, SL, NCH > 0), "pclip_classify_f16 (mid-N kernel)"))
+        return e;
     const int ngroups = ceil_div(Q, 16);
     const int cap = (SL == 8 ? 1 : 2) * cus;
     const int grid = ngroups < cap ? ngroups : cap;
@@ -360,8 +355,7 @@ bool pclip_classify_mid_applies(int Q, int N, int D, bool has_zt, bool topk, boo
 
 int pclip_classify_mid_launch(const void* q, const void* zi, const void* zt, int Q, int N, int D, float alpha, float oma, float beta, float* p, int32_t* argmax,
                               hipStream_t s) {
-    int cus = pclip_device_cus();
-    if (cus <= 0) cus = 256;
+    const int cus = pclip_cus();
     const int ntiles = ceil_div(N, 16);
     if (ntiles <= 4) return launch_mid<1, 4>(q, zi, zt, Q, N, D, alpha, oma, beta, p, argmax, cus, s);
     if (ntiles <= 8) return launch_mid<1, 8>(q, zi, zt, Q, N, D, alpha, oma, beta, p, argmax, cus, s);

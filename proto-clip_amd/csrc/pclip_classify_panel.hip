@@ -372,8 +372,7 @@ __global__ __launch_bounds__(512, 2) void classify_panel_kernel(const half_t* __
 
 size_t pclip_classify_panel_workspace(int Q, int N, int D) {
     const size_t rows2 = (size_t)2 * ((N + 127) / 128 * 128), Qp = (size_t)(Q + 255) / 256 * 256;
-    int cus = pclip_device_cus();
-    if (cus <= 0) cus = 256;
+    const int cus = pclip_cus();
     const size_t npanels = Qp / 256, grid = npanels < (size_t)cus ? npanels : (size_t)cus;
     // + the candidate records: per resident panel and class tile 8 x 256 groups x 32 B (a quarter of the fp32 distance rows the two stages would write)
     return align_up(rows2 * D * 2, 256) + align_up(rows2 * 4, 256) + align_up(Qp * 4, 256) + grid * (rows2 / 256) * (8 * 256 * 32) + 256;
@@ -424,8 +423,7 @@ int pclip_classify_panel_launch(const void* q, const void* zi, const void* zt, i
         if (D <= 512) PCLIP_PREP(1); else if (D <= 1024) PCLIP_PREP(2); else if (D <= 2048) PCLIP_PREP(4); else PCLIP_PREP(8);
 #undef PCLIP_PREP
     }
-    int cus = pclip_device_cus();
-    if (cus <= 0) cus = 256;
+    const int cus = pclip_cus();
     const int npanels = Qp / 256, grid = npanels < cus ? npanels : cus;
     constexpr int LDS = CP::LDS_BYTES + 8192 + 64 + 2048;              // K-tile ring | norm strips + per-row constants | tile mask | the candidates' best per row
     // d2 = max(||q||^2 + ||z||^2 - 2 q.z, 0) by default: without torch.cdist's sqrt -> square round trip (<= 1 fp32 ulp from the two-stage path's distances, whose
@@ -435,13 +433,7 @@ int pclip_classify_panel_launch(const void* q, const void* zi, const void* zt, i
 #define PCLIP_PANEL(EX, DU, CA)                                                                                                                  \
     do {                                                                                                                                         \
         static DevOnce attr;                                                                                                                     \
-        if (!attr.done()) {                                                                                                                      \
-            if (hipFuncSetAttribute((const void*)classify_panel_kernel<EX, DU, CA>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) { \
-                pclip_set_error("pclip_classify_f16: cannot raise the dynamic LDS limit to %d", LDS);                                            \
-                return PCLIP_E_LAUNCH;                                                                                                           \
-            }                                                                                                                                    \
-            attr.set();                                                                                                                          \
-        }                                                                                                                                        \
+        if (int e = pclip_raise_lds(attr, {(const void*)classify_panel_kernel<EX, DU, CA>}, LDS, "pclip_classify_f16")) return e;                \
         classify_panel_kernel<EX, DU, CA><<<DU ? 1 : grid, 512, LDS, s>>>((const half_t*)q, zz, Q, rows2, D, q_sqp, zz_sq, alpha, oma, w, argmax, dump, DU ? 1 : npanels, rec, stats, passes); \
     } while (0)
     const bool cand = passes != 1;

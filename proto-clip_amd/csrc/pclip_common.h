@@ -1,9 +1,11 @@
 // Shared device/host helpers for libpclip (gfx950 only: wave64, MFMA, 160 KiB LDS).
 #pragma once
 #include <atomic>
+#include <initializer_list>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdlib.h>
 #include "../../include/pclip.h"
 
 typedef _Float16 half_t;
@@ -133,6 +135,31 @@ struct DevOnce {
     bool done() const { return (mask.load(std::memory_order_acquire) & bit()) != 0; }
     void set() { mask.fetch_or(bit(), std::memory_order_release); }
 };
+
+// Raise the dynamic-LDS limit of every kernel in `fns` to `bytes`, once per device; `entry` names the entry point in the error.
+static inline int pclip_raise_lds(DevOnce& once, std::initializer_list<const void*> fns, int bytes, const char* entry) {
+    if (once.done()) return PCLIP_OK;
+    for (const void* fn : fns)
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
+            pclip_set_error("%s: cannot raise the dynamic LDS limit to %d", entry, bytes);
+            return PCLIP_E_LAUNCH;
+        }
+    once.set();
+    return PCLIP_OK;
+}
+
+// CU count of the current device for sizing grids; 256 (MI355X) where it is unknown.  Callers that must tell "unknown" apart test pclip_device_cus() > 0 themselves.
+static inline int pclip_cus() {
+    int cus = pclip_device_cus();
+    if (cus <= 0) cus = 256;
+    return cus;
+}
+
+// A/B environment switch that is on unless set to a value starting with '0'.  Callers keep the result in a static: one getenv per process.
+static inline bool pclip_env_on(const char* name) {
+    const char* e = getenv(name);
+    return !(e && e[0] == '0');
+}
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }

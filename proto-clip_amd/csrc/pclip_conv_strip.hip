@@ -329,13 +329,7 @@ template <int CIN, int COUT, int ACT, bool POOL = false>
 int launch_strip(const void* x, const void* w, int B, int H, int W, const float* scale, const float* shift, void* y, int cus, hipStream_t s) {
     static DevOnce attr;
     constexpr int LDS = 2 * StripGeo<CIN>::BUF;
-    if (!attr.done()) {
-        if (hipFuncSetAttribute((const void*)conv3x3_strip_kernel<CIN, COUT, ACT, POOL>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-            pclip_set_error("pclip_conv3x3_bn_f16: cannot raise the dynamic LDS limit to %d", LDS);
-            return PCLIP_E_LAUNCH;
-        }
-        attr.set();
-    }
+    if (int e = pclip_raise_lds(attr, {(const void*)conv3x3_strip_kernel<CIN, COUT, ACT, POOL>}, LDS, "pclip_conv3x3_bn_f16")) return e;
     const int ntiles = B * (H / ST_ROWS) * (W / ST_COLS), ldw = (9 * CIN + 63) / 64 * 64;
     conv3x3_strip_kernel<CIN, COUT, ACT, POOL><<<ntiles < cus ? ntiles : cus, 256, LDS, s>>>((const half_t*)x, (const half_t*)w, ldw, H, W, ntiles, scale,
                                                                                       shift, (half_t*)y);
@@ -346,7 +340,7 @@ int launch_strip(const void* x, const void* w, int B, int H, int W, const float*
 
 // Does the strip kernel take this convolution?  (pclip_conv3x3_bn_f16's routing; exported for the tests' route check.)
 extern "C" int pclip_conv3x3_strip_applies(int B, int H, int W, int Cin, int Cout) {
-    static const bool env_on = !(getenv("PCLIP_CONV_STRIP") && getenv("PCLIP_CONV_STRIP")[0] == '0');
+    static const bool env_on = pclip_env_on("PCLIP_CONV_STRIP");
     const bool on = g_strip_mode < 0 ? env_on : g_strip_mode != 0;
     // (by the layer's shape alone, never by the batch: an image's features do not depend on how many images are encoded with it — tests/test_gpu_encoder.py)
     return on && (Cin == 32 || Cin == 64) && (Cout == 32 || Cout == 64) && H % ST_ROWS == 0 && W % ST_COLS == 0 && B > 0 && (long)H * W * Cin * 2 < (1L << 31);
@@ -390,7 +384,7 @@ int pclip_conv3x3_strip_launch(const void* x, const void* w, int B, int H, int W
 // The stem's first convolution + BatchNorm + ReLU straight from the NCHW images (fp32 or fp16): see stem_conv_kernel.  R even, ((R - 1) / 2 + 1) a multiple of 56 (and of
 // 8), Cout 32 or 64, w [Cout][64] in im2col column order (ky, kx, channel; zero beyond 27).
 extern "C" int pclip_stem_conv_applies(int R, int Cout) {
-    static const bool env_on = !(getenv("PCLIP_CONV_STEM") && getenv("PCLIP_CONV_STEM")[0] == '0');
+    static const bool env_on = pclip_env_on("PCLIP_CONV_STEM");
     const int Ho = (R - 1) / 2 + 1;
     return env_on && R > 0 && R % 2 == 0 && Ho % ST_ROWS == 0 && Ho % ST_COLS == 0 && (Cout == 32 || Cout == 64);
 }
@@ -420,7 +414,7 @@ extern "C" int pclip_stem_conv_bn_f16(const void* img, int img_is_f32, int B, in
 // relu(bn(conv3x3(x))) followed by nn.AvgPool2d(2), in one launch: y [B * (H / 2) * (W / 2), Cout] — the stem's conv3 / bn3 / relu / avgpool (clip/model.py:104-105,
 // 142-143).  Same bits as pclip_conv3x3_bn_f16 (strip kernel) + pclip_avgpool_nhwc_f16.  Shapes: pclip_conv3x3_pool_applies (Cin 32, Cout 64, H % 8 == 0, W % 56 == 0).
 extern "C" int pclip_conv3x3_pool_applies(int H, int W, int Cin, int Cout) {
-    static const bool env_on = !(getenv("PCLIP_CONV_POOL") && getenv("PCLIP_CONV_POOL")[0] == '0');
+    static const bool env_on = pclip_env_on("PCLIP_CONV_POOL");
     return env_on && pclip_conv3x3_strip_applies(1, H, W, Cin, Cout) && Cin == 32 && Cout == 64;
 }
 
@@ -431,7 +425,5 @@ extern "C" int pclip_conv3x3_bn_pool_f16(const void* x, const void* w, int B, in
                   "pclip_conv3x3_bn_pool_f16: shape H=%d W=%d Cin=%d Cout=%d not supported (pclip_conv3x3_pool_applies; use pclip_conv3x3_bn_f16 + pclip_avgpool_nhwc_f16)", H, W, Cin, Cout);
     PCLIP_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0 && ((uintptr_t)y & 15) == 0, "pclip_conv3x3_bn_pool_f16: pointers must be 16-byte aligned");
     if (B == 0) return PCLIP_OK;
-    int cus = pclip_device_cus();
-    if (cus <= 0) cus = 256;
-    return pclip_conv3x3_strip_launch(x, w, B, H, W, Cin, Cout, scale, shift, 1, y, cus, (hipStream_t)stream, 2);
+    return pclip_conv3x3_strip_launch(x, w, B, H, W, Cin, Cout, scale, shift, 1, y, pclip_cus(), (hipStream_t)stream, 2);
 }

@@ -582,17 +582,6 @@ int ce_validate(const char* fn, const void* a, int lda, int M, const void* b, in
     return PCLIP_OK;
 }
 
-template <typename K>
-int ce_raise_lds(const char* fn, K kernel, DevOnce& attr) {
-    if (attr.done()) return PCLIP_OK;
-    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CE_LDS_MAX) != hipSuccess) {
-        pclip_set_error("%s: cannot raise the dynamic LDS limit to %d", fn, CE_LDS_MAX);
-        return PCLIP_E_LAUNCH;
-    }
-    attr.set();
-    return PCLIP_OK;
-}
-
 int ce_norm_rows(const half_t* x, int ldx, half_t* y, int R, int D, hipStream_t s) {
     int g = ceil_div(R, 4);
     g = g > 8192 ? 8192 : g;
@@ -641,7 +630,7 @@ extern "C" int pclip_cosine_ce_f16(const void* a, int lda, int M, const void* b,
 #define PCLIP_CE_FWD(NCH, RFV, NDF)                                                                                                               \
     do {                                                                                                                                        \
         static DevOnce attr;                                                                                                                    \
-        if (int e = ce_raise_lds(fn, ce_fwd_kernel<NCH, RFV>, attr)) return e;                                                                  \
+        if (int e = pclip_raise_lds(attr, {(const void*)ce_fwd_kernel<NCH, RFV>}, CE_LDS_MAX, fn)) return e;                                     \
         ce_fwd_kernel<NCH, RFV><<<npanels, 64 * CE_FW, lds, s>>>((const half_t*)a, lda, M, bw, ldbw, T, D, scale, (flags & PCLIP_CE_NORMALIZE_A) ? 1 : 0, \
                                                        symmetric, labels, (flags & PCLIP_CE_LABELS_I64) ? 1 : 0, lse_row, tgt, row_loss, colpart); \
     } while (0)
@@ -699,7 +688,7 @@ extern "C" int pclip_cosine_ce_backward_f16(const void* a, int lda, int M, const
 #define PCLIP_CE_BWD(NCH, RFV, NDF)                                                                                                        \
     do {                                                                                                                                 \
         static DevOnce attr;                                                                                                             \
-        if (int e = ce_raise_lds(fn, ce_bwd_kernel<NCH, RFV, NDF>, attr)) return e;                                                      \
+        if (int e = pclip_raise_lds(attr, {(const void*)ce_bwd_kernel<NCH, RFV, NDF>}, CE_LDS_MAX, fn)) return e;                         \
         ce_bwd_kernel<NCH, RFV, NDF><<<grid, 256, lds, s>>>(own, ldo, Ro, walk, ldw, Rw, walkT, ldt, D, scale, weight, norm_own, symmetric, lab_own, lab_walk, \
                                                              (flags & PCLIP_CE_LABELS_I64) ? 1 : 0, lse_own, lse_walk, gpanel, dsc_part);   \
     } while (0)

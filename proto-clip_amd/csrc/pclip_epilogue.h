@@ -35,6 +35,39 @@ __device__ __forceinline__ half4_t quick_gelu16x4(float4_t v) {
     return half4_t{y01[0], y01[1], y23[0], y23[1]};
 }
 
+// Plain fp32 -> fp16 of four values: the one rounding of r16(acc + bias) (the bias is already inside the accumulators).
+__device__ __forceinline__ half4_t cvt16x4(float4_t v) {
+    half4_t h;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) h[e] = (half_t)v[e];
+    return h;
+}
+
+// eval-mode BatchNorm (+ReLU) on four columns with their scale / shift (clip/model.py:43-52), two roundings: the convolution's output is an fp16 tensor
+// (r16(v)), and so is bn's (r16(. * sc + sh), the product and the sum in fp32); ReLU is exact.
+template <bool RELU>
+__device__ __forceinline__ half4_t bn16x4(float4_t v, float4_t sc, float4_t sh) {
+    half4_t h;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float y = r16(r16(v[e]) * sc[e] + sh[e]);
+        if (RELU) y = fmaxf(y, 0.f);
+        h[e] = (half_t)y;
+    }
+    return h;
+}
+
+// Residual add on one 16-byte chunk: r16(x + h) of two fp16 tensors — one rounding, the sum in fp32 — (+ exact ReLU: `out += identity; relu` of a bottleneck).
+template <bool RELU>
+__device__ __forceinline__ half8_t add_residual16x8(half8_t x, half8_t h) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float y = r16((float)x[j] + (float)h[j]);
+        h[j] = (half_t)(RELU ? fmaxf(y, 0.f) : y);
+    }
+    return h;
+}
+
 // Output rows of the persistent linear kernels: non-temporal 16-byte stores (A/B switch PCLIP_NT_STORE) — a c_fc launch writes
 // 1.2 GB that nobody re-reads before it has left the 4 MiB L2 anyway; keeping it out leaves the L2 to the operand panels.
 #ifndef PCLIP_NT_STORE

@@ -151,21 +151,11 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void linear_fast_kernel(const half_
         const bool colok = !KT || col < N;                    // KT: the chunk exists (N % 8 == 0)
         auto pre = [&](int i, int j, int coff, float4_t v, int rl, int g) {
             if (ACT == 1) return quick_gelu16x4(v);
-            half4_t h;
             if (AFFINE) {
                 const float* st = affine_lds + parity * 2 * C::BN + wn * (C::BN / C::WN) + j * 32 + coff;
-                const float4_t sc = *reinterpret_cast<const float4_t*>(st), sh = *reinterpret_cast<const float4_t*>(st + C::BN);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float y = r16(r16(v[e]) * sc[e] + sh[e]);              // bn(conv(x)): the conv output is an fp16 tensor
-                    if (ACT == 3) y = fmaxf(y, 0.f);
-                    h[e] = (half_t)y;
-                }
-                return h;
+                return bn16x4<ACT == 3>(v, *reinterpret_cast<const float4_t*>(st), *reinterpret_cast<const float4_t*>(st + C::BN));
             }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) h[e] = (half_t)v[e];
-            return h;
+            return cvt16x4(v);
         };
         // Residual operand: the NPASS 16-byte chunks a thread adds to in slab h are requested TOGETHER in the slab hook, before
         // the slab is staged (they fly during the LDS write pass) — Cout may alias residual (in-place residual stream), so the
@@ -193,15 +183,8 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void linear_fast_kernel(const half_
                 if ((full || m0 + r < M) && colok) rr[ps] = ld_half8(residual + (size_t)(m0 + r) * ldc + col);
             }
         };
-        auto add_res = [&](int pass, half8_t h) {
-            const half8_t x = rr[RES ? pass % C::NPASS : 0];     // (PIPE: pass = 4 k + ps -> (k & 1) * 4 + ps = pass % 8, NPASS = 8)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float y = r16((float)x[j] + (float)h[j]);
-                h[j] = (half_t)(ACT == 5 ? fmaxf(y, 0.f) : y);
-            }
-            return h;
-        };
+        // (PIPE: pass = 4 k + ps -> (k & 1) * 4 + ps = pass % 8, NPASS = 8)
+        auto add_res = [&](int pass, half8_t h) { return add_residual16x8<ACT == 5>(rr[RES ? pass % C::NPASS : 0], h); };
         if constexpr (PIPE) {
             static_assert(C::NPASS == 8, "rr[pass % NPASS] pairs slab parity and pass");
             if (full)
@@ -302,16 +285,8 @@ __global__ __launch_bounds__(C::NTHREADS, 2) void conv3x3_fast_kernel(const half
         char* stg = smem + (p ^ 1) * C::STAGE_BYTES;
         const int col = n0 + 8 * (tid % C::CPR);
         auto pre = [&](int, int j, int coff, float4_t v, int rl, int g) {
-            half4_t h;
             const float* st = affine_lds + parity * 2 * C::BN + wn * (C::BN / C::WN) + j * 32 + coff;
-            const float4_t sc = *reinterpret_cast<const float4_t*>(st), sh = *reinterpret_cast<const float4_t*>(st + C::BN);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float y = r16(r16(v[e]) * sc[e] + sh[e]);
-                if (ACT == 3) y = fmaxf(y, 0.f);
-                h[e] = (half_t)y;
-            }
-            return h;
+            return bn16x4<ACT == 3>(v, *reinterpret_cast<const float4_t*>(st), *reinterpret_cast<const float4_t*>(st + C::BN));
         };
         const bool colok = !TAIL || col < N;
         if (full)
@@ -387,7 +362,14 @@ using CfgSmall = pgemm::CfgSmall;
 
 // Tile-order switches (PCLIP_GEMM_BAND, PCLIP_GEMM_REV): read from the environment ONCE; only under PCLIP_GEMM_CFG_LIVE (the A/B tools flip
 // them between calls of one process) are they re-read per launch — no getenv on the product's launch path.
-struct TileOrder { int band, rev, band_n; };      // band: launches with >= 8 column tiles (c_fc); band_n: narrower ones (in_proj: 9 -> 8 counts as wide; out_proj / c_proj: 3)
+struct TileOrder {
+    int band, rev, band_n;                        // band: launches with >= 8 column tiles (c_fc); band_n: narrower ones (in_proj: 9 -> 8 counts as wide; out_proj / c_proj: 3)
+    // Tile order against the Infinity Cache (256 MiB, memory-side): a LayerNorm / attention pass writes its 310 MB output in ascending row order, so what is still
+    // cached when the consuming GEMM starts are its LAST rows — walking the tiles in descending order reads those first (and leaves the GEMM's own first-written, high
+    // rows to be evicted, its low rows fresh for the ascending pass behind it).  Same bits (tile order only); bench +0.4 % (profiles/r03_bench_rev.txt).  Default 2.
+    // 1: every launch descending; 2: only the launches that read a LayerNorm / attention output (K <= 1024: in_proj, c_fc, out_proj), c_proj ascending behind the descending c_fc
+    bool descending(int K) const { return rev == 1 || (rev == 2 && K <= 1024); }
+};
 static TileOrder read_tile_order() {
     const char* b = getenv("PCLIP_GEMM_BAND");
     const char* r = getenv("PCLIP_GEMM_REV");
@@ -408,28 +390,13 @@ static int launch_fast2(const void* A, int lda, const void* B, int ldb, int M, i
     static DevOnce attr;
     constexpr int LDS = C::LDS_BYTES + ((ACT == 2 || ACT == 3 || ACT == 5) ? 2 * 2 * C::BN * 4 : 2 * C::BN * 2) + 256;   // K-tile ring + double-buffered bias / affine strips + prefetch scrap
     using CK = std::conditional_t<KT, pgemm::Tail<C>, C>;
-    const void* fn = (const void*)linear_fast_kernel<CK, HAS_BIAS, ACT>;
-    if (!attr.done()) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                LDS) != hipSuccess) {
-            pclip_set_error("pclip_gemm_f16: cannot raise the dynamic LDS limit to %d", LDS);
-            return PCLIP_E_LAUNCH;
-        }
-        attr.set();
-    }
+    if (int e = pclip_raise_lds(attr, {(const void*)linear_fast_kernel<CK, HAS_BIAS, ACT>}, LDS, "pclip_gemm_f16")) return e;
     const int tiles_m = ceil_div(M, C::BM), tiles_n = KT ? ceil_div(N, C::BN) : N / C::BN, ntiles = tiles_m * tiles_n;
     const int grid = ntiles < slots ? ntiles : slots;
     const TileOrder& order = tile_order();
-    const int band = order.band;
-    // Tile order against the Infinity Cache (256 MiB, memory-side): a LayerNorm / attention pass writes its 310 MB output in ascending row order, so what is still
-    // cached when the consuming GEMM starts are its LAST rows — walking the tiles in descending order reads those first (and leaves the GEMM's own first-written, high
-    // rows to be evicted, its low rows fresh for the ascending pass behind it).  Same bits (tile order only); bench +0.4 % (profiles/r03_bench_rev.txt).  Default 2.
-    const int rev_mode = order.rev;
-    // 1: every launch descending; 2: only the launches that read a LayerNorm / attention output (K <= 1024: in_proj, c_fc, out_proj), c_proj ascending behind the descending c_fc
-    const bool rev = rev_mode == 1 || (rev_mode == 2 && K <= 1024);
     linear_fast_kernel<CK, HAS_BIAS, ACT><<<grid, C::NTHREADS, LDS, s>>>(
         (const half_t*)A, lda, (const half_t*)B, ldb, M, N, K, epi.bias, epi.scale, epi.shift, epi.C, epi.ldc, tiles_n, ntiles, epi.residual,
-        rev ? -1 : (tiles_n >= 8 ? band : 0), pclip_gemm_time_slot());
+        order.descending(K) ? -1 : (tiles_n >= 8 ? order.band : 0), pclip_gemm_time_slot());
     return pclip_check_launch("gemm_f16");
 }
 
@@ -516,6 +483,10 @@ inline int best_cfg(long M, int N, int cus, double* cost_out, bool ragged = fals
 
 // fewer 128x64 tiles than CUs: the latency-oriented ring kernel (defined below), bit-identical to the persistent kernels
 bool small_applies(int M, int N, int cus, bool ragged = false);
+bool small_enabled() {                                      // A/B switch PCLIP_GEMM_SMALL: 0 = the persistent kernels for every shape
+    static const bool on = pclip_env_on("PCLIP_GEMM_SMALL");
+    return on;
+}
 int launch_small_one(const half_t* A, int lda, const half_t* B, int ldb, int M, int N, int K, const LinearEpi& epi, hipStream_t s, bool kt = false);
 
 }  // namespace
@@ -531,8 +502,7 @@ int gemm_dispatch(const half_t* A, int lda, const half_t* B, int ldb, int M, int
     const bool kt = K % pgemm::BK != 0;
     const bool aligned = (!epi.residual || ((epi.act == 5 || epi.act == 6) && ((uintptr_t)epi.residual & 15) == 0)) && epi.ldc % 8 == 0 && ((uintptr_t)epi.C & 15) == 0 &&
                          (!epi.bias || ((uintptr_t)epi.bias & 15) == 0) && (!kt || N % 8 == 0);
-    static const bool small_on = !(getenv("PCLIP_GEMM_SMALL") && getenv("PCLIP_GEMM_SMALL")[0] == '0');
-    if (aligned && forced == -1 && small_on && (epi.act <= 1 || epi.act == 6 || (((uintptr_t)epi.scale | (uintptr_t)epi.shift) & 15) == 0) && small_applies(M, N, cus, kt))
+    if (aligned && forced == -1 && small_enabled() && (epi.act <= 1 || epi.act == 6 || (((uintptr_t)epi.scale | (uintptr_t)epi.shift) & 15) == 0) && small_applies(M, N, cus, kt))
         return launch_small_one(A, lda, B, ldb, M, N, K, epi, s, kt);
     double cost = 1e30;
     int pick = aligned ? best_cfg(M, N, cus, &cost, kt) : -1;
@@ -572,8 +542,7 @@ int gemm_dispatch(const half_t* A, int lda, const half_t* B, int ldb, int M, int
         if (g_use4w < 0) { const char* e = getenv("PCLIP_GEMM_4W"); g_use4w = e ? (atoi(e) != 0) : PCLIP_GEMM_4W_DEFAULT; }
         if (g_use4w && pclip_gemm4w_supports(M, N, K, lda, ldb, epi.ldc, epi.C, epi.bias, epi.residual, epi.act)) {
             const TileOrder& order = tile_order();
-            const bool rev = order.rev == 1 || (order.rev == 2 && K <= 1024);
-            return pclip_gemm4w_launch(A, lda, B, ldb, M, N, K, epi.bias, epi.C, epi.ldc, epi.act, epi.residual, cus, rev ? 1 : 0, N / 256 >= 8 ? order.band : order.band_n, s);
+            return pclip_gemm4w_launch(A, lda, B, ldb, M, N, K, epi.bias, epi.C, epi.ldc, epi.act, epi.residual, cus, order.descending(K) ? 1 : 0, N / 256 >= 8 ? order.band : order.band_n, s);
         }
         return launch_fast_k<CfgBig>(kt, A, lda, B, ldb, M, N, K, epi, cus, s);
     }
@@ -600,8 +569,7 @@ extern "C" int pclip_gemm_f16(const void* A, int lda, const void* B, int ldb, vo
     if (M == 0) return PCLIP_OK;
     LinearEpi epi{(const half_t*)bias, (const half_t*)residual, (half_t*)C, ldc, act, nullptr, nullptr};
     if (residual && bias && act == 0) epi.act = 6;              // fused residual epilogue of the persistent / ring kernels
-    int cus = pclip_device_cus();                          // per device (a process may drive several GPUs): cached per device id in pclip_api.hip
-    if (cus <= 0) cus = 256;
+    const int cus = pclip_cus();                           // per device (a process may drive several GPUs): cached per device id in pclip_api.hip
     static int forced = -1;
     static bool live = false, nosplit = false, init = false;
     if (!init || live) {
@@ -676,35 +644,19 @@ __global__ __launch_bounds__(CfgSplit::NTHREADS, 1) void linear_small_kernel(con
         const int col = n0 + 8 * (tid % C::CPR);
         auto pre = [&](int i, int j, int coff, float4_t v, int rl, int g) {
             if (ACT == 1) return quick_gelu16x4(v);
-            half4_t h;
-            if (ACT == 2 || ACT == 3 || ACT == 5) {         // eval BatchNorm (+ReLU) as in linear_fast_kernel: same roundings
+            if (ACT == 2 || ACT == 3 || ACT == 5) {         // eval BatchNorm (+ReLU)
                 const int n = n0 + wn * (C::BN / C::WN) + j * 32 + coff;
                 const float4_t z4 = {0.f, 0.f, 0.f, 0.f};
                 const float4_t sc = KT && n >= N ? z4 : *reinterpret_cast<const float4_t*>(scale + n), sh = KT && n >= N ? z4 : *reinterpret_cast<const float4_t*>(shift + n);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float y = r16(r16(v[e]) * sc[e] + sh[e]);
-                    if (ACT == 3) y = fmaxf(y, 0.f);
-                    h[e] = (half_t)y;
-                }
-                return h;
+                return bn16x4<ACT == 3>(v, sc, sh);
             }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) h[e] = (half_t)v[e];
-            return h;
+            return cvt16x4(v);
         };
         // slot 0 of the ring is the staging buffer: the epilogue's first barrier comes after every wave's last K-tile
         pgemm::epilogue_f16<C, true>(acc, smem, [](int) {}, pre, [&](int r, int c, int, half8_t h) {
             const bool valid = KT ? m0 + r < M && col < N : m0 + r < M;
             const size_t o = (size_t)(m0 + r) * ldc + col;
-            if ((ACT == 5 || ACT == 6) && valid) {
-                const half8_t rr = ld_half8(residual + o);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float y = r16((float)rr[j] + (float)h[j]);
-                    h[j] = (half_t)(ACT == 5 ? fmaxf(y, 0.f) : y);
-                }
-            }
+            if ((ACT == 5 || ACT == 6) && valid) h = add_residual16x8<ACT == 5>(ld_half8(residual + o), h);
             if (valid) st_half8(Cout + o, h);
         });
         pgemm::time_end(tslot);
@@ -760,14 +712,7 @@ __global__ __launch_bounds__(CfgSplit::NTHREADS, 1) void conv3x3_small_kernel(co
         const int n = n0 + wn * (C::BN / C::WN) + j * 32 + coff;
         const float4_t z4 = {0.f, 0.f, 0.f, 0.f};
         const float4_t sc = TAIL && n >= N ? z4 : *reinterpret_cast<const float4_t*>(scale + n), sh = TAIL && n >= N ? z4 : *reinterpret_cast<const float4_t*>(shift + n);
-        half4_t h;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float y = r16(r16(v[e]) * sc[e] + sh[e]);
-            if (ACT == 3) y = fmaxf(y, 0.f);
-            h[e] = (half_t)y;
-        }
-        return h;
+        return bn16x4<ACT == 3>(v, sc, sh);
     };
     pgemm::epilogue_f16<C, true>(acc, smem, [](int) {}, pre, [&](int r, int, int, half8_t h) {
         if (TAIL ? m0 + r < M && col < N : m0 + r < M) st_half8(Cout + (size_t)(m0 + r) * N + col, h);
@@ -807,48 +752,32 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 
 inline int small_attr() {
     static DevOnce done;
-    if (!done.done()) {
-        const void* fns[] = {(const void*)linear_small_kernel<0>, (const void*)linear_small_kernel<1>, (const void*)linear_small_kernel<2>,
-                             (const void*)linear_small_kernel<3>, (const void*)linear_small_kernel<5>, (const void*)linear_small_kernel<6>,
-                             (const void*)linear_small_kernel<7>, (const void*)linear_small_kernel<8>, (const void*)linear_small_kernel<9>, (const void*)conv3x3_small_kernel<2>, (const void*)conv3x3_small_kernel<3>,
-                             (const void*)linear_small_kernel<0 | ACT_KT>, (const void*)linear_small_kernel<1 | ACT_KT>, (const void*)linear_small_kernel<2 | ACT_KT>,
-                             (const void*)linear_small_kernel<3 | ACT_KT>, (const void*)linear_small_kernel<5 | ACT_KT>, (const void*)linear_small_kernel<6 | ACT_KT>,
-                             (const void*)conv3x3_small_kernel<2 | ACT_KT>, (const void*)conv3x3_small_kernel<3 | ACT_KT>};
-        for (const void* f : fns)
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kSmallLds) != hipSuccess) {
-                pclip_set_error("gemm_f16 (small M): cannot raise the dynamic LDS limit to %d", kSmallLds);
-                return PCLIP_E_LAUNCH;
-            }
-        done.set();
-    }
-    return PCLIP_OK;
+    return pclip_raise_lds(done,
+                           {(const void*)linear_small_kernel<0>, (const void*)linear_small_kernel<1>, (const void*)linear_small_kernel<2>,
+                            (const void*)linear_small_kernel<3>, (const void*)linear_small_kernel<5>, (const void*)linear_small_kernel<6>,
+                            (const void*)linear_small_kernel<7>, (const void*)linear_small_kernel<8>, (const void*)linear_small_kernel<9>, (const void*)conv3x3_small_kernel<2>, (const void*)conv3x3_small_kernel<3>,
+                            (const void*)linear_small_kernel<0 | ACT_KT>, (const void*)linear_small_kernel<1 | ACT_KT>, (const void*)linear_small_kernel<2 | ACT_KT>,
+                            (const void*)linear_small_kernel<3 | ACT_KT>, (const void*)linear_small_kernel<5 | ACT_KT>, (const void*)linear_small_kernel<6 | ACT_KT>,
+                            (const void*)conv3x3_small_kernel<2 | ACT_KT>, (const void*)conv3x3_small_kernel<3 | ACT_KT>},
+                           kSmallLds, "gemm_f16 (small M)");
 }
 
 bool small_applies(int M, int N, int cus, bool ragged) {
     return M > 0 && (ragged || N % CfgSplit::BN == 0) && (long)ceil_div(M, CfgSplit::BM) * col_tiles(N, CfgSplit::BN, ragged) <= cus;
 }
 
-int launch_small_one(const half_t* A, int lda, const half_t* B, int ldb, int M, int N, int K, const LinearEpi& epi, hipStream_t s, bool kt) {
+// KT: K % 64 != 0 — the KT instantiation, ceil(N / BN) column tiles and a K-tail (no split-K either way: S == 1)
+template <bool KT>
+int launch_small_kt(const half_t* A, int lda, const half_t* B, int ldb, int M, int N, int K, const LinearEpi& epi, hipStream_t s) {
     if (int e = small_attr()) return e;
-    const int tiles_n = kt ? ceil_div(N, CfgSplit::BN) : N / CfgSplit::BN, grid = ceil_div(M, CfgSplit::BM) * tiles_n, steps = K / pgemm::BK;
+    constexpr int FLAGS = KT ? ACT_KT : 0;
+    const int tiles_n = KT ? ceil_div(N, CfgSplit::BN) : N / CfgSplit::BN, grid = ceil_div(M, CfgSplit::BM) * tiles_n;
+    const int steps = KT ? ceil_div(K, pgemm::BK) : K / pgemm::BK;
     ++g_gemm_launches;
     unsigned long long* tslot = pclip_gemm_time_slot();
-    if (kt) {                                                   // K % 64 != 0: the KT instantiation (no split-K: S == 1)
-#define PCLIP_SMALL_KT_LAUNCH(ACT)                                                                                                      \
-        linear_small_kernel<ACT | ACT_KT><<<grid, CfgSplit::NTHREADS, kSmallLds, s>>>(A, lda, B, ldb, M, N, K, tiles_n, 1, ceil_div(K, pgemm::BK), nullptr, \
-                                                                                  epi.bias, epi.C, epi.ldc, epi.scale, epi.shift, epi.residual, tslot)
-        if (epi.act == 5) PCLIP_SMALL_KT_LAUNCH(5);
-        else if (epi.act == 6) PCLIP_SMALL_KT_LAUNCH(6);
-        else if (epi.act == 1) PCLIP_SMALL_KT_LAUNCH(1);
-        else if (epi.act == 2) PCLIP_SMALL_KT_LAUNCH(2);
-        else if (epi.act == 3) PCLIP_SMALL_KT_LAUNCH(3);
-        else PCLIP_SMALL_KT_LAUNCH(0);
-#undef PCLIP_SMALL_KT_LAUNCH
-        return pclip_check_launch("gemm_f16 (small M)");
-    }
-#define PCLIP_SMALL_LAUNCH(ACT)                                                                                                          \
-    linear_small_kernel<ACT><<<grid, CfgSplit::NTHREADS, kSmallLds, s>>>(A, lda, B, ldb, M, N, K, tiles_n, 1, steps, nullptr, epi.bias, epi.C, \
-                                                                        epi.ldc, epi.scale, epi.shift, epi.residual, tslot)
+#define PCLIP_SMALL_LAUNCH(ACT)                                                                                                                  \
+    linear_small_kernel<ACT | FLAGS><<<grid, CfgSplit::NTHREADS, kSmallLds, s>>>(A, lda, B, ldb, M, N, K, tiles_n, 1, steps, nullptr, epi.bias, epi.C, \
+                                                                                epi.ldc, epi.scale, epi.shift, epi.residual, tslot)
     if (epi.act == 5) PCLIP_SMALL_LAUNCH(5);
     else if (epi.act == 6) PCLIP_SMALL_LAUNCH(6);
     else if (epi.act == 1) PCLIP_SMALL_LAUNCH(1);
@@ -857,6 +786,22 @@ int launch_small_one(const half_t* A, int lda, const half_t* B, int ldb, int M, 
     else PCLIP_SMALL_LAUNCH(0);
 #undef PCLIP_SMALL_LAUNCH
     return pclip_check_launch("gemm_f16 (small M)");
+}
+int launch_small_one(const half_t* A, int lda, const half_t* B, int ldb, int M, int N, int K, const LinearEpi& epi, hipStream_t s, bool kt) {
+    return kt ? launch_small_kt<true>(A, lda, B, ldb, M, N, K, epi, s) : launch_small_kt<false>(A, lda, B, ldb, M, N, K, epi, s);
+}
+
+// The ring convolution (conv3x3_small_kernel) for a request of a few images.  TAIL: the channel-tail instantiation, ceil(Cout / BN) column tiles.
+template <bool TAIL>
+int launch_conv_small(const void* x, const void* w, int M, int H, int W, int Cin, int Cout, const float* scale, const float* shift, int relu, void* y, hipStream_t s) {
+    if (int e = small_attr()) return e;
+    constexpr int FLAGS = TAIL ? ACT_KT : 0;
+    const int tiles_n = TAIL ? ceil_div(Cout, CfgSplit::BN) : Cout / CfgSplit::BN, grid = ceil_div(M, CfgSplit::BM) * tiles_n;
+    if (relu)
+        conv3x3_small_kernel<3 | FLAGS><<<grid, CfgSplit::NTHREADS, kSmallLds, s>>>((const half_t*)x, (const half_t*)w, H, W, Cin, M, Cout, scale, shift, (half_t*)y, tiles_n);
+    else
+        conv3x3_small_kernel<2 | FLAGS><<<grid, CfgSplit::NTHREADS, kSmallLds, s>>>((const half_t*)x, (const half_t*)w, H, W, Cin, M, Cout, scale, shift, (half_t*)y, tiles_n);
+    return pclip_check_launch("conv3x3_bn (small M)");
 }
 
 struct SplitPlan { int tiles_m, tiles_n, S, steps_per; size_t bytes; };
@@ -883,9 +828,7 @@ inline SplitPlan splitk_plan(int M, int N, int K, int cus) {
 }  // namespace
 
 extern "C" size_t pclip_gemm_splitk_workspace(int M, int N, int K) {
-    int cus = pclip_device_cus();
-    if (cus <= 0) cus = 256;
-    return splitk_plan(M, N, K, cus).bytes;
+    return splitk_plan(M, N, K, pclip_cus()).bytes;
 }
 
 extern "C" int pclip_gemm_splitk_f16(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
@@ -895,9 +838,7 @@ extern "C" int pclip_gemm_splitk_f16(const void* A, int lda, const void* B, int 
     PCLIP_REQUIRE(lda >= K && ldb >= K && ldc >= N && lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0, "pclip_gemm_splitk_f16: bad leading dims");
     PCLIP_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0 && ((uintptr_t)C & 15) == 0 && (!bias || ((uintptr_t)bias & 15) == 0) &&
                       ((uintptr_t)ws & 15) == 0, "pclip_gemm_splitk_f16: operands must be 16-byte aligned");
-    int cus = pclip_device_cus();
-    if (cus <= 0) cus = 256;
-    const SplitPlan pl = splitk_plan(M, N, K, cus);
+    const SplitPlan pl = splitk_plan(M, N, K, pclip_cus());
     PCLIP_REQUIRE(pl.S >= 2, "pclip_gemm_splitk_f16: shape M=%d N=%d K=%d is not a split-K shape (pclip_gemm_splitk_workspace == 0)", M, N, K);
     if (ws_bytes < pl.bytes) { pclip_set_error("pclip_gemm_splitk_f16: workspace %zu < %zu", ws_bytes, pl.bytes); return PCLIP_E_WORKSPACE; }
     hipStream_t s = (hipStream_t)stream;
@@ -927,9 +868,7 @@ extern "C" int pclip_gemm_bn_res_f16(const void* A, int lda, const void* B, int 
     PCLIP_REQUIRE(((uintptr_t)scale & 15) == 0 && ((uintptr_t)shift & 15) == 0, "pclip_gemm_bn_res_f16: scale / shift must be 16-byte aligned");
     if (M == 0) return PCLIP_OK;
     LinearEpi epi{nullptr, (const half_t*)residual, (half_t*)C, ldc, 5, scale, shift};
-    int cus = pclip_device_cus();
-    if (cus <= 0) cus = 256;
-    return gemm_dispatch((const half_t*)A, lda, (const half_t*)B, ldb, M, N, K, epi, cus, bn_forced_cfg(), true, (hipStream_t)stream);
+    return gemm_dispatch((const half_t*)A, lda, (const half_t*)B, ldb, M, N, K, epi, pclip_cus(), bn_forced_cfg(), true, (hipStream_t)stream);
 }
 
 extern "C" int pclip_gemm_bn_f16(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
@@ -940,10 +879,8 @@ extern "C" int pclip_gemm_bn_f16(const void* A, int lda, const void* B, int ldb,
     PCLIP_REQUIRE(lda >= K && ldb >= K && ldc >= N && lda % 8 == 0 && ldb % 8 == 0, "pclip_gemm_bn_f16: bad leading dims");
     if (M == 0) return PCLIP_OK;
     LinearEpi epi{nullptr, nullptr, (half_t*)C, ldc, relu ? 3 : 2, scale, shift};
-    int cus = pclip_device_cus();
-    if (cus <= 0) cus = 256;
     const bool strips_ok = N % 4 == 0 && ((uintptr_t)scale & 15) == 0 && ((uintptr_t)shift & 15) == 0;
-    return gemm_dispatch((const half_t*)A, lda, (const half_t*)B, ldb, M, N, K, epi, cus, strips_ok ? bn_forced_cfg() : -2, true, (hipStream_t)stream);
+    return gemm_dispatch((const half_t*)A, lda, (const half_t*)B, ldb, M, N, K, epi, pclip_cus(), strips_ok ? bn_forced_cfg() : -2, true, (hipStream_t)stream);
 }
 
 namespace {
@@ -954,14 +891,7 @@ int launch_conv2(const void* x, const void* w, int B, int H, int W, int Cin, int
     static DevOnce attr;
     constexpr int LDS = C::LDS_BYTES + 2 * 2 * C::BN * 4;
     using CK = std::conditional_t<TAIL, pgemm::Tail<C>, C>;
-    const void* fn = (const void*)conv3x3_fast_kernel<CK, ACT>;
-    if (!attr.done()) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-            pclip_set_error("pclip_conv3x3_bn_f16: cannot raise the dynamic LDS limit to %d", LDS);
-            return PCLIP_E_LAUNCH;
-        }
-        attr.set();
-    }
+    if (int e = pclip_raise_lds(attr, {(const void*)conv3x3_fast_kernel<CK, ACT>}, LDS, "pclip_conv3x3_bn_f16")) return e;
     const int M = B * H * W, tiles_m = ceil_div(M, C::BM), tiles_n = TAIL ? ceil_div(Cout, C::BN) : Cout / C::BN, ntiles = tiles_m * tiles_n;
     conv3x3_fast_kernel<CK, ACT><<<ntiles < slots ? ntiles : slots, C::NTHREADS, LDS, s>>>(
         (const half_t*)x, (const half_t*)w, H, W, Cin, M, Cout, scale, shift, (half_t*)y, tiles_n, ntiles);
@@ -979,18 +909,8 @@ int launch_conv(const void* x, const void* w, int B, int H, int W, int Cin, int 
 int conv3x3_tail_dispatch(const void* x, const void* w, int B, int H, int W, int Cin, int Cout, const float* scale, const float* shift, int relu,
                           void* y, int cus, hipStream_t s) {
     const int M = B * H * W;
-    static const bool small_on = !(getenv("PCLIP_GEMM_SMALL") && getenv("PCLIP_GEMM_SMALL")[0] == '0');
-    if (small_on && small_applies(M, Cout, cus, true)) {                        // a request of a few images: the ring kernel
-        if (int e = small_attr()) return e;
-        const int tiles_n = ceil_div(Cout, CfgSplit::BN), grid = ceil_div(M, CfgSplit::BM) * tiles_n;
-        if (relu)
-            conv3x3_small_kernel<3 | ACT_KT><<<grid, CfgSplit::NTHREADS, kSmallLds, s>>>((const half_t*)x, (const half_t*)w, H, W, Cin, M, Cout, scale, shift,
-                                                                                   (half_t*)y, tiles_n);
-        else
-            conv3x3_small_kernel<2 | ACT_KT><<<grid, CfgSplit::NTHREADS, kSmallLds, s>>>((const half_t*)x, (const half_t*)w, H, W, Cin, M, Cout, scale, shift,
-                                                                                   (half_t*)y, tiles_n);
-        return pclip_check_launch("conv3x3_bn (small M)");
-    }
+    if (small_enabled() && small_applies(M, Cout, cus, true))                   // a request of a few images: the ring kernel
+        return launch_conv_small<true>(x, w, M, H, W, Cin, Cout, scale, shift, relu, y, s);
     double cost;
     const int pick = best_cfg(M, Cout, cus, &cost, true, (1u << 0) | (1u << 1) | (1u << 3) | (1u << 4));
     if (pick == 1) return launch_conv<CfgWide, true>(x, w, B, H, W, Cin, Cout, scale, shift, relu, y, cus, s);
@@ -1015,8 +935,7 @@ extern "C" int pclip_conv3x3_bn_f16(const void* x, const void* w, const void* ze
     PCLIP_REQUIRE(((uintptr_t)scale & 15) == 0 && ((uintptr_t)shift & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)x & 15) == 0,
                   "pclip_conv3x3_bn_f16: pointers must be 16-byte aligned");
     if (B == 0) return PCLIP_OK;
-    int cus = pclip_device_cus();
-    if (cus <= 0) cus = 256;
+    const int cus = pclip_cus();
     hipStream_t s = (hipStream_t)stream;
     // the gather addresses the activations through a buffer descriptor with 32-bit offsets: a larger batch goes in slices of whole images (same kernels, same bits)
     const long per_image = (long)H * W * Cin * 2;
@@ -1037,18 +956,8 @@ extern "C" int pclip_conv3x3_bn_f16(const void* x, const void* w, const void* ze
         return pclip_conv3x3_strip_launch(x, w, B, H, W, Cin, Cout, scale, shift, relu, y, cus, s, 1);
     if (Cout == 32)                                                             // the stem's 32 -> 32 convolution: 256 x 32 tiles
         return launch_conv<CfgThin>(x, w, B, H, W, Cin, Cout, scale, shift, relu, y, 2 * cus, s);
-    static const bool small_on = !(getenv("PCLIP_GEMM_SMALL") && getenv("PCLIP_GEMM_SMALL")[0] == '0');
-    if (small_on && small_applies(B * H * W, Cout, cus)) {                     // a request of a few images: the ring kernel
-        if (int e = small_attr()) return e;
-        const int tiles_n = Cout / CfgSplit::BN, grid = ceil_div(B * H * W, CfgSplit::BM) * tiles_n;
-        if (relu)
-            conv3x3_small_kernel<3><<<grid, CfgSplit::NTHREADS, kSmallLds, s>>>((const half_t*)x, (const half_t*)w, H, W, Cin,
-                                                                           B * H * W, Cout, scale, shift, (half_t*)y, tiles_n);
-        else
-            conv3x3_small_kernel<2><<<grid, CfgSplit::NTHREADS, kSmallLds, s>>>((const half_t*)x, (const half_t*)w, H, W, Cin,
-                                                                           B * H * W, Cout, scale, shift, (half_t*)y, tiles_n);
-        return pclip_check_launch("conv3x3_bn (small M)");
-    }
+    if (small_enabled() && small_applies(B * H * W, Cout, cus))                // a request of a few images: the ring kernel
+        return launch_conv_small<false>(x, w, B * H * W, H, W, Cin, Cout, scale, shift, relu, y, s);
     double cost;
     int pick = best_cfg((long)B * H * W, Cout, cus, &cost);
     if (pick == 4 || pick < 0) pick = 3;                        // the 4-wave thin tile has no gather variant; Cout % 64 == 0 always fits 256x64

@@ -251,9 +251,7 @@ extern "C" int pclip_cosine_logits_f16(const void* a, int lda, int M, const void
     const int npanels = ceil_div(M, 16 * RF), ncb = ceil_div(T, 64);
     int ysplit = 1;                                       // the logits alone: few panels share the column blocks between workgroups (a row's bits do not depend on it)
     if (!fused) {
-        int cus = pclip_device_cus();
-        if (cus <= 0) cus = 256;
-        ysplit = ceil_div(2 * cus, npanels);
+        ysplit = ceil_div(2 * pclip_cus(), npanels);
         const int ymax = ceil_div(ncb, 4);
         ysplit = ysplit > ymax ? ymax : ysplit;
         ysplit = ysplit > 65535 ? 65535 : ysplit;
@@ -277,13 +275,7 @@ extern "C" int pclip_cosine_logits_f16(const void* a, int lda, int M, const void
 #define PCLIP_LG(NCH, RFV, KM)                                                                                                                     \
     do {                                                                                                                                         \
         static DevOnce attr;                                                                                                                     \
-        if (!attr.done()) {                                                                                                                      \
-            if (hipFuncSetAttribute((const void*)cosine_logits_kernel<NCH, RFV, KM>, hipFuncAttributeMaxDynamicSharedMemorySize, LG_LDS_MAX) != hipSuccess) { \
-                pclip_set_error("%s: cannot raise the dynamic LDS limit to %d", fn, LG_LDS_MAX);                                                 \
-                return PCLIP_E_LAUNCH;                                                                                                           \
-            }                                                                                                                                    \
-            attr.set();                                                                                                                          \
-        }                                                                                                                                        \
+        if (int e = pclip_raise_lds(attr, {(const void*)cosine_logits_kernel<NCH, RFV, KM>}, LG_LDS_MAX, fn)) return e;                          \
         cosine_logits_kernel<NCH, RFV, KM><<<grid, 256, lds, s>>>((const half_t*)a, lda, M, bw, ldbw, T, D, scale, (flags & PCLIP_LOGITS_NORMALIZE_A) ? 1 : 0, \
                                                              (half_t*)logits, ldl, argmax, (half_t*)topk_v, topk_i, k, keff);                   \
     } while (0)

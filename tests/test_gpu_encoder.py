@@ -1047,10 +1047,10 @@ def test_clip_load_runs_on_gpu(tmp_path):
 
 
 @pytest.mark.parametrize("M,N,K", [(50432, 768, 768), (197, 768, 3072), (8, 768, 768), (1024, 768, 3072), (3000, 512, 2048), (777, 1024, 64),
-                                   (20000, 1024, 256), (257, 100, 128)])
+                                   (20000, 1024, 256), (257, 100, 128), (130, 72, 72)])
 def test_gemm_residual_epilogue_in_place(ops, M, N, K):
     """`x += linear(a)` of a transformer block (clip/model.py:188-189) as the epilogue of the GEMM (persistent kernels incl. the row
-    split, the ring kernel for small M, the generic kernel for ragged N), with the output written over the residual operand:
+    split, the ring kernel for small M — (130, 72, 72): its K-tail instantiation, a partial row tile and a ragged column tile —, the generic kernel for ragged N), with the output written over the residual operand:
     bit-identical to the GEMM followed by a separate fp16 add, and to the fused add + LayerNorm pass it replaces."""
     g = torch.Generator(device="cuda").manual_seed(M + N + K)
     a = (torch.randn(M, K, device="cuda", generator=g) * 0.5).half()
