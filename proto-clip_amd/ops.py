@@ -537,8 +537,9 @@ def gemm(a, w, bias=None, act: int = 0, residual=None, out=None):
 
 
 def gemm4w(a, w, bias=None, act: int = 0, residual=None, out=None, var: int = 0):
-    """ops.gemm on the four-wave asm-loop kernel explicitly (csrc/pclip_gemm4w.hip; ops.gemm routes its 256 x 256 tiles there by itself).  var: 0 product loop,
-    1 race-stress build, 6 the no-epilogue ablation (stores nothing), 8 the stamped diagnostic build (pclip_gemm4w_stamp_buffer).  Raises PclipError for shapes outside the kernel (N % 256, K % 64, K >= 192)."""
+    """ops.gemm on the four-wave asm-loop kernel explicitly (csrc/pclip_gemm4w.hip; ops.gemm routes its 256 x 256 tiles there by itself).  var: the kernel build — 0 product,
+    1 race-stress (its own K-loop statement), 6 the product loop without the epilogue (stores nothing), 8 the product loop with time stamps (pclip_gemm4w_stamp_buffer);
+    6 and 8 need a bias, without one they run 0.  Raises PclipError for shapes outside the kernel (N % 256, K % 64, K >= 192)."""
     require_cuda(a, w)
     M, K = a.shape
     N = w.shape[0]

@@ -1,7 +1,7 @@
 """CPU check of the generated four-wave K-loop (tools/gen_gemm4w.py -> csrc/pclip_gemm4w_loop.inc): tools/sim_gemm4w.py interprets one wave's instruction
 stream and checks the ring protocol event by event — piece order / addresses, RAW (counted vmcnt + barrier before every fragment read), WAR (lgkmcnt(0) +
 barrier before a slot is refilled), the M0 wait state, fragment / accumulator pairing and k order — for every tail variant, every ring phase across chained
-output tiles, the race-stress build and the schedule experiments; mutations of the stream must be caught; the committed .inc is what the generator emits."""
+output tiles and the race-stress build; mutations of the stream must be caught; the committed .inc is what the generator emits."""
 import os
 import subprocess
 import sys
@@ -15,6 +15,9 @@ import sim_gemm4w  # noqa: E402
 
 
 def test_protocol_holds_for_every_variant_and_tile_count():
+    """VARIANTS holds the two instruction streams that exist, the product loop and its race-stress build: 2 x 6 tile counts x 5 chained tiles = 60 statements.  (It
+    used to list the product stream under two further keys, for the no-epilogue and the stamped kernel builds; those 60 cases re-simulated the identical stream, so
+    every distinct stream is still checked at every tile count and ring phase.)"""
     assert sim_gemm4w.check_all(nts=(3, 4, 5, 6, 12, 48)) == len(gen_gemm4w.VARIANTS) * 6 * 5
 
 

@@ -198,6 +198,37 @@ def test_gemm4w_is_the_eight_wave_kernel_bit_for_bit(ops, M, N, K):
             assert torch.equal(ops.gemm4w(ai, wi, bi, var=var)[:4096], exact)
 
 
+def test_gemm4w_instrument_builds(ops):
+    """The two instrument builds of the four-wave kernel run the product K-loop with different C++ around it.  The stamped build (var 8) must give the product's
+    bits and leave the guard row alone while it fills its stamp buffer; the no-epilogue build (var 6) must store nothing.  One shape that reaches what they can
+    get wrong: 524 tiles over at most 256 workgroups (consecutive tiles per workgroup), 13 K-tiles (the ring phase changes from tile to tile), a ragged last
+    row tile."""
+    M, N, K = 33333, 1024, 832
+    g = torch.Generator(device="cuda").manual_seed(M + 3 * N + K)
+    a = (torch.randn(M, K, device="cuda", generator=g) * 0.5).half()
+    w = (torch.randn(N, K, device="cuda", generator=g) * K ** -0.5).half()
+    bias = torch.randn(N, device="cuda", generator=g).half()
+    res = torch.randn(M, N, device="cuda", generator=g).half()
+    lib = ops._lib.load()
+    stamps = torch.zeros(260, dtype=torch.int32, device="cuda")
+    ops._lib.check(lib.pclip_gemm4w_stamp_buffer(ops._lib.ptr(stamps)), "pclip_gemm4w_stamp_buffer")
+    try:
+        for act, b, r in ((0, bias, None), (1, bias, None), (0, bias, res)):
+            ref = ops.gemm4w(a, w, b, act, r)
+            stamps.zero_()
+            out = torch.full((M + 1, N), 7.0, device="cuda", dtype=torch.float16)
+            ops.gemm4w(a, w, b, act, r, out[:M], 8)
+            assert torch.equal(out[:M], ref), act
+            assert bool((out[M] == 7.0).all())
+            assert bool((stamps[:64] != 0).any()), act                         # the stamp block of workgroup 0 / wave 0
+            out.fill_(7.0)
+            ops.gemm4w(a, w, b, act, r, out[:M], 6)
+            assert bool((out == 7.0).all()), act
+    finally:
+        torch.cuda.synchronize()
+        lib.pclip_gemm4w_stamp_buffer(None)
+
+
 @pytest.mark.parametrize("M,N,K,band", [(20000, 2304, 768, 3), (20000, 3072, 768, 6), (33333, 1024, 832, 2), (70001, 768, 768, 1), (9000, 3072, 768, 5)])
 def test_gemm4w_band_tile_order_is_bit_identical(ops, M, N, K, band, monkeypatch):
     """PCLIP_GEMM_BAND's tile order in the four-wave kernel (bands of `band` column tiles, row panels fastest inside a band): a permutation of the

@@ -88,7 +88,7 @@ def main():
     ap.add_argument("--no-bench", action="store_true")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--imgs", type=int, default=1024)
-    ap.add_argument("--variants", default="", help="comma list of PCLIP_GEMM4W_VAR values timed against variant 0 (same process, interleaved rounds)")
+    ap.add_argument("--variants", default="", help="comma list of `var` values of pclip_gemm4w_var_f16 (1 race-stress, 6 no-epilogue, 8 stamped) timed against the product build 0 (same process, interleaved rounds)")
     args = ap.parse_args()
     if args.variants:
         return variants(args)

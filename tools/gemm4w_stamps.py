@@ -6,7 +6,7 @@ as in the bench (the launch is the bench's own shape, every CU busy).  Prints, p
     k_loop    the asm statement
     drain     statement done -> epilogue's first barrier passed            (MFMA results back, residual requests, LDS barrier)
     slab k    barrier opening interval k -> next                            (stage slab k+1 | read back + store slab k)
-    tail      last interval (stores of slab 3, B'(1) request) -> next tile's loop top
+    tail      last interval (stores of slab 3) -> next tile's loop top
 in microseconds and as a fraction of the tile, + the sum against the launch's time per tile."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

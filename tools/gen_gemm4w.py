@@ -49,27 +49,20 @@ class Ops:
 
 
 class Gen:
-    def __init__(self, dma_spread=6, dma_first=9, read_stride=2, sleep=0, cold=False, b1=False, b1_early=False, first_vm=8):
+    def __init__(self, dma_spread=6, dma_first=9, read_stride=2, sleep=0, cold=False):
         self.lines = []
         self.dma_spread = dma_spread      # MFMAs between two LDS-DMA pieces of a block
         self.dma_first = dma_first        # MFMA index behind which the first piece's M0 write sits
         self.read_stride = read_stride    # MFMAs between two fragment reads
         self.sleep = sleep                # race-stress build: s_sleep jitter around waits (0 = off)
-        self.cold = cold or b1                # statements without MFMAs: the first tile's prefetch (cold) / the next tile's B'(1) out of the epilogue (b1)
-        self.b1 = b1
-        self.b1_early = b1_early              # B(1) is requested by the PREVIOUS tile's epilogue (PCLIP_GEMM4W_B1), not by this statement's first block
-        # counted wait behind the statement's first block: 8 = only A(2) stays in flight; with b1_early on tiles whose last epilogue slab issues exactly eight stores per
-        # wave (bias / QuickGELU tiles: one bounds-checked descriptor, no branch) 24 = those eight stores + the eight bias loads + A(2): B(1) is OLDER than all of them
-        self.first_vm = first_vm
-        cold = self.cold
+        self.cold = cold                  # the statement without MFMAs: a workgroup's first tile's prefetch
         o = Ops()
         if not cold:
             for i in range(8):
                 for j in range(8): o.out(f"acc{i}_{j}", "+a", f"acc.q[{i}][{j}]")
             for k in range(32): o.out(f"fr{k}", "=&v", f"fr[{k}]")
             for k in range(4): o.out(f"vr{k}", "=&v", f"vr[{k}]")
-        if not b1:
-            for k in range(8): o.out(f"nb{k}", "=&v", f"nb[{k}]")
+        for k in range(8): o.out(f"nb{k}", "=&v", f"nb[{k}]")
         for k in range(8): o.out(f"so{k}", "=&s", f"so[{k}]")
         for n in ("cnt", "tmp", "scr"): o.out(n, "=&s", f"st_{n}")
         for n in ("wr", "rda", "rdb"): o.out(n, "+s", f"ring_{n}")
@@ -80,7 +73,7 @@ class Gen:
         if not cold: o.inp("nt", "s", "nt")
         o.inp("wbase", "s", "wbase")
         for n in ("voffa0", "voffa1", "voffb0", "voffb1"): o.inp(n, "v", n)
-        if not b1: o.inp("biasp", "v", "biasp")
+        o.inp("biasp", "v", "biasp")
         if not cold:
             o.inp("lanea", "v", "lanea"); o.inp("laneb", "v", "laneb")
         self.ops = o
@@ -206,21 +199,8 @@ class Gen:
         self.jitter(7)
         e("s_waitcnt vmcnt(8)")
 
-    def b1_plain(self):
-        """B'(1) of the next output tile into the slot the epilogue has just finished with (issued from the epilogue, one interval before it ends)"""
-        e = self.e
-        e("s_nop 4")
-        for ins in self.reset_k('B', 1): e(ins)
-        e(self.m0_base())
-        for p in range(8):
-            e(self.dma_m0(p)); e("s_nop 0"); e(self.dma_load('B', p, nxt=True))
-        for ins in self.ring_next_wr(): e(ins)
-
     def generate(self):
         self.lines = []
-        if self.b1:
-            self.b1_plain()
-            return self.lines
         if self.cold:
             self.prefetch_plain()
             return self.lines
@@ -228,15 +208,15 @@ class Gen:
         e("s_nop 4")                                            # SGPR operands fresh from v_readfirstlane -> buffer / global instructions
         # next tile's bias fragment (the caller turns it into the next accumulators' initial value): older than every wait below
         self.bias_loads()
-        # A(0), B(0), A(1) were requested by the previous statement (and B(1) by the epilogue behind it): B continues at K-tile 1 (2), A at K-tile 2
-        for ins in self.reset_k('A', 2) + self.reset_k('B', 2 if self.b1_early else 1): e(ins)
+        # A(0), B(0), A(1) were requested by the previous statement: B continues at K-tile 1, A at K-tile 2
+        for ins in self.reset_k('A', 2) + self.reset_k('B', 1): e(ins)
         self.set_read_addresses()
         for ins in self.reads(0, 0): e(ins)
         for ins in self.ring_next_rd("rda") + self.ring_next_rd("rdb"): e(ins)            # -> K-tile 1
         e("s_waitcnt lgkmcnt(0)")
-        self.block(buf=0, read_buf=1, read_ks=1, dmas=[('A', False, [])] if self.b1_early else [('B', False, []), ('A', False, [])], salu=[])
+        self.block(buf=0, read_buf=1, read_ks=1, dmas=[('B', False, []), ('A', False, [])], salu=[])
         self.jitter(5)
-        e(f"s_waitcnt vmcnt({self.first_vm}) lgkmcnt(0)")       # K-tile 1 landed (and everything older: the previous tile's output stores), A(2) may fly
+        e("s_waitcnt vmcnt(8) lgkmcnt(0)")                      # K-tile 1 landed (and everything older: the previous tile's output stores), A(2) may fly
         self.jitter(6)
         e("s_barrier")                                          # B(0)
         # ---- steady iterations t = 0 .. nt - 4
@@ -270,35 +250,22 @@ class Gen:
                 f"#define {name}() \\\n    asm volatile( \\\n{body}\n        : {outs} \\\n        : {ins} \\\n        : \"memory\", \"scc\")\n")
 
 
-# Variants compiled side by side (linear4w_kernel<ACT, HAS_BIAS, VAR>, selected per launch by PCLIP_GEMM4W_VAR): 0 = the product loop, 1 = its race-stress build
-# (s_sleep jitter in front of every counted wait and barrier), 2 .. = schedule experiments measured in the same process (tools/gemm4w_check.py --variants)
-# Measured (profiles/r05_gemm4w_variants.txt, same process, interleaved rounds, bit-identical): pieces behind most of the block's fragment reads (first at MFMA 9, every
-# sixth) +0.5 ... +1.7 % over pieces from the first gap; a burst in the first sixteen gaps -2 ... -3 %; spread over the whole block +-0; B'(1) requested out of the previous
-# tile's epilogue (one interval of lead instead of half a K-tile) -0.9 ... -1.5 %.
+# The two schedules that exist (linear4w_kernel<ACT, HAS_BIAS, VAR>; tools/sim_gemm4w.py checks both): 0 = the product loop, 1 = its race-stress build (s_sleep jitter in
+# front of every counted wait and barrier).  The kernel's other builds (no-epilogue ablation, time stamps) use the product loop and differ in the C++ around it.
+# Piece placement, measured (profiles/r05_gemm4w_variants.txt, same process, interleaved rounds, bit-identical): pieces behind most of the block's fragment reads (first
+# at MFMA 9, every sixth) +0.5 ... +1.7 % over pieces from the first gap; a burst in the first sixteen gaps -2 ... -3 %; spread over the whole block +-0.
+# The schedule / epilogue experiments of rounds 5 and 6 are removed: profiles/r05_gemm4w_variants.txt, r05_gemm4w_epilogue.txt, r05_gemm4w_defer.txt.
 VARIANTS = {
     0: dict(),
     1: dict(sleep=3),
-    # 2 .. 5: schedule / epilogue experiments of round 5, measured and removed from the product sources (git history: piece placement from the first gap or later, a burst,
-    #         every gap; B'(1) out of the epilogue with and without a relaxed first wait; batched LDS reads on residual tiles; un-staged 8-byte stores) — all within +-1.5 %
-    #         or slower: profiles/r05_gemm4w_variants.txt, r05_gemm4w_epilogue.txt
-    6: dict(),                                # the product loop WITHOUT the epilogue (nothing is stored): ablation — what a fully hidden epilogue would buy at most
-    8: dict(),                                # the product loop in a kernel that keeps time stamps of its tile phases (tools/gemm4w_stamps.py)
-    # 7 (round 5, removed in round 6): K = 768 unrolled with the previous tile's second half stored from registers under the loop — bit-identical and 5 - 13 % SLOWER in
-    #    every form (profiles/r05_gemm4w_defer.txt: the scattered stores cost the LDS-DMA stream more than the half epilogue they hide)
 }
-B1_EARLY = {v: kw.get("b1_early", False) for v, kw in VARIANTS.items()}
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("-o", default="proto-clip_amd/csrc/pclip_gemm4w_loop.inc")
     a = ap.parse_args()
-    txt = ""
-    for v, kw in VARIANTS.items():
-        txt += Gen(**kw).emit_statement(f"PCLIP_GEMM4W_LOOP_V{v}") + "\n"
-    txt += Gen(cold=True).emit_statement("PCLIP_GEMM4W_COLD") + "\n" + Gen(cold=True, sleep=3).emit_statement("PCLIP_GEMM4W_COLD_STRESS")
-    txt += "\n" + Gen(b1=True).emit_statement("PCLIP_GEMM4W_B1")
-    txt += "\n#define PCLIP_GEMM4W_NVAR %d\n" % (max(VARIANTS) + 1)
-    txt += "#define PCLIP_GEMM4W_HAS_VAR(v) (%s)\n" % " || ".join(f"(v) == {v}" for v in VARIANTS)
-    txt += "#define PCLIP_GEMM4W_B1_EARLY(v) (%s)\n" % (" || ".join(f"(v) == {v}" for v, on in B1_EARLY.items() if on) or "false")
+    txt = "\n".join(Gen(**kw).emit_statement(name) for name, kw in [
+        ("PCLIP_GEMM4W_LOOP", VARIANTS[0]), ("PCLIP_GEMM4W_LOOP_STRESS", VARIANTS[1]),
+        ("PCLIP_GEMM4W_COLD", dict(cold=True)), ("PCLIP_GEMM4W_COLD_STRESS", dict(cold=True, **VARIANTS[1]))])
     open(a.o, "w").write(txt)
     print("wrote", a.o)

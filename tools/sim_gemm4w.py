@@ -96,13 +96,11 @@ def check(gen: Gen, nt: int, wr0=0, rda0=0, rdb0=0x8000, **kw):
     row16a, row16b, wbase = kw.get("row16a", 16 * 768 * 2), kw.get("row16b", 16 * 1024 * 2), kw.get("wbase", 8192)
     ev, S = simulate(gen, nt, wr0, rda0, rdb0, row16a, row16b, wbase)
     cold = gen.cold
-    early = gen.b1_early and not cold
     # ---- expected half-tile stream of this statement
-    if gen.b1: stream = [("B", 1, True)]
-    elif cold: stream = [("A", 0, True), ("B", 0, True), ("A", 1, True)]
+    if cold: stream = [("A", 0, True), ("B", 0, True), ("A", 1, True)]
     else:
-        # B(1) A(2) B(2) A(3) ... B(nt-1) A'(0) B'(0) A'(1); with b1_early B(1) was requested by the previous tile's epilogue
-        stream = ([] if early else [("B", 1, False)]) + [("A", 2, False)] + \
+        # B(1) A(2) B(2) A(3) ... B(nt-1) A'(0) B'(0) A'(1)
+        stream = [("B", 1, False), ("A", 2, False)] + \
                  [x for t in range(2, nt) for x in ([("B", t, False)] + ([("A", t + 1, False)] if t + 1 < nt else []))] + [("A", 0, True), ("B", 0, True), ("A", 1, True)]
     dmas = [e[1] for e in ev if e[0] == "dma"]
     if len(dmas) != 8 * len(stream): raise ProtocolError(f"{len(dmas)} pieces, expected {8 * len(stream)}")
@@ -119,22 +117,19 @@ def check(gen: Gen, nt: int, wr0=0, rda0=0, rdb0=0x8000, **kw):
         slot = (slot + 0x8000) % 0x28000
     if S["wr"] != slot: raise ProtocolError("write position returned")
     if cold: return S["wr"], S["rda"], S["rdb"]
-    # what the statement found in the ring: A(0), B(0), A(1) (and B(1)) in the slots before wr0
-    back = 0x8000 if early else 0
-    if early: slot_of[("B", 1, False)] = (wr0 - 0x8000) % 0x28000
-    slot_of[("A", 1, False)] = (wr0 - back - 0x8000) % 0x28000
-    slot_of[("B", 0, False)] = (wr0 - back - 0x10000) % 0x28000
-    slot_of[("A", 0, False)] = (wr0 - back - 0x18000) % 0x28000
+    # what the statement found in the ring: A(0), B(0), A(1) in the slots before wr0
+    slot_of[("A", 1, False)] = (wr0 - 0x8000) % 0x28000
+    slot_of[("B", 0, False)] = (wr0 - 0x10000) % 0x28000
+    slot_of[("A", 0, False)] = (wr0 - 0x18000) % 0x28000
     if (rda0, rdb0) != (slot_of[("A", 0, False)], slot_of[("B", 0, False)]): raise ProtocolError("entry read positions do not match the write position")
     # ---- walk the events: ordering rules
     # vector-memory ops in issue order: the half-tile of a piece, None for anything else.  At entry the previous statement's A(1) pieces may still be in flight, with the
     # epilogue's output stores behind them
-    issued = [] if cold else [("A", 1, False)] * 8 + [None] * 24 + ([("B", 1, False)] * 8 if early else []) + [None] * 8      # (... + the epilogue's last eight stores)
+    issued = [("A", 1, False)] * 8 + [None] * 32
     landed_visible = {("A", 0, False), ("B", 0, False)}      # published by the previous statement + the caller's barrier
     waited = {("A", 0, False), ("B", 0, False)}              # this wave's pieces have landed (counted wait), not yet published by a barrier
     reads_of = {}                                            # slot -> state of its last read: "pending" (issued), "done" (behind lgkmcnt(0)), "free" (behind a barrier after that)
-    occupant = {v: k for k, v in slot_of.items() if not k[2]}
-    occupant = {slot_of[k]: k for k in [("A", 0, False), ("B", 0, False), ("A", 1, False)] + ([("B", 1, False)] if early else [])}
+    occupant = {slot_of[k]: k for k in [("A", 0, False), ("B", 0, False), ("A", 1, False)]}
     ndma = 0
     frag_src = {}                                            # fragment register -> (op, t, ks, idx)
     mfma_seen = {}
@@ -223,7 +218,6 @@ def check_all(variants=None, nts=(3, 4, 5, 6, 7, 12, 13, 48)):
             wr, rda, rdb = check(Gen(cold=True), 0, wr0=0)
             # chain five statements: the ring phase advances by 2 nt mod 5 from tile to tile
             for _ in range(5):
-                if kw.get("b1_early", False): wr, _, _ = check(Gen(b1=True), 0, wr0=wr)          # out of the previous tile's epilogue (the first tile's: behind the cold prefetch)
                 wr, rda, rdb = check(Gen(**kw), nt, wr0=wr, rda0=rda, rdb0=rdb)
                 n += 1
     return n
