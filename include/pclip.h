@@ -211,6 +211,51 @@ int pclip_cosine_ce_backward_f16(const void* a, int lda, int M, const void* b, i
 #define PCLIP_CE_SYMMETRIC 0x4
 #define PCLIP_CE_LABELS_I64 0x8
 
+/* ---- Tip-Adapter's cache logits (Tip-Adapter main.py: run_tip_adapter / search_hp; the baseline the Proto-CLIP tables compare against) ------------- */
+
+/* logit[q, n] = r16( c[q, n] + alpha * S[q, n] ): `100. * features @ clip_weights + alpha * exp(-(beta - beta * features @ cache_keys)) @ cache_values`
+ * with the one-hot cache_values given as segments: f [Q, D], keys [NK, D] (rows sorted by class), w [N, D] fp16 rows ldf / ldk / ldw >= D halves apart, all
+ * taken as given; seg [N + 1] int32 on the device, class n owns key rows seg[n] .. seg[n + 1] - 1 (ragged, empty classes allowed: S = 0).
+ *   aff[q, j] = the fp32 matrix-pipe accumulation of f[q, :] . keys[j, :], one accumulator over k = 0, 32, ... — NOT rounded to fp16;
+ *   E[q, j]   = exp(x), x = fma(beta, aff, -beta) in fp32 (the hardware exp2 of x log2 e: relative error within (|x| + 2) 2^-22);
+ *   S[q, n]   = ((E[q, seg[n]] + E[q, seg[n] + 1]) + ...) + E[q, seg[n + 1] - 1]: one fp32 accumulator, strictly in ascending j — an association that does not
+ *               depend on Q, on the rows that travel with q, on N, on the grid or on any routing choice;
+ *   c[q, n]   = what pclip_cosine_logits_f16 (flags 0) accumulates before its final rounding: r16(scale * f) against w, the same k order;
+ *   the last step is ONE fma, v = fma(alpha, S, c) rounded to fp32 (the value logits32 receives), and r16(v) is the only fp16 rounding of the result.
+ * This is deliberately more exact than the upstream fp16 tensor chain, which rounds the affinity, beta * affinity, the difference, the exp and the class sums
+ * (and the product with alpha) to fp16; tests/tip_adapter_ref.py restates that chain as a yardstick (profiles/tip_adapter.txt has both distances to float64).
+ * At alpha == 0 the fp16 logits are those of pclip_cosine_logits_f16, bit for bit.
+ * Outputs, each nullable, at least one: logits [Q, ldl >= N] fp16; logits32 [Q, N] fp32 (dense), the unrounded fma(alpha, S, c), for the training path;
+ * argmax [Q] int32 over the ROUNDED fp16 logits, lowest index among equal logits (the key packing of pclip_cosine_logits_f16).  With only the argmax
+ * requested nothing of size Q x N or Q x NK is written.  A row's logits do not depend on Q or on its neighbours, a column's not on N (nor on the key rows
+ * of later classes); no floating-point atomics: two calls give the same bits.
+ * Envelope: Q >= 1; 1 <= N <= 4096; NK >= 0 (keys may be NULL at NK == 0); D % 64 == 0, D <= 2048; alpha, beta finite and >= 0; ldf, ldk, ldw, ldl multiples
+ * of 8 halves, 16-byte aligned bases.  seg must be non-decreasing from 0 to NK: the caller's binding checks that on the host (ops.tip_segments), the kernel
+ * does not — whatever seg holds, nothing outside the operands is read or written.  No workspace.  Everything else is PCLIP_E_INVALID before any launch. */
+int pclip_tip_logits_f16(const void* f, int ldf, int Q, const void* keys, int ldk, int NK, const int32_t* seg, const void* w, int ldw, int N, int D,
+                         float scale, float alpha, float beta, void* logits, int ldl, float* logits32, int32_t* argmax, pclip_stream_t stream);
+/* Tip-Adapter's search_hp: correct[ib * na + ia] (int32, beta-major: upstream's loop order) = the number of queries whose fused argmax under
+ * (betas[ib], alphas[ia]) equals labels[q] (int32 [Q]; a label outside [0, N) matches nothing) — exactly the counts of nb x na calls of the entry above: the same
+ * aff, E, S, c, fma and key arithmetic.  betas [nb], alphas [na] fp32 on the device, 1 <= na <= 32, nb >= 1; their values are the caller's to check (finite, >= 0).
+ * The affinity tile is formed once per chunk of 2 betas (measured against 1 and 4: profiles/tip_adapter.txt), not once per pair; nothing of size Q x N or Q x NK is written.  `correct` is cleared and then summed with
+ * integer atomics: deterministic.  Same envelope otherwise; no workspace. */
+int pclip_tip_grid_f16(const void* f, int ldf, int Q, const void* keys, int ldk, int NK, const int32_t* seg, const void* w, int ldw, int N, int D,
+                       float scale, const float* betas, int nb, const float* alphas, int na, const int32_t* labels, int32_t* correct, pclip_stream_t stream);
+
+/* Tip-Adapter-F trains the cache keys only: dkeys[j, :] = alpha beta sum_q dL[q, class(j)] E[q, j] f[q, :]  ([NK, D] fp32, dense) for dL [Q, N] fp32 (dense), the
+ * gradient of a loss with respect to the fp32 logits of pclip_tip_logits_f16.  No gradient is produced for f, w, alpha or beta.  E is recomputed tile by tile with
+ * the forward's arithmetic (fp32 aff, fma, exp): no [Q, NK] tensor is kept from the forward.  G = dL E is formed in fp32 and enters the second matrix product rounded
+ * to fp16 under an exact power-of-two scaling 2^s taken from max |dL| (2^s max |dL| in (2^13, 2^14]: relative unit 2^-11 for |G| >= 2^-27 max |dL|, an absolute
+ * 2^-38 max |dL| below; a loss scaled by a power of two moves s with it; E <= 2 is assumed, as normalised features and keys give, so that 2^s G stays inside
+ * fp16); the sum over q is fp32 in index order; alpha beta 2^-s multiply in fp32 at the end.
+ * Deterministic (no atomics on floating point), and a key row's gradient does not depend on the other key rows or on NK.  Rows of dkeys are written for
+ * j < NK only.  Every workgroup walks all Q queries: meant for training batches, not for a 50 000-row split.
+ * Envelope of pclip_tip_logits_f16 (Q >= 1, 1 <= N <= 4096, NK >= 0, D % 64 == 0, D <= 2048, alpha, beta finite and >= 0, strides multiples of 8 halves, 16-byte
+ * aligned f, keys, dkeys, ws); seg as there (checked by the caller's binding).  ws: pclip_workspace_bytes(PCLIP_OP_TIP_BACKWARD, Q, NK, D) (PCLIP_E_WORKSPACE if
+ * smaller).  Everything else is PCLIP_E_INVALID before any launch. */
+int pclip_tip_keys_backward_f16(const void* f, int ldf, int Q, const void* keys, int ldk, int NK, const int32_t* seg, int N, int D, float alpha, float beta,
+                                const float* dL, float* dkeys, void* ws, size_t ws_bytes, pclip_stream_t stream);
+
 /* (alpha, beta) grid, main.py:142-146, 187-199, 419-430: from the two distance matrices evaluate all
  * na*nb pairs and accumulate correct[ia*nb + ib] += #{q : argmax_n p == labels[q]} (int32, the
  * caller zeroes it; lowest-index tie rule).  Replaces 3*na*nb `P` calls + host syncs. */
@@ -616,6 +661,7 @@ int pclip_preprocess_u8(const void* const* srcs, const int32_t* desc, int B, int
 #define PCLIP_OP_LOGITS 4 /* Q = M, N = T */
 #define PCLIP_OP_COSINE_CE 5          /* Q = M, N = T: normalised rows of b, per-panel column partials, target logits: O(T D + panels T + M) */
 #define PCLIP_OP_COSINE_CE_BACKWARD 6 /* Q = M, N = T: the walked operand normalised and transposed, for either direction: O(max(M, T) D) */
+#define PCLIP_OP_TIP_BACKWARD 7       /* N = NK, the key rows: the queries transposed, a class per key row, the largest |dL|: O(Q D + NK) */
 size_t pclip_workspace_bytes(int op, int Q, int N, int D);
 
 #ifdef __cplusplus

@@ -10,12 +10,13 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpclip.so")
 
-OP_SQDIST, OP_CLASSIFY, OP_ADAPTER_FC, OP_LOGITS, OP_COSINE_CE, OP_COSINE_CE_BACKWARD = 1, 2, 3, 4, 5, 6
+OP_SQDIST, OP_CLASSIFY, OP_ADAPTER_FC, OP_LOGITS, OP_COSINE_CE, OP_COSINE_CE_BACKWARD, OP_TIP_BACKWARD = 1, 2, 3, 4, 5, 6, 7
 LOGITS_NORMALIZE_A, LOGITS_NORMALIZE_B = 0x1, 0x2          # flags of pclip_cosine_logits_f16
 CE_NORMALIZE_A, CE_NORMALIZE_B, CE_SYMMETRIC, CE_LABELS_I64 = 0x1, 0x2, 0x4, 0x8          # flags of pclip_cosine_ce_f16 / pclip_cosine_ce_backward_f16
 # routing flags of pclip_classify_ex_f16 / pclip_classify_route_ex (include/pclip.h)
 CLASSIFY_NO_SMALL, CLASSIFY_NO_MID, CLASSIFY_FORCE_MID, CLASSIFY_NO_PANELS, CLASSIFY_FORCE_PANELS = 0x1, 0x2, 0x4, 0x8, 0x10
 CLASSIFY_PANEL_TWO_PASS, CLASSIFY_PANEL_FORCE_SECOND, CLASSIFY_PANEL_EXACT = 0x20, 0x40, 0x80
+TIP_MAX_ALPHAS, TIP_MAX_CLASSES, TIP_MAX_D = 32, 4096, 2048                                # envelope of pclip_tip_logits_f16 / pclip_tip_grid_f16
 # pclip_tower_grad_sumsq / pclip_tower_optim_finish / pclip_tower_adamw: chunk length, table row / state block sizes, row flags
 TOWER_CHUNK, TOWER_ROW_BYTES, TOWER_STATE_BYTES = 4096, 64, 64
 TOWER_PARAM_F16, TOWER_GRAD_F16, TOWER_ALIGNED, TOWER_DECAY = 0x1, 0x2, 0x4, 0x8
@@ -57,6 +58,9 @@ _SIGS = {
     "pclip_cosine_logits_f16": [_P, c_int, c_int, _P, c_int, c_int, c_int, c_float, c_int, _P, c_int, _P, _P, _P, c_int, _P, c_size_t, _P],
     "pclip_cosine_ce_f16": [_P, c_int, c_int, _P, c_int, c_int, c_int, c_float, c_int, _P, _P, _P, _P, _P, _P, c_size_t, _P],
     "pclip_cosine_ce_backward_f16": [_P, c_int, c_int, _P, c_int, c_int, c_int, c_float, c_int, _P, _P, _P, c_float, c_int, _P, _P, _P, c_size_t, _P],
+    "pclip_tip_logits_f16": [_P, c_int, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_float, c_float, c_float, _P, c_int, _P, _P, _P],
+    "pclip_tip_grid_f16": [_P, c_int, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_float, _P, c_int, _P, c_int, _P, _P, _P],
+    "pclip_tip_keys_backward_f16": [_P, c_int, c_int, _P, c_int, c_int, _P, c_int, c_int, c_float, c_float, _P, _P, _P, c_size_t, _P],
     "pclip_hp_sweep": [_P, _P, _P, c_int, c_int, c_int, _P, _P, c_int, _P, c_int, _P, _P],
     "pclip_adapter_fc_f16": [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_float, c_float, c_int, _P, _P, _P,
                              c_size_t, _P],

@@ -83,6 +83,26 @@ class AdapterFcFn(torch.autograd.Function):
         return dx, _like(dw1, w1), _like(dg1, g1), _like(db1, g1), _like(dw2, w2), _like(dg2, g2), _like(db2, g2)
 
 
+class TipLogitsFn(torch.autograd.Function):
+    """Tip-Adapter-F's logits `100. * features @ clip_weights + alpha * exp(-(beta - beta * features @ keys^T)) @ cache_values` as fp32 [Q, N] (nothing rounded to
+    fp16, unlike the inference call), differentiable in the KEY ROWS [NK, D] only — upstream trains nothing else.  backward = pclip_tip_keys_backward_f16, which
+    recomputes the exponentials: only the operands are saved."""
+
+    @staticmethod
+    def forward(ctx, key_rows, features, seg, clip_rows, alpha, beta):
+        ctx.alpha, ctx.beta = float(alpha), float(beta)
+        ctx.save_for_backward(key_rows, features, seg)
+        return ops.tip_logits(features, key_rows, seg, clip_rows, alpha, beta, want_logits=False, want_f32=True, layout="nd")[1]
+
+    @staticmethod
+    def backward(ctx, g):
+        key_rows, features, seg = ctx.saved_tensors
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[3]:
+            raise NotImplementedError("TipLogitsFn: only the cache keys get a gradient (features and clip_weights are constants of Tip-Adapter-F)")
+        dk = ops.tip_keys_backward(features, key_rows, seg, g.float().contiguous(), ctx.alpha, ctx.beta, layout="nd")
+        return _like(dk, key_rows), None, None, None, None, None
+
+
 class PFn(torch.autograd.Function):
     """utils.P (utils.py:225-244) on fp32 operands: exact-fp32 MFMA distances + softmax fusion; backward through both softmaxes
     (pclip_fuse_probs_backward) and cdist(...)**2:  dq = sum_c 2 G[q,c] (q - z_c),  dz_c = sum_q 2 G[q,c] (z_c - q)."""

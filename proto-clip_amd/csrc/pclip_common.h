@@ -21,6 +21,7 @@ typedef float float16_t __attribute__((ext_vector_type(16)));
 void pclip_set_error(const char* fmt, ...);
 int pclip_check_launch(const char* what);
 size_t pclip_cosine_ce_workspace(int backward, int M, int T, int D);   // pclip_cosine_ce.hip, behind pclip_workspace_bytes
+size_t pclip_tip_workspace(int Q, int NK, int D);                      // pclip_tip.hip, behind pclip_workspace_bytes
 #define PCLIP_REQUIRE(cond, ...)              \
     do {                                      \
         if (!(cond)) {                        \

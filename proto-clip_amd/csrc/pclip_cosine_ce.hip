@@ -85,21 +85,6 @@ __global__ __launch_bounds__(256) void ce_norm_rows_kernel(const half_t* __restr
     }
 }
 
-// y [D][ldt] = x^T, 64 x 64 tiles through LDS; rows R .. ldt - 1 of x read as zeros (ldt = R rounded up to 64: every column of y is written)
-__global__ __launch_bounds__(256) void ce_transpose_kernel(const half_t* __restrict__ x, int ldx, int R, half_t* __restrict__ y, int ldt) {
-    __shared__ half_t tile[64][66];
-    const int r0 = blockIdx.x * 64, d0 = blockIdx.y * 64;
-    for (int i = threadIdx.x; i < 64 * 64; i += 256) {
-        const int r = i >> 6, c = i & 63;
-        tile[r][c] = r0 + r < R ? x[(size_t)(r0 + r) * ldx + d0 + c] : (half_t)0.f;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 64 * 64; i += 256) {
-        const int c = i >> 6, r = i & 63;
-        y[(size_t)(d0 + c) * ldt + r0 + r] = tile[r][c];
-    }
-}
-
 template <int NCH, int RF>
 __global__ __launch_bounds__(64 * CE_FW) void ce_fwd_kernel(const half_t* __restrict__ a, int lda, int M, const half_t* __restrict__ b, int ldb, int T, int D, float scale,
                                                      int norm_a, int symmetric, const void* __restrict__ labels, int lab64, float* __restrict__ lse_row,
@@ -676,7 +661,7 @@ extern "C" int pclip_cosine_ce_backward_f16(const void* a, int lda, int M, const
     }
     half_t* walkT = (half_t*)(wsb + w.wt);
     const int ldt = ce_round64(Rw);
-    ce_transpose_kernel<<<dim3(ldt / 64, D / 64), 256, 0, s>>>(walk, ldw, Rw, walkT, ldt);
+    ce_transpose_kernel<64><<<dim3(ldt / 64, D / 64), 256, 0, s>>>(walk, ldw, Rw, walkT, ldt);
     if (int e = pclip_check_launch("cosine_ce_backward (transpose)")) return e;
 
     const int RF = ce_rf(Ro, D), npanels = ceil_div(Ro, 16 * RF);

@@ -25,25 +25,6 @@ namespace {
 constexpr int LG_PAD = 8;                      // halves between the LDS rows of the panel beyond D
 constexpr int LG_LDS_MAX = 160 * 1024;
 
-__device__ __forceinline__ unsigned logit_key(half_t v, int t) {
-    unsigned b = __builtin_bit_cast(unsigned short, v);
-    if (b == 0x8000u) b = 0;                                                    // -0 == +0: the lower column wins
-    const unsigned o = (b & 0x8000u) ? (~b & 0xFFFFu) : (b | 0x8000u);
-    return (o << 16) | (0xFFFFu - (unsigned)t);
-}
-__device__ __forceinline__ half_t key_value(unsigned key) {
-    const unsigned o = key >> 16;
-    const unsigned b = (o & 0x8000u) ? (o & 0x7FFFu) : (~o & 0xFFFFu);
-    return __builtin_bit_cast(half_t, (unsigned short)b);
-}
-
-// r16(s * v): the fp32 product rounded to fp32, then to fp16 (torch's fp16 tensor times a scalar) — not one fused rounding
-__device__ __forceinline__ half_t scale_r16(float s, half_t v) {
-#pragma clang fp contract(off)
-    const float p = s * (float)v;
-    return (half_t)p;
-}
-
 // rows of `b` normalised into the workspace (dense [R, D])
 template <int NCH>
 __global__ __launch_bounds__(256) void logits_norm_rows_kernel(const half_t* __restrict__ x, int ldx, half_t* __restrict__ y, int R, int D) {

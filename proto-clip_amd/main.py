@@ -131,8 +131,8 @@ def train_proto_clip(cfg, visual_memory_keys, textual_memory_bank, adapter, val_
     return dict(history=history, best_acc=best_acc, best_epoch=best_epoch, trainer=trainer)
 
 
-# per-dataset (search_scale, search_step) constants the reference writes into cfg before a run (main.py:74-103; Tip-Adapter
-# legacy, read by nothing on this path — kept so that a cfg dict leaves run_proto_clip with the same keys)
+# per-dataset (search_scale, search_step) constants the reference writes into cfg before a run (main.py:74-103): Tip-Adapter's
+# search ranges, read by tip_adapter.search_hp; run_proto_clip itself does not use them and keeps them so that a cfg dict leaves it with the same keys
 _SEARCH = {"caltech101": ([12, 5], [200, 20]), "dtd": ([13, 13], [200, 20]), "eurosat": ([12, 10], [200, 20]),
            "fgvc": ([30, 30], [200, 20]), "food101": ([10, 10], [200, 20]), "imagenet": ([7, 3], [200, 20]),
            "oxford_flowers": ([50, 50], [200, 20]), "oxford_pets": ([7, 3], [200, 20]), "stanford_cars": ([20, 10], [200, 20]),

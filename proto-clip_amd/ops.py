@@ -355,6 +355,170 @@ def cosine_cross_entropy_backward(a, b, scale: float, lse_row, lse_col=None, lab
     return (grads[0] if want_a else None), grads[1], ds
 
 
+def _tip_segment_table(t: torch.Tensor, N=None):
+    """The checks and the table of `tip_segments` on whatever device `t` lives on: (seg [N + 1] int32, N).  One host transfer."""
+    if t.dim() == 2:
+        if N is not None and int(N) != t.shape[1]:
+            raise _lib.PclipError(f"tip_segments: cache_values {tuple(t.shape)} has {t.shape[1]} classes, N={N} was given")
+        N = t.shape[1]
+        if N < 1:
+            raise _lib.PclipError(f"tip_segments: cache_values {tuple(t.shape)} has no classes")
+        onehot = (((t == 0) | (t == 1)).all(1) & ((t != 0).sum(1) == 1)).all() if t.shape[0] else torch.ones((), dtype=torch.bool, device=t.device)
+        labels = t.argmax(1) if t.shape[0] else torch.zeros(0, dtype=torch.int64, device=t.device)
+    elif t.dim() == 1:
+        if t.dtype not in (torch.int32, torch.int64):
+            raise _lib.PclipError(f"tip_segments: a label vector must be int32 / int64, got {t.dtype}")
+        onehot, labels = torch.ones((), dtype=torch.bool, device=t.device), t.long()
+    else:
+        raise _lib.PclipError(f"tip_segments: expected one-hot cache_values [NK, N] or labels [NK], got shape {tuple(t.shape)}")
+    NK = labels.shape[0]
+    if NK:
+        ordered = (labels[1:] >= labels[:-1]).all()
+        facts = torch.stack([onehot.long(), ordered.long(), labels.min(), labels.max()]).cpu().tolist()          # the one synchronisation
+    else:
+        facts = [1, 1, 0, 0]
+    if not facts[0]:
+        raise _lib.PclipError("tip_segments: cache_values is not one-hot (every row needs exactly one 1 among zeros; soft cache values are not supported)")
+    if N is None:
+        N = facts[3] + 1
+    N = int(N)
+    if N < 1 or facts[2] < 0 or facts[3] >= N:
+        raise _lib.PclipError(f"tip_segments: labels span [{facts[2]}, {facts[3]}], outside [0, N={N})")
+    if not facts[1]:
+        raise _lib.PclipError("tip_segments: the cache rows are not sorted by class (build_cache_model sorts them; sort keys and values with the same permutation)")
+    # seg[n] = the number of rows whose class is below n: a search in the sorted labels (no second synchronisation, unlike a bincount on the device)
+    seg = torch.searchsorted(labels, torch.arange(N + 1, dtype=labels.dtype, device=t.device)).int()
+    return seg, N
+
+
+def tip_segments(cache_values_or_labels: torch.Tensor, N: int = None) -> torch.Tensor:
+    """Segment offsets of a Tip-Adapter cache: int32 [N + 1] on the device, class n owns key rows seg[n] .. seg[n + 1] - 1 (ragged; empty classes allowed).
+    Takes upstream's one-hot `cache_values` [NK, N] or the label vector [NK]; raises PclipError if a row is not one-hot or the rows are not sorted by class.
+    Synchronises once: compute it once per cache and pass it on (`tip_logits(..., seg)`)."""
+    require_cuda(cache_values_or_labels)
+    return _tip_segment_table(cache_values_or_labels, N)[0]
+
+
+def _tip_coef(what: str, name: str, v) -> float:
+    """alpha / beta as the fp32 number the kernel takes: finite and >= 0."""
+    if isinstance(v, torch.Tensor):
+        if v.requires_grad:
+            raise NotImplementedError(f"{what}: {name} requires grad — no gradient is produced for it (upstream trains only the cache keys)")
+        v = v.item()
+    v = float(np.float32(v))
+    if not math.isfinite(v) or v < 0:
+        raise _lib.PclipError(f"{what}: {name}={v} must be finite and >= 0")
+    return v
+
+
+def _tip_args(what, features, cache_keys, seg, clip_rows, layout, N=None):
+    """Shape and envelope checks first (they need no device), then the device checks: (f, key rows, seg, w, ldf, ldk, ldw, Q, NK, N, D).
+    clip_rows None (the key gradient, which has no zero-shot term): N is given instead."""
+    if layout not in (None, "dn", "nd"):
+        raise _lib.PclipError(f"{what}: layout={layout!r}: expected 'dn' (cache_keys [D, NK], as build_cache_model returns), 'nd' ([NK, D] rows) or None")
+    for name, t in (("features", features), ("cache_keys", cache_keys), ("clip weight rows", clip_rows)):
+        if t is not None and (t.dtype != torch.float16 or t.dim() != 2):
+            raise _lib.PclipError(f"{what}: {name} must be a 2-D float16 tensor, got {t.dtype} {tuple(t.shape)}")
+    Q, D = features.shape
+    if D % 64 or D < 64 or D > _lib.TIP_MAX_D:
+        raise _lib.PclipError(f"{what}: D={D} must be a multiple of 64, <= {_lib.TIP_MAX_D}")
+    if Q < 1:
+        raise _lib.PclipError(f"{what}: no query rows")
+    N = clip_rows.shape[0] if clip_rows is not None else int(N)
+    if clip_rows is not None and clip_rows.shape[1] != D:
+        raise _lib.PclipError(f"{what}: clip weight rows {tuple(clip_rows.shape)} are not [N, D={D}]")
+    if N < 1 or N > _lib.TIP_MAX_CLASSES:
+        raise _lib.PclipError(f"{what}: N={N} must be in [1, {_lib.TIP_MAX_CLASSES}] (the fused argmax's cap)")
+    if layout is None:                                                  # the rule of utils._clip_weight_rows: told from the shape, a square tensor read as upstream's [D, NK]
+        if D not in cache_keys.shape:
+            raise _lib.PclipError(f"{what}: cache_keys {tuple(cache_keys.shape)} matches neither [D={D}, NK] nor [NK, D]")
+        layout = "dn" if cache_keys.shape[0] == D else "nd"
+    if cache_keys.shape[0 if layout == "dn" else 1] != D:
+        raise _lib.PclipError(f"{what}: cache_keys {tuple(cache_keys.shape)} is not {'[D, NK]' if layout == 'dn' else '[NK, D]'} with D={D}")
+    NK = cache_keys.shape[1 if layout == "dn" else 0]
+    if seg.dtype != torch.int32 or seg.dim() != 1 or seg.shape[0] != N + 1 or not seg.is_contiguous():
+        raise _lib.PclipError(f"{what}: seg must be a contiguous int32 tensor of N + 1 = {N + 1} entries (ops.tip_segments), got {seg.dtype} {tuple(seg.shape)}")
+    require_cuda(features, cache_keys, seg, clip_rows)
+    f = _f16_rows(features, f"{what}: features")
+    w = _f16_rows(clip_rows, f"{what}: clip weight rows") if clip_rows is not None else None
+    if NK == 0:
+        keys = None
+    else:
+        keys = transpose(cache_keys) if layout == "dn" else _f16_rows(cache_keys, f"{what}: cache_keys")
+    ldk = keys.stride(0) if NK > 1 else D
+    return f, keys, seg, w, (f.stride(0) if Q > 1 else D), ldk, (w.stride(0) if w is not None and N > 1 else D), Q, NK, N, D
+
+
+def tip_logits(features, cache_keys, seg, clip_rows, alpha, beta, scale: float = 100., want_logits: bool = True, want_f32: bool = False,
+               want_argmax: bool = False, layout=None):
+    """Tip-Adapter's logits `scale * features @ clip_rows^T + alpha * exp(-(beta - beta * features @ keys^T)) @ one_hot` on the fused kernel (pclip_tip_logits_f16):
+    features [Q, D], clip_rows [N, D] fp16; cache_keys upstream's [D, NK] (one `transpose`) or [NK, D] rows (`layout` "dn" / "nd" / None = told from the shape, a
+    square tensor read as [D, NK]); seg from `tip_segments`.  Returns (logits [Q, N] fp16 | None, logits32 [Q, N] fp32 | None, argmax [Q] int32 | None); with the
+    argmax alone no matrix is written.  The fp16 logits are the first N columns of a buffer whose rows are N rounded up to 8 halves apart."""
+    what = "tip_logits"
+    alpha, beta = _tip_coef(what, "alpha", alpha), _tip_coef(what, "beta", beta)
+    if not (want_logits or want_f32 or want_argmax):
+        raise _lib.PclipError(f"{what}: no output requested")
+    f, keys, seg, w, ldf, ldk, ldw, Q, NK, N, D = _tip_args(what, features, cache_keys, seg, clip_rows, layout)
+    dev = f.device
+    ldl = (N + 7) // 8 * 8
+    buf = torch.empty(Q, ldl, dtype=torch.float16, device=dev) if want_logits else None
+    l32 = torch.empty(Q, N, dtype=torch.float32, device=dev) if want_f32 else None
+    am = torch.empty(Q, dtype=torch.int32, device=dev) if want_argmax else None
+    check(_lib.load().pclip_tip_logits_f16(ptr(f), ldf, Q, ptr(keys), ldk, NK, ptr(seg), ptr(w), ldw, N, D, float(np.float32(scale)), alpha, beta,
+                                           ptr(buf), ldl, ptr(l32), ptr(am), stream()), "pclip_tip_logits_f16")
+    return (buf[:, :N] if want_logits else None), l32, am
+
+
+def tip_grid(features, cache_keys, seg, clip_rows, betas, alphas, labels, scale: float = 100., layout=None) -> torch.Tensor:
+    """Tip-Adapter's `search_hp` counts on one launch (pclip_tip_grid_f16): int32 [nb, na] on the device, [ib, ia] = the number of queries whose `tip_logits`
+    argmax under (betas[ib], alphas[ia]) equals their label — exactly what nb x na single calls count.  betas / alphas: sequences of numbers (na <= 32);
+    labels [Q] int32 / int64, one outside [0, N) matches nothing."""
+    what = "tip_grid"
+    betas = [_tip_coef(what, f"betas[{i}]", b) for i, b in enumerate(betas)]
+    alphas = [_tip_coef(what, f"alphas[{i}]", a) for i, a in enumerate(alphas)]
+    if not betas or not alphas or len(alphas) > _lib.TIP_MAX_ALPHAS:
+        raise _lib.PclipError(f"{what}: {len(betas)} betas x {len(alphas)} alphas: at least one of each, at most {_lib.TIP_MAX_ALPHAS} alphas")
+    if labels.dtype not in (torch.int32, torch.int64) or labels.dim() != 1 or labels.shape[0] != features.shape[0]:
+        raise _lib.PclipError(f"{what}: labels must be an int32 / int64 tensor of {features.shape[0]} entries")
+    f, keys, seg, w, ldf, ldk, ldw, Q, NK, N, D = _tip_args(what, features, cache_keys, seg, clip_rows, layout)
+    require_cuda(f, labels)
+    dev = f.device
+    lab = torch.where((labels >= 0) & (labels < N), labels, torch.full_like(labels, -1)).int().contiguous()
+    bt = torch.tensor(betas, dtype=torch.float32).to(dev)
+    at = torch.tensor(alphas, dtype=torch.float32).to(dev)
+    correct = torch.empty(len(betas), len(alphas), dtype=torch.int32, device=dev)
+    check(_lib.load().pclip_tip_grid_f16(ptr(f), ldf, Q, ptr(keys), ldk, NK, ptr(seg), ptr(w), ldw, N, D, float(np.float32(scale)), ptr(bt), len(betas),
+                                         ptr(at), len(alphas), ptr(lab), ptr(correct), stream()), "pclip_tip_grid_f16")
+    return correct
+
+
+def tip_keys_backward(features, cache_keys, seg, dlogits, alpha, beta, layout=None, out: torch.Tensor = None) -> torch.Tensor:
+    """The gradient of a loss with respect to the cache KEY ROWS from its gradient `dlogits` [Q, N] fp32 with respect to the fp32 logits of `tip_logits`
+    (pclip_tip_keys_backward_f16): fp32 [NK, D], dkeys[j] = alpha beta sum_q dlogits[q, class(j)] E[q, j] features[q].  E is recomputed; nothing of the forward is
+    kept.  Nothing else gets a gradient (upstream's Tip-Adapter-F trains the keys only).  cache_keys / layout as in `tip_logits`.
+    out: an optional contiguous float32 [NK, D] tensor (16-byte aligned) that receives the gradient."""
+    what = "tip_keys_backward"
+    alpha, beta = _tip_coef(what, "alpha", alpha), _tip_coef(what, "beta", beta)
+    if dlogits.dtype != torch.float32 or dlogits.dim() != 2 or dlogits.shape[0] != features.shape[0] or dlogits.shape[1] != seg.shape[0] - 1:
+        raise _lib.PclipError(f"{what}: dlogits must be a float32 [Q={features.shape[0]}, N={seg.shape[0] - 1}] tensor, got {dlogits.dtype} {tuple(dlogits.shape)}")
+    N = dlogits.shape[1]
+    f, keys, seg, _, ldf, ldk, _, Q, NK, N, D = _tip_args(what, features, cache_keys, seg, None, layout, N=N)
+    require_cuda(f, dlogits)
+    dl = dlogits.contiguous()
+    if out is None:
+        dkeys = torch.empty(NK, D, dtype=torch.float32, device=f.device)
+    else:
+        if out.dtype != torch.float32 or tuple(out.shape) != (NK, D) or not out.is_contiguous() or not out.is_cuda or out.data_ptr() % 16:
+            raise _lib.PclipError(f"{what}: out must be a contiguous, 16-byte aligned float32 [NK={NK}, D={D}] device tensor")
+        dkeys = out
+    nws = _lib.workspace_bytes(_lib.OP_TIP_BACKWARD, Q, NK, D)
+    ws = _workspace(nws, f.device)
+    check(_lib.load().pclip_tip_keys_backward_f16(ptr(f), ldf, Q, ptr(keys), ldk, NK, ptr(seg), N, D, alpha, beta, ptr(dl), ptr(dkeys), ptr(ws), nws, stream()),
+          "pclip_tip_keys_backward_f16")
+    return dkeys
+
+
 CLASSIFY_ROUTES = ("two stages", "one launch, small N", "one launch, mid N", "fused row panels")
 
 
