@@ -589,6 +589,25 @@ int pclip_colsum_f16(const void* x, int ldx, int R, int C, float* part, int nsli
 int pclip_layernorm_backward_g32_f16(const void* x, int ldx, const float* gamma, const void* dy, int lddy, const void* residual, int ldr,
                                      int R, int D, float eps, void* dx, int lddx, float* part, int nblk, pclip_stream_t stream);
 
+/* ---- learned prompt context (CoOp: context rows trained through the frozen text tower; csrc/pclip_prompt.hip) ---------------- */
+
+/* The embedded prompts of clip/model.py:342-343 with learned rows in place of the token embeddings at positions 1 .. n_ctx:
+ * x [N, L_out, W] fp16, x[n, l] = r16(f32(src) + f32(pos_emb[l])), src = r16(ctx[..][l - 1]) for 1 <= l <= n_ctx and
+ * tok_emb[clamp(tokens[n, l], 0, vocab - 1)] elsewhere (pclip_text_embed_f16's clamp; on a context row holding fp16-exact values its bits).
+ * ctx fp32: [n_ctx, W] shared by all classes, or with class_specific [N, n_ctx, W].  tokens int64 [N, L_tok], L_out <= L_tok: a truncated
+ * assembly reads the full-width token matrix.  pos_emb has at least L_out rows.  W % 8 == 0; operands 16-byte aligned. */
+int pclip_prompt_embed_f16(const int64_t* tokens, int L_tok, const void* tok_emb, const void* pos_emb, const float* ctx, int class_specific,
+                           int n_ctx, int N, int L_out, int W, int vocab, void* x, pclip_stream_t stream);
+
+/* Gradient of that assembly wrt ctx from dx [N * L_out, W] fp16 (the cast of ctx to fp16 is passed through).  class_specific:
+ * dctx [N, n_ctx, W] = f32(dx[n, 1 + j]), exact; part and nslice are ignored.  Shared: dctx [n_ctx, W] = sum over the classes in fp32 in ONE
+ * fixed order — slices of PCLIP_PROMPT_CTX_SLICE consecutive classes summed in class order into part [nslice][n_ctx * W], the slices then summed
+ * in slice order, every sum starting from its first term; nslice must be ceil(N / PCLIP_PROMPT_CTX_SLICE), and part may be NULL when that is 1.
+ * No atomics: two calls give the same bits.  Context rows at 1 + j >= L_out get a zero gradient. */
+#define PCLIP_PROMPT_CTX_SLICE 16
+int pclip_prompt_ctx_grad_f32(const void* dx, int N, int L_out, int n_ctx, int W, int class_specific, float* dctx, float* part, int nslice,
+                              pclip_stream_t stream);
+
 /* One torch.optim.AdamW step (main.py:134-135: eps 1e-4, weight_decay 0.05) on fp16 parameters with fp16 moments, every
  * intermediate rounded to fp16 where the single-tensor implementation materialises an fp16 tensor; step counts from 1. */
 int pclip_adamw_f16(void* p, const void* g, void* m, void* v, size_t n, double lr, double beta1, double beta2, double eps,

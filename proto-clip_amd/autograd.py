@@ -267,9 +267,11 @@ def _bias_grad(dy):
 
 
 class TowerTailFn(torch.autograd.Function):
-    """x [B*L, W] (the residual stream entering the first taped block; a constant) -> features [B, E] through `len(blocks)` residual blocks, the
-    row pick (class token / EOT row), the final LayerNorm and the projection.  Arguments after the bookkeeping: the 12 parameters of every taped
-    block (block order, each in _block_params' order), then ln.weight, ln.bias, proj."""
+    """x [B*L, W] (the residual stream entering the first taped block: a constant, or — learned prompt rows, `PromptEmbedFn` — a tensor on the tape,
+    which then receives the stream gradient that leaves the first block) -> features [B, E] through `len(blocks)` residual blocks, the row pick
+    (class token / EOT row), the final LayerNorm and the projection.  Arguments after the bookkeeping: the 12 parameters of every taped block (block
+    order, each in _block_params' order), then ln.weight, ln.bias, proj.  The backward issues a weight / bias gradient only for a parameter that
+    requires one: a frozen tower under a trainable input pays for none."""
 
     @staticmethod
     def forward(ctx, x, h0, meta, *params):
@@ -277,6 +279,8 @@ class TowerTailFn(torch.autograd.Function):
         nb = (len(params) - 3) // 12
         W = x.shape[1]
         ctx.meta, ctx.nb = meta, nb
+        if ctx.needs_input_grad[0] and nb > 0:                                 # the blocks update the stream in place: a taped input keeps its values
+            x = x.clone()
         tape = []
         h = None
         if nb > 0:
@@ -321,12 +325,16 @@ class TowerTailFn(torch.autograd.Function):
         params = ctx.saved_tensors
         nb = ctx.nb
         grads = [None] * len(params)
+        need = ctx.needs_input_grad[3:]
+        wgrad = lambda k, dy, x: _weight_grad(dy, x) if need[k] else None      # a frozen parameter's gradient is not computed at all
+        bgrad = lambda k, dy: _bias_grad(dy) if need[k] else None
         lnw, lnb, proj = params[-3:]
         g = g.contiguous()
         if g.dtype != torch.float16:
             g = ops.cast_f16(g.float())
         # features = y proj: dproj = y^T g, dy = g proj^T
-        grads[-1] = ops.gemm(ops.transpose(_pad_rows8(ctx.y)), ops.transpose(_pad_rows8(g)))
+        if need[-1]:
+            grads[-1] = ops.gemm(ops.transpose(_pad_rows8(ctx.y)), ops.transpose(_pad_rows8(g)))
         dy = ops.gemm(g, proj)
         gx, dg, db = ops.layernorm_backward_f32(ctx.x_out, lnw, dy)
         grads[-3], grads[-2] = dg, db
@@ -340,17 +348,17 @@ class TowerTailFn(torch.autograd.Function):
             rec = ctx.tape[i]
             o = 12 * i
             # x_out = x_mid + c_proj(f), f = QuickGELU(u), u = c_fc(h2), h2 = ln_2(x_mid)
-            grads[o + 10], grads[o + 11] = _weight_grad(gx, rec["f"]), _bias_grad(gx)
+            grads[o + 10], grads[o + 11] = wgrad(o + 10, gx, rec["f"]), bgrad(o + 11, gx)
             df = ops.gemm(gx, wT(("tail_wT", i, "pr"), wpr))
             u = ops.gemm(rec["h2"], wfc, bfc)                                  # the pre-activation, recomputed (the forward's epilogue keeps only f)
             du = ops.quick_gelu_backward(u, df)
             del u, df
-            grads[o + 8], grads[o + 9] = _weight_grad(du, rec["h2"]), _bias_grad(du)
+            grads[o + 8], grads[o + 9] = wgrad(o + 8, du, rec["h2"]), bgrad(o + 9, du)
             dh2 = ops.gemm(du, wT(("tail_wT", i, "fc"), wfc))
             del du
             gx, grads[o + 6], grads[o + 7] = ops.layernorm_backward_f32(rec["x_mid"], ln2w, dh2, residual=gx)
             # x_mid = x_in + out_proj(a)
-            grads[o + 4], grads[o + 5] = _weight_grad(gx, rec["a"]), _bias_grad(gx)
+            grads[o + 4], grads[o + 5] = wgrad(o + 4, gx, rec["a"]), bgrad(o + 5, gx)
             da = ops.gemm(gx, wT(("tail_wT", i, "out"), wout))
             if rec["picked"]:                                                  # only B rows left the block: zeros on the others
                 full = torch.zeros(B * L, W, dtype=torch.float16, device=gx.device)
@@ -367,14 +375,18 @@ class TowerTailFn(torch.autograd.Function):
                 qkv[sel_rows, :W] = rec["q"]
             dqkv = ops.attention_backward(qkv, da, B, L, heads, causal=causal)
             del qkv, da
-            grads[o + 2], grads[o + 3] = _weight_grad(dqkv, rec["h1"]), _bias_grad(dqkv)
+            grads[o + 2], grads[o + 3] = wgrad(o + 2, dqkv, rec["h1"]), bgrad(o + 3, dqkv)
             dh1 = ops.gemm(dqkv, wT(("tail_wT", i, "in"), win))
             del dqkv
             gx, grads[o + 0], grads[o + 1] = ops.layernorm_backward_f32(rec["x_in"], ln1w, dh1, residual=gx)
-        out = []
-        for p, gr, need in zip(params, grads, ctx.needs_input_grad[3:]):
-            out.append(gr.reshape(p.shape) if need else None)
-        return (None, None, None) + tuple(out)
+        dx = None
+        if ctx.needs_input_grad[0]:                                            # the stream gradient that leaves the first taped block (block 0's ln_1 backward)
+            dx = gx
+            if select is not None and nb == 0:                                 # heads only: the picked rows are all that reached the final LayerNorm
+                dx = torch.zeros(B * L, W, dtype=torch.float16, device=gx.device)
+                dx[sel_rows] = gx
+        out = [gr.reshape(p.shape) if n else None for p, gr, n in zip(params, grads, need)]
+        return (dx, None, None) + tuple(out)
 
 
 def tower_plan(tower_name, blocks, prefix_params, head_params):
@@ -409,3 +421,27 @@ def run_tower_tail(x, h0, blocks, first, B, L, heads, causal, select, sel_rows, 
             raise PclipError(f"{what}: unsupported parameter dtype {p.dtype}")
     meta = (B, L, heads, causal, select, sel_rows, first_token, cache)
     return TowerTailFn.apply(x, h0, meta, *params)
+
+
+# ---- learned prompt context (CoOp): the embedded prompts as a function of the fp32 context rows ---------------------------------------------------
+
+class PromptEmbedFn(torch.autograd.Function):
+    """(ctx, tokens, emb16, pos16, n_ctx, L_out) -> x [N * L_out, W] fp16, the residual stream that enters block 0 of the text tower: the fp32 context
+    rows `ctx` ([n_ctx, W] shared, or [N, n_ctx, W]) at positions 1 .. n_ctx, the token embeddings elsewhere, plus the positional embedding
+    (pclip_prompt_embed_f16).  backward: dctx in fp32 (pclip_prompt_ctx_grad_f32: a fixed summation order over the classes, no atomics); nothing else
+    gets a gradient."""
+
+    @staticmethod
+    def forward(ctx, ctx_rows, tokens, emb16, pos16, n_ctx, L_out):
+        if ctx_rows.shape[-2] != n_ctx:
+            raise PclipError(f"PromptEmbedFn: context {tuple(ctx_rows.shape)} does not hold n_ctx={n_ctx} rows")
+        ctx.shape = (tokens.shape[0], int(L_out), int(n_ctx), ctx_rows.dim() == 3)
+        return ops.prompt_embed(ctx_rows, tokens, emb16, pos16, L_out)
+
+    @staticmethod
+    def backward(ctx, dx):
+        N, L_out, n_ctx, per_class = ctx.shape
+        dx = dx.contiguous()
+        if dx.dtype != torch.float16:
+            dx = ops.cast_f16(dx.float())
+        return ops.prompt_ctx_grad(dx, N, L_out, n_ctx, per_class), None, None, None, None, None

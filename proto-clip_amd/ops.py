@@ -970,6 +970,53 @@ def text_embed(tokens, tok_emb, pos_emb) -> torch.Tensor:
     return x
 
 
+def _prompt_ctx_shape(ctx, N: int, W: int):
+    """(n_ctx, class_specific) of a context tensor: fp32 [n_ctx, W] shared, or [N, n_ctx, W]."""
+    if ctx.dtype != torch.float32:
+        raise _lib.PclipError(f"prompt context must be float32, got {ctx.dtype}")
+    if ctx.dim() not in (2, 3) or ctx.shape[-1] != W or (ctx.dim() == 3 and ctx.shape[0] != N):
+        raise _lib.PclipError(f"prompt context {tuple(ctx.shape)} is neither [n_ctx, {W}] nor [{N}, n_ctx, {W}]")
+    return ctx.shape[-2], ctx.dim() == 3
+
+
+def prompt_embed(ctx, tokens, tok_emb, pos_emb, L_out: int = None) -> torch.Tensor:
+    """Embedded prompts [N * L_out, W] fp16 with the fp32 context rows `ctx` ([n_ctx, W] shared or [N, n_ctx, W]) at positions 1 .. n_ctx and the
+    token embeddings elsewhere, plus the positional embedding (pclip_prompt_embed_f16).  L_out <= tokens.shape[1]: the first L_out positions only."""
+    require_cuda(ctx, tokens, tok_emb, pos_emb)
+    N, L_tok = tokens.shape
+    vocab, W = tok_emb.shape
+    L_out = L_tok if L_out is None else int(L_out)
+    n_ctx, per_class = _prompt_ctx_shape(ctx, N, W)
+    if not 1 <= L_out <= L_tok or pos_emb.shape[0] < L_out or pos_emb.shape[1] != W:
+        raise _lib.PclipError(f"prompt_embed: L_out={L_out} with tokens {tuple(tokens.shape)} and positional rows {tuple(pos_emb.shape)}")
+    tokens = tokens.to(torch.int64).contiguous()
+    ctx, tok_emb, pos_emb = ctx.contiguous(), _f16c(tok_emb), _f16c(pos_emb)
+    x = torch.empty(N * L_out, W, dtype=torch.float16, device=tok_emb.device)
+    check(_lib.load().pclip_prompt_embed_f16(ptr(tokens), L_tok, ptr(tok_emb), ptr(pos_emb), ptr(ctx), int(per_class), n_ctx, N, L_out, W, vocab,
+                                             ptr(x), stream()), "pclip_prompt_embed_f16")
+    return x
+
+
+def prompt_ctx_grad(dx, N: int, L_out: int, n_ctx: int, class_specific: bool = False) -> torch.Tensor:
+    """Gradient of `prompt_embed` wrt the context from dx [N * L_out, W] fp16: fp32 [n_ctx, W] (summed over the classes in one fixed order) or, class
+    specific, [N, n_ctx, W] (pclip_prompt_ctx_grad_f32)."""
+    require_cuda(dx)
+    dx = _f16c(dx)
+    W = dx.shape[1]
+    if dx.shape[0] != N * L_out:
+        raise _lib.PclipError(f"prompt_ctx_grad: dx has {dx.shape[0]} rows, expected N * L_out = {N * L_out}")
+    if class_specific:
+        dctx = torch.empty(N, n_ctx, W, dtype=torch.float32, device=dx.device)
+        part, nslice = None, 0
+    else:
+        dctx = torch.empty(n_ctx, W, dtype=torch.float32, device=dx.device)
+        nslice = (N + _lib.PROMPT_CTX_SLICE - 1) // _lib.PROMPT_CTX_SLICE
+        part = torch.empty(nslice, n_ctx * W, dtype=torch.float32, device=dx.device) if nslice > 1 else None
+    check(_lib.load().pclip_prompt_ctx_grad_f32(ptr(dx), N, L_out, n_ctx, W, int(class_specific), ptr(dctx), ptr(part), nslice, stream()),
+          "pclip_prompt_ctx_grad_f32")
+    return dctx
+
+
 def gather_eot(x, tokens, B: int, L: int, W: int) -> torch.Tensor:
     tokens = tokens.to(torch.int64).contiguous()
     out = torch.empty(B, W, dtype=torch.float16, device=x.device)
