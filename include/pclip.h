@@ -608,6 +608,28 @@ int pclip_prompt_embed_f16(const int64_t* tokens, int L_tok, const void* tok_emb
 int pclip_prompt_ctx_grad_f32(const void* dx, int N, int L_out, int n_ctx, int W, int class_specific, float* dctx, float* part, int nslice,
                               pclip_stream_t stream);
 
+/* ---- backward of the embedding stages in front of block 0 (whole-tower fine-tuning; csrc/pclip_embed_bwd.hip lists every rounding) ---------- */
+
+/* Envelope of both entry points: B >= 1, 1 <= L <= 4096, W % 64 == 0, W <= 2048 (and V >= 1); operands 16-byte aligned.  fp32 accumulation, no atomics:
+ * two calls give the same bits. */
+#define PCLIP_EMBED_BWD_CHUNK 128
+
+/* Backward of the text embedding x = token_embedding(text) + positional_embedding (clip/model.py:342-344) from dx [B * L, W] fp16:
+ * dE [V, W] fp32, dense (rows whose id does not occur are exactly zero), and dpos [L, W] fp32 = sum over b, ascending, of dx[b, l].  The caller sorts
+ * the B * L flat ids (clamped to [0, V - 1], as pclip_text_embed_f16 clamps them) STABLY: sorted_ids ascending, order[r] = the row of dx at sorted
+ * position r.  dE is a segmented reduction over chunks of PCLIP_EMBED_BWD_CHUNK consecutive sorted positions: rows added in ascending sorted position into
+ * one fp32 accumulator per column; a run of equal ids inside one chunk is written directly, a run that crosses chunk boundaries leaves one partial per
+ * chunk in part [ceil(B * L / CHUNK)][2][W] fp32, and a second pass adds those partials in ascending chunk order.  dE or dpos may be NULL (that
+ * gradient is not wanted); sorted_ids, order and part are read only for dE. */
+int pclip_text_embed_backward(const void* dx, const int64_t* sorted_ids, const int64_t* order, int B, int L, int W, int V, float* dE, float* dpos,
+                              float* part, pclip_stream_t stream);
+
+/* Backward of the vision stem's token assembly x = [class_embedding ; patches] + positional_embedding (clip/model.py:222-227; dt [B, L, W] fp16 is the
+ * gradient of the assembled tokens, i.e. what ln_pre's backward returns), one pass over dt: dpos [L, W] fp32 = sum over b, ascending, of dt[b, l] (row 0
+ * is also the gradient of class_embedding) and dpatch [B * (L - 1), W] fp16 = the rows dt[b, 1:], contiguous, bit-exact copies (the gradient of the
+ * patch convolution's output).  dpos or dpatch may be NULL. */
+int pclip_vit_embed_backward_f16(const void* dt, int B, int L, int W, float* dpos, void* dpatch, pclip_stream_t stream);
+
 /* One torch.optim.AdamW step (main.py:134-135: eps 1e-4, weight_decay 0.05) on fp16 parameters with fp16 moments, every
  * intermediate rounded to fp16 where the single-tensor implementation materialises an fp16 tensor; step counts from 1. */
 int pclip_adamw_f16(void* p, const void* g, void* m, void* v, size_t n, double lr, double beta1, double beta2, double eps,

@@ -20,6 +20,7 @@ TIP_MAX_ALPHAS, TIP_MAX_CLASSES, TIP_MAX_D = 32, 4096, 2048                     
 # pclip_tower_grad_sumsq / pclip_tower_optim_finish / pclip_tower_adamw: chunk length, table row / state block sizes, row flags
 TOWER_CHUNK, TOWER_ROW_BYTES, TOWER_STATE_BYTES = 4096, 64, 64
 TOWER_PARAM_F16, TOWER_GRAD_F16, TOWER_ALIGNED, TOWER_DECAY = 0x1, 0x2, 0x4, 0x8
+EMBED_BWD_CHUNK = 128                                      # PCLIP_EMBED_BWD_CHUNK: sorted rows per chunk of pclip_text_embed_backward's segmented reduction
 PROMPT_CTX_SLICE = 16                                      # PCLIP_PROMPT_CTX_SLICE: classes per slice of pclip_prompt_ctx_grad_f32's first stage
 
 
@@ -124,6 +125,8 @@ _SIGS = {
     "pclip_layernorm_backward_g32_f16": [_P, c_int, _P, _P, c_int, _P, c_int, c_int, c_int, c_float, _P, c_int, _P, c_int, _P],
     "pclip_prompt_embed_f16": [_P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P],
     "pclip_prompt_ctx_grad_f32": [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P],
+    "pclip_text_embed_backward": [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P],
+    "pclip_vit_embed_backward_f16": [_P, c_int, c_int, c_int, _P, _P, _P],
     "pclip_adamw_f16": [_P, _P, _P, _P, c_size_t, c_double, c_double, c_double, c_double, c_double, c_int, _P],
     "pclip_tower_grad_sumsq": [_P, c_int, c_int, _P, _P],
     "pclip_tower_optim_finish": [_P, c_int, _P, c_float, c_double, c_double, c_float, c_float, c_int, c_int, _P],

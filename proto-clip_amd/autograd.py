@@ -423,6 +423,90 @@ def run_tower_tail(x, h0, blocks, first, B, L, heads, causal, select, sel_rows, 
     return TowerTailFn.apply(x, h0, meta, *params)
 
 
+# ---- the stages in front of block 0: whole-tower fine-tuning (CLIP.unfreeze(stem=...)) ---------------------------------------------------------------
+# Both Functions put the residual stream that enters block 0 on the tape with the same kernels, hence the same bits, as the frozen path; TowerTailFn
+# (taped from block 0) hands back the stream gradient.  A gradient is computed only for a parameter that requires one and arrives in its dtype.
+
+def _f32(t):
+    return t if t.dtype == torch.float32 else t.float()
+
+
+def _stem_dx(dx):
+    dx = dx.contiguous()
+    return dx if dx.dtype == torch.float16 else ops.cast_f16(dx.float())
+
+
+class VitStemFn(torch.autograd.Function):
+    """(img, conv1.weight, class_embedding, positional_embedding, ln_pre.weight, ln_pre.bias) -> x [B*L, W] fp16 = ln_pre([class ; conv1(img)] + pos)
+    (clip/model.py:222-227): im2col + GEMM, token assembly, LayerNorm — the bits of the fused pclip_vit_embed_ln_f16 pass.  Kept for the backward: the
+    pre-LayerNorm tokens; the im2col matrix is recomputed from the image (the caller holds the image anyway; the matrix would be a second copy of
+    it).  backward: pclip_layernorm_backward_g32_f16 -> dt, dln_pre; pclip_vit_embed_backward_f16 -> dpos (row 0 = dclass), dpatch;
+    dconv1 = dpatch^T cols, cut from the padded columns.  The pixels get no gradient."""
+
+    @staticmethod
+    def forward(ctx, img, wconv, cls, pos, lnw, lnb, P, cache):
+        from .clip.model import _pad_patch_weight
+        B, W = img.shape[0], wconv.shape[0]
+        G2 = (img.shape[2] // P) ** 2
+        kp = 3 * P * P
+        w16 = cache.get("conv1", wconv, _pad_patch_weight)
+        cls16 = cache.get("cls", cls, lambda t: t.half())
+        pos16 = cache.get("pos", pos, lambda t: t.half().contiguous())
+        patch = ops.gemm(ops.im2col_patches(img, P), w16 if w16.dtype == torch.float16 else w16.half())
+        tokens = ops.vit_assemble_tokens(patch, cls16, pos16, B, G2, W)
+        ctx.shape = (B, G2 + 1, W, P, kp)
+        ctx.save_for_backward(img, tokens, wconv, cls, pos, lnw, lnb)
+        return ops.layernorm(tokens, _f32(lnw), _f32(lnb))
+
+    @staticmethod
+    def backward(ctx, dx):
+        img, tokens, wconv, cls, pos, lnw, lnb = ctx.saved_tensors
+        B, L, W, P, kp = ctx.shape
+        if ctx.needs_input_grad[0]:
+            raise NotImplementedError("VitStemFn: the pixels get no gradient; detach the images")
+        need = ctx.needs_input_grad
+        dt, dg, db = ops.layernorm_backward_f32(tokens, _f32(lnw), _stem_dx(dx))
+        dpos, dpatch = ops.vit_embed_backward(dt, B, L, want_pos=need[2] or need[3], want_patch=need[1])
+        dw = None                                                          # (dclass is a copy of dpos' row 0: the two .grad tensors must not share storage)
+        if need[1]:
+            dw = _weight_grad(dpatch, ops.im2col_patches(img, P))[:, :kp].reshape(wconv.shape)          # fp16 [W, kpad] -> [W, 3, P, P]
+            dw = dw.contiguous() if wconv.dtype == torch.float16 else dw.float()
+        return (None, dw, _like(dpos[0].clone(), cls) if need[2] else None, _like(dpos, pos) if need[3] else None,
+                _like(dg, lnw) if need[4] else None, _like(db, lnb) if need[5] else None, None, None)
+
+
+class TextEmbedFn(torch.autograd.Function):
+    """(tokens, token_embedding.weight, positional_embedding) -> x [B*L, W] fp16 = token_embedding[tokens] + positional_embedding (clip/model.py:342-344),
+    the bits of ops.text_embed.  backward: pclip_text_embed_backward (dense fp32 dE by a fixed-order segmented reduction, dpos summed over the prompts)."""
+
+    @staticmethod
+    def forward(ctx, tokens, emb, pos, cache):
+        emb16 = cache.get("tok", emb, lambda t: t.half().contiguous())
+        pos16 = cache.get("pos", pos, lambda t: t.half().contiguous())
+        tokens = tokens.to(torch.int64).contiguous()
+        ctx.save_for_backward(tokens, emb, pos)
+        return ops.text_embed(tokens, emb16, pos16)
+
+    @staticmethod
+    def backward(ctx, dx):
+        tokens, emb, pos = ctx.saved_tensors
+        dE, dpos = ops.text_embed_backward(_stem_dx(dx), tokens, emb.shape[0], want_emb=ctx.needs_input_grad[1], want_pos=ctx.needs_input_grad[2])
+        return None, _like(dE, emb), _like(dpos, pos), None
+
+
+def stem_plan(tower_name, blocks, prefix_params, head_params, opted_in):
+    """(first, stem) for a tower whose prefix parameters may have been opted in through CLIP.unfreeze(stem=...): stem is True when an opted-in prefix
+    parameter requires grad — the whole tower is then taped, first = 0.  Without the opt-in this is `tower_plan`, refusals included."""
+    if not opted_in:
+        return tower_plan(tower_name, blocks, prefix_params, head_params), False
+    if any(p.requires_grad for _, p in prefix_params):
+        for name, p in prefix_params:
+            if p.requires_grad and p.dtype not in (torch.float16, torch.float32):
+                raise PclipError(f"{tower_name}: unsupported dtype {p.dtype} of parameter {name}")
+        return 0, True
+    return tower_plan(tower_name, blocks, [], head_params), False
+
+
 # ---- learned prompt context (CoOp): the embedded prompts as a function of the fp32 context rows ---------------------------------------------------
 
 class PromptEmbedFn(torch.autograd.Function):

@@ -152,6 +152,16 @@ class _Cached:
         return hit[1]
 
 
+def _pad_patch_weight(w):
+    """conv1.weight [W, 3, P, P] -> GEMM rows [W, kpad]: zero columns up to the K-tile, as ops.im2col_patches pads its matrix."""
+    kp = w.shape[1] * w.shape[2] * w.shape[3]
+    kpad = (kp + 63) // 64 * 64
+    w2 = w.reshape(w.shape[0], kp)
+    if kpad != kp:
+        w2 = torch.cat([w2, w2.new_zeros(w.shape[0], kpad - kp)], dim=1)
+    return w2.contiguous()
+
+
 class VisionTransformer(nn.Module):
     """clip/model.py:204-238."""
 
@@ -169,6 +179,7 @@ class VisionTransformer(nn.Module):
         self.ln_post = _ln(width)
         self.proj = nn.Parameter(torch.empty(width, output_dim), requires_grad=False)
         self._cache = _Cached()
+        self._stem_opt_in = False                                           # CLIP.unfreeze(stem=...): conv1 / embeddings / ln_pre may train
         # images per pass: bounds activation memory (c_fc output = chunk*L*4W*2 B = 1.2 GB for ViT-B/16 at 1024);
         # larger passes waste less of the GEMMs' last round of persistent tiles (measured on MI355X: 1024 > 512 > 256)
         self.chunk = int(os.environ.get("PCLIP_VIT_CHUNK", "1024"))
@@ -179,14 +190,25 @@ class VisionTransformer(nn.Module):
         outs = [self._forward_chunk(x[i:i + self.chunk]) for i in range(0, x.shape[0], self.chunk)]
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
 
+    def _prefix_params(self):
+        """(name, parameter) of everything in front of block 0, in VitStemFn's argument order."""
+        return [("visual.conv1.weight", self.conv1.weight), ("visual.class_embedding", self.class_embedding),
+                ("visual.positional_embedding", self.positional_embedding), ("visual.ln_pre.weight", self.ln_pre.weight),
+                ("visual.ln_pre.bias", self.ln_pre.bias)]
+
+    def _head_params(self):
+        return [("visual.ln_post.weight", self.ln_post.weight), ("visual.ln_post.bias", self.ln_post.bias), ("visual.proj", self.proj)]
+
     def _tape_from(self):
-        """Index of the first residual block with a trainable parameter (layers: only ln_post / proj train), None when the tower is frozen."""
+        """Index of the first residual block with a trainable parameter (layers: only ln_post / proj train), None when the tower is frozen.
+        Refuses a trainable prefix parameter, opted in or not: the taped passes plan with `_tape_plan`."""
         from ..autograd import tower_plan
-        prefix = [("visual.conv1.weight", self.conv1.weight), ("visual.class_embedding", self.class_embedding),
-                  ("visual.positional_embedding", self.positional_embedding), ("visual.ln_pre.weight", self.ln_pre.weight),
-                  ("visual.ln_pre.bias", self.ln_pre.bias)]
-        heads = [("visual.ln_post.weight", self.ln_post.weight), ("visual.ln_post.bias", self.ln_post.bias), ("visual.proj", self.proj)]
-        return tower_plan("visual tower", self.transformer.resblocks, prefix, heads)
+        return tower_plan("visual tower", self.transformer.resblocks, self._prefix_params(), self._head_params())
+
+    def _tape_plan(self):
+        """(first, stem): `_tape_from`, except that prefix parameters opted in through CLIP.unfreeze(stem=...) put the whole tower on the tape."""
+        from ..autograd import stem_plan
+        return stem_plan("visual tower", self.transformer.resblocks, self._prefix_params(), self._head_params(), self._stem_opt_in)
 
     def _forward_chunk(self, img):
         B, P, W = img.shape[0], self.patch_size, self.width
@@ -195,16 +217,17 @@ class VisionTransformer(nn.Module):
         if img.dtype not in (torch.float32, torch.float16):   # fp32: image.type(self.dtype) (clip/model.py:339) rides on the im2col gather
             raise PclipError(f"unsupported image dtype {img.dtype}")
         img = img.contiguous()
-        kp = 3 * P * P
-        kpad = (kp + 63) // 64 * 64
-
-        def pad_w(w):
-            w2 = w.reshape(W, kp)
-            if kpad != kp:
-                w2 = torch.cat([w2, w2.new_zeros(W, kpad - kp)], dim=1)
-            return w2.contiguous()
-
-        wconv = self._cache.get("conv1", self.conv1.weight, pad_w)
+        first, stem = self._tape_plan() if torch.is_grad_enabled() else (None, False)
+        if stem:                                                            # whole-tower fine-tuning: the stem and every block on the tape
+            from ..autograd import VitStemFn, run_tower_tail
+            blocks = self.transformer.resblocks
+            x = VitStemFn.apply(img, self.conv1.weight, self.class_embedding, self.positional_embedding, self.ln_pre.weight, self.ln_pre.bias,
+                                P, self._cache)
+            rows = torch.arange(B, device=x.device) * L
+            what = f"encode_image (visual tower, stem + blocks 0..{len(blocks) - 1} + heads on the tape)"
+            return run_tower_tail(x, None, blocks, 0, B, L, self.heads, False, lambda t: t.view(B, L, W)[:, 0, :].contiguous(), rows, True,
+                                  self.ln_post, self.proj, self._cache, what)
+        wconv = self._cache.get("conv1", self.conv1.weight, _pad_patch_weight)
         cls16 = self._cache.get("cls", self.class_embedding, lambda t: t.half())
         pos16 = self._cache.get("pos", self.positional_embedding, lambda t: t.half().contiguous())
         projT = self._cache.get("projT", self.proj, lambda t: t.t().contiguous())
@@ -219,7 +242,6 @@ class VisionTransformer(nn.Module):
             x = ops.vit_assemble_tokens(patch, cls16, pos16, B, G * G, W)   # clip/model.py:225-226
             x = ops.layernorm(x, self.ln_pre.weight, self.ln_pre.bias)      # 227
         pick_cls = lambda t: t.view(B, L, W)[:, 0, :].contiguous()          # x[:, 0, :], 233 (taken before the last block's tail)
-        first = self._tape_from() if torch.is_grad_enabled() else None
         if first is not None:                                               # fine-tuning: blocks[first:] + ln_post + proj on the tape
             from ..autograd import run_tower_tail
             what = f"encode_image (visual tower, blocks {first}..{len(blocks) - 1} + heads trainable)"
@@ -424,6 +446,7 @@ class CLIP(nn.Module):
         self.text_projection = nn.Parameter(torch.empty(transformer_width, embed_dim), requires_grad=False)
         self.logit_scale = nn.Parameter(torch.ones([]) * np.log(1 / 0.07), requires_grad=False)
         self._cache = _Cached()
+        self._text_stem_opt_in = False                                      # unfreeze(stem=...): token_embedding / positional_embedding may train
         self.text_chunk = 1024
 
     @property
@@ -446,47 +469,81 @@ class CLIP(nn.Module):
     def encode_text(self, text):
         """text [n, context_length] int64 -> [n, embed_dim] fp16 (clip/model.py:341-354).  Unlike the
         reference's per-class calls (utils.py:264-266, n = #templates) any n is efficient here."""
-        first = self._text_tape_from() if torch.is_grad_enabled() else None
+        first, stem = self._text_tape_plan() if torch.is_grad_enabled() else (None, False)
         with torch.set_grad_enabled(first is not None):
-            outs = [self._encode_text_chunk(text[i:i + self.text_chunk], first) for i in range(0, text.shape[0], self.text_chunk)]
+            outs = [self._encode_text_chunk(text[i:i + self.text_chunk], first, stem) for i in range(0, text.shape[0], self.text_chunk)]
             return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+
+    def _text_prefix_params(self):
+        return [("token_embedding.weight", self.token_embedding.weight), ("positional_embedding", self.positional_embedding)]
+
+    def _text_head_params(self):
+        return [("ln_final.weight", self.ln_final.weight), ("ln_final.bias", self.ln_final.bias), ("text_projection", self.text_projection)]
 
     def _text_tape_from(self):
         """As VisionTransformer._tape_from for the text tower (ln_final / text_projection are its heads)."""
         from ..autograd import tower_plan
-        prefix = [("token_embedding.weight", self.token_embedding.weight), ("positional_embedding", self.positional_embedding)]
-        heads = [("ln_final.weight", self.ln_final.weight), ("ln_final.bias", self.ln_final.bias), ("text_projection", self.text_projection)]
-        return tower_plan("text tower", self.transformer.resblocks, prefix, heads)
+        return tower_plan("text tower", self.transformer.resblocks, self._text_prefix_params(), self._text_head_params())
 
-    def unfreeze(self, visual_blocks=0, text_blocks=0, heads=True):
+    def _text_tape_plan(self):
+        """As VisionTransformer._tape_plan for the text tower."""
+        from ..autograd import stem_plan
+        return stem_plan("text tower", self.transformer.resblocks, self._text_prefix_params(), self._text_head_params(), self._text_stem_opt_in)
+
+    def unfreeze(self, visual_blocks=0, text_blocks=0, heads=True, stem=False):
         """Make a tail of the transformer towers trainable: the last `visual_blocks` / `text_blocks` residual blocks and, with `heads`, ln_post / proj
         and ln_final / text_projection.  Returns the list of those parameters, ready for an optimizer; encode_image / encode_text then record their
-        tail for autograd whenever grad mode is on.  (Everything before the first trainable block stays frozen: conv1, the embeddings, ln_pre.)"""
+        tail for autograd whenever grad mode is on.  Everything before the first trainable block stays frozen — unless `stem` opts a tower's prefix
+        in: True (both towers), "visual" (conv1, class / positional embedding, ln_pre) or "text" (token / positional embedding).  Those parameters are
+        then marked and returned too, the opt-in is recorded on the model, and a pass of that tower tapes the stem and every block (blocks that stay
+        frozen pay for no weight gradient).  A prefix parameter that merely has requires_grad set, without this opt-in, is refused as before."""
+        if stem not in (False, True, "visual", "text"):
+            raise PclipError(f"unfreeze: stem={stem!r} is none of False, True, 'visual', 'text'")
+        stem_visual, stem_text = stem in (True, "visual"), stem in (True, "text")
         if isinstance(self.visual, ModifiedResNet):                         # no backward: the tower stays frozen, the text side may train
             if visual_blocks:
                 raise PclipError(f"unfreeze: visual_blocks={visual_blocks}, but the ModifiedResNet tower has no backward (only transformer towers)")
+            if stem_visual:
+                raise PclipError(f"unfreeze: stem={stem!r} asks for the visual stem, but the ModifiedResNet visual tower has no backward "
+                                 "(only transformer towers; stem='text' trains the text embeddings beside it)")
             vis = []
         else:
             nv = len(self.visual.transformer.resblocks)
             if not 0 <= visual_blocks <= nv:
                 raise PclipError(f"unfreeze: visual_blocks={visual_blocks} outside 0..{nv}")
-            vis = [p for blk in list(self.visual.transformer.resblocks)[nv - visual_blocks:] for p in blk.parameters()]
+            vis = [p for _, p in self.visual._prefix_params()] if stem_visual else []
+            vis += [p for blk in list(self.visual.transformer.resblocks)[nv - visual_blocks:] for p in blk.parameters()]
             if heads:
                 vis += [self.visual.ln_post.weight, self.visual.ln_post.bias, self.visual.proj]
         nt = len(self.transformer.resblocks)
         if not 0 <= text_blocks <= nt:
             raise PclipError(f"unfreeze: text_blocks={text_blocks} outside 0..{nt}")
-        txt = [p for blk in list(self.transformer.resblocks)[nt - text_blocks:] for p in blk.parameters()]
+        txt = [p for _, p in self._text_prefix_params()] if stem_text else []
+        txt += [p for blk in list(self.transformer.resblocks)[nt - text_blocks:] for p in blk.parameters()]
         if heads:
             txt += [self.ln_final.weight, self.ln_final.bias, self.text_projection]
+        if stem_visual:
+            self.visual._stem_opt_in = True
+        if stem_text:
+            self._text_stem_opt_in = True
         params = vis + txt
         for p in params:
             p.requires_grad_(True)
         return params
 
-    def _encode_text_chunk(self, text, first=None):
+    def _encode_text_chunk(self, text, first=None, stem=False):
         B, L = text.shape
         W = self.transformer.width
+        if stem:                                                                 # whole-tower fine-tuning: the embedding and every block on the tape
+            from ..autograd import TextEmbedFn, run_tower_tail
+            blocks = self.transformer.resblocks
+            x = TextEmbedFn.apply(text, self.token_embedding.weight, self.positional_embedding, self._cache)
+            pos = torch.arange(L, device=x.device).expand(B, L)                  # the FIRST maximum, gather_eot's tie rule
+            eot = torch.where(text == text.max(dim=-1, keepdim=True).values, pos, pos.new_full((), L)).min(dim=-1).values
+            rows = torch.arange(B, device=x.device) * L + eot
+            what = f"encode_text (text tower, embeddings + blocks 0..{len(blocks) - 1} + heads on the tape)"
+            return run_tower_tail(x, None, blocks, 0, B, L, self.transformer_heads, True, lambda t: ops.gather_eot(t, text, B, L, W), rows, False,
+                                  self.ln_final, self.text_projection, self._cache, what)
         emb16 = self._cache.get("tok", self.token_embedding.weight, lambda t: t.half().contiguous())
         pos16 = self._cache.get("pos", self.positional_embedding, lambda t: t.half().contiguous())
         projT = self._cache.get("tprojT", self.text_projection, lambda t: t.t().contiguous())

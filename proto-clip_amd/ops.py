@@ -970,6 +970,64 @@ def text_embed(tokens, tok_emb, pos_emb) -> torch.Tensor:
     return x
 
 
+EMBED_BWD_CHUNK = _lib.EMBED_BWD_CHUNK      # sorted rows per chunk of text_embed_backward's segmented reduction (PCLIP_EMBED_BWD_CHUNK)
+EMBED_BWD_MAX_L, EMBED_BWD_MAX_W = 4096, 2048
+
+
+def _embed_bwd_envelope(what: str, B: int, L: int, W: int):
+    if not (B >= 1 and 1 <= L <= EMBED_BWD_MAX_L and W >= 64 and W % 64 == 0 and W <= EMBED_BWD_MAX_W):
+        raise _lib.PclipError(f"{what}: B={B} L={L} W={W} outside the envelope (B >= 1, 1 <= L <= {EMBED_BWD_MAX_L}, W % 64 == 0, W <= {EMBED_BWD_MAX_W})")
+
+
+def text_embed_backward(dx, tokens, vocab: int, want_emb: bool = True, want_pos: bool = True):
+    """Backward of `text_embed` from dx [B * L, W] fp16 and tokens [B, L] int64: (dE [vocab, W], dpos [L, W]), fp32, None where not wanted
+    (pclip_text_embed_backward).  dE is dense: a row whose id does not occur is exactly zero.  torch's stable sort of the flat ids is the plumbing
+    of the segmented reduction (no host synchronisation); ids are clamped to the vocabulary as the forward clamps them."""
+    require_cuda(dx, tokens)
+    dx = _f16c(dx)
+    if tokens.dim() != 2 or tokens.dtype != torch.int64:
+        raise _lib.PclipError(f"text_embed_backward: tokens must be int64 [B, L], got {tokens.dtype} {tuple(tokens.shape)}")
+    B, L = tokens.shape
+    W = dx.shape[-1]
+    _embed_bwd_envelope("text_embed_backward", B, L, W)
+    if dx.dim() != 2 or dx.shape[0] != B * L:
+        raise _lib.PclipError(f"text_embed_backward: dx {tuple(dx.shape)} does not hold B * L = {B * L} rows")
+    if vocab < 1:
+        raise _lib.PclipError(f"text_embed_backward: vocab={vocab}")
+    if not (want_emb or want_pos):
+        return None, None
+    dE = ids = order = part = None
+    if want_emb:
+        ids, order = torch.sort(tokens.reshape(-1).clamp(0, vocab - 1), stable=True)
+        dE = torch.empty(vocab, W, dtype=torch.float32, device=dx.device)
+        part = torch.empty((B * L + EMBED_BWD_CHUNK - 1) // EMBED_BWD_CHUNK, 2, W, dtype=torch.float32, device=dx.device)
+    dpos = torch.empty(L, W, dtype=torch.float32, device=dx.device) if want_pos else None
+    check(_lib.load().pclip_text_embed_backward(ptr(dx), ptr(ids), ptr(order), B, L, W, vocab, ptr(dE), ptr(dpos), ptr(part), stream()),
+          "pclip_text_embed_backward")
+    return dE, dpos
+
+
+def vit_embed_backward(dt, B: int, L: int, want_pos: bool = True, want_patch: bool = True):
+    """Backward of `vit_assemble_tokens` from dt [B * L, W] fp16 (the gradient of the assembled tokens), one pass: (dpos [L, W] fp32 — row 0 is also
+    the class embedding's gradient —, dpatch [B * (L - 1), W] fp16, bit-exact copies of the non-class rows), None where not wanted
+    (pclip_vit_embed_backward_f16)."""
+    require_cuda(dt)
+    dt = _f16c(dt)
+    W = dt.shape[-1]
+    _embed_bwd_envelope("vit_embed_backward", B, L, W)
+    if dt.numel() != B * L * W:
+        raise _lib.PclipError(f"vit_embed_backward: dt {tuple(dt.shape)} does not hold B * L = {B * L} rows")
+    if not (want_pos or want_patch):
+        return None, None
+    dpos = torch.empty(L, W, dtype=torch.float32, device=dt.device) if want_pos else None
+    dpatch = torch.empty(B * (L - 1), W, dtype=torch.float16, device=dt.device) if want_patch else None
+    if dpos is None and L == 1:                 # no patch rows and no sum wanted: nothing to launch
+        return None, dpatch
+    check(_lib.load().pclip_vit_embed_backward_f16(ptr(dt), B, L, W, ptr(dpos), ptr(dpatch) if want_patch and L > 1 else None, stream()),
+          "pclip_vit_embed_backward_f16")
+    return dpos, dpatch
+
+
 def _prompt_ctx_shape(ctx, N: int, W: int):
     """(n_ctx, class_specific) of a context tensor: fp32 [n_ctx, W] shared, or [N, n_ctx, W]."""
     if ctx.dtype != torch.float32:
