@@ -1,6 +1,8 @@
 // Cross-entropy over cosine logits and its gradients, for training on the logits of clip/model.py:356-370 (a text-initialised classifier or an adapter under
 // `scale * f' @ w'^T`, CLIP's symmetric contrastive loss, the temperature).  Ragged in M and T; the [M, T] matrix never reaches memory, forward or backward.
 //   cos[m, t] = fp32 MFMA accumulation of a'[m, :] . b'[t, :],  s = scale * cos in fp32.  Unlike pclip_logits.hip NOTHING is rounded to fp16 on the way to s.
+// The panel walk of pclip_panel_walk.h: the forward is built from its staging and its paired form; the backward calls its second product and gradient store and keeps
+// its staging, first product and prefetch written out (the note at ce_bwd_kernel says why).
 // Forward (ce_fwd_kernel): the walk of cosine_logits_kernel by eight waves — a panel of 16 RF rows of a' in LDS, the rows of b' streamed in the MFMA operand layout, a lane
 //   ending with 4 consecutive columns of one row per fragment — with an online (max, sum-exp) per row in place of the top-k lists and the target logit picked
 //   out by comparing the label with the column index (a label is never an index: one outside [0, T) matches nothing).  Symmetric mode: the same tile gives a
@@ -20,12 +22,10 @@
 // Every workgroup walks ALL walked rows in index order and an element has one accumulator: a row's lse, loss term and gradient do not depend on RF, the grid or
 // (labelled, direction 0) the other rows; where the own rows are few panels, the walked tiles are shared between workgroups in fixed chunks (ce_chunks).
 // Only __syncthreads barriers and compiler-counted waits: nothing here for the race-stress build.
-#include "pclip_proto_dev.h"
+#include "pclip_panel_walk.h"
 
 namespace {
 
-constexpr int CE_PAD = 8;                      // halves between the LDS rows of the panel beyond D
-constexpr int CE_PLD = 72;                     // halves per LDS row of the E / Y tiles (64 walked rows + 8: 16-byte reads spread over the banks)
 constexpr int CE_LDS_MAX = 152 * 1024;           // dynamic LDS asked for: the forward kernel keeps up to 6 KB of static LDS next to it (the most used is 104 KB)
 constexpr int CE_DMAX = 2048;
 constexpr int CE_FW = 8;                        // waves of a forward workgroup: each walks every eighth block of 64 columns (a constant: a row's merge order never changes)
@@ -45,7 +45,7 @@ __device__ __forceinline__ long long load_label(const void* labels, int i64, int
     return i64 ? (long long)reinterpret_cast<const int64_t*>(labels)[i] : (long long)reinterpret_cast<const int32_t*>(labels)[i];
 }
 
-// one wave per row of the panel: normalised when asked, zeros beyond R
+// ce_bwd_kernel's own staging: stage_panel with the wave count read from blockDim, as that kernel has always had it (see the note at the kernel)
 template <int NCH>
 __device__ __forceinline__ void load_panel(half_t* panel, int LDP, const half_t* __restrict__ x, int ldx, int R, int D, int r0, int rows, int norm) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
@@ -69,22 +69,6 @@ __device__ __forceinline__ void load_panel(half_t* panel, int LDP, const half_t*
     }
 }
 
-// rows normalised into the workspace (dense [R, D])
-template <int NCH>
-__global__ __launch_bounds__(256) void ce_norm_rows_kernel(const half_t* __restrict__ x, int ldx, half_t* __restrict__ y, int R, int D) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int row = blockIdx.x * 4 + wave; row < R; row += gridDim.x * 4) {
-        RowRegs<NCH> r;
-        load_row<NCH>(x + (size_t)row * ldx, D, lane, r);
-        normalise_row<NCH>(r);
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const int d = c * 512 + lane * 8;
-            if (d < D) st_half8(y + (size_t)row * D + d, r.v[c]);
-        }
-    }
-}
-
 template <int NCH, int RF>
 __global__ __launch_bounds__(64 * CE_FW) void ce_fwd_kernel(const half_t* __restrict__ a, int lda, int M, const half_t* __restrict__ b, int ldb, int T, int D, float scale,
                                                      int norm_a, int symmetric, const void* __restrict__ labels, int lab64, float* __restrict__ lse_row,
@@ -92,10 +76,10 @@ __global__ __launch_bounds__(64 * CE_FW) void ce_fwd_kernel(const half_t* __rest
     extern __shared__ __attribute__((aligned(16))) char ce_smem[];
     __shared__ float red[CE_FW][RF][16][3];
     half_t* panel = reinterpret_cast<half_t*>(ce_smem);                                      // [16 RF][D + 8]
-    const int LDP = D + CE_PAD;
+    const int LDP = D + PW_PAD;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int m0 = blockIdx.x * 16 * RF;
-    load_panel<NCH>(panel, LDP, a, lda, M, D, m0, 16 * RF, norm_a);
+    stage_panel<NCH, CE_FW>(panel, LDP, a, lda, M, D, m0, 16 * RF, lane, wave, norm_a);
 
     const int lr = lane & 15, lq = lane >> 4;
     float mx[RF], sm[RF], tg[RF];
@@ -113,38 +97,9 @@ __global__ __launch_bounds__(64 * CE_FW) void ce_fwd_kernel(const half_t* __rest
         const int t0 = cb * 64;
         const half_t* bp[4];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            int t = t0 + 16 * c + lr;
-            t = t < T ? t : T - 1;
-            bp[c] = b + (size_t)t * ldb + lq * 8;
-        }
-        const half_t* ap = panel + (size_t)lr * LDP + lq * 8;
+        for (int c = 0; c < 4; ++c) bp[c] = walked_row(b, ldb, t0 + 16 * c + lr, T, lq);
         float4_t acc[RF][4];
-#pragma unroll
-        for (int f = 0; f < RF; ++f)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc[f][c] = float4_t{0.f, 0.f, 0.f, 0.f};
-        half8_t b0[4], b1[4];                                                                // k-steps ks, ks + 1 (KS is even); the pair after them is in flight under their MFMAs
-#pragma unroll
-        for (int c = 0; c < 4; ++c) b0[c] = ld_half8(bp[c]), b1[c] = ld_half8(bp[c] + 32);
-        for (int ks = 0; ks < KS; ks += 2) {
-            half8_t n0[4], n1[4];
-            const int kn = ks + 2 < KS ? ks + 2 : ks;                                        // (the last pair re-reads itself: no read past column D)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) n0[c] = ld_half8(bp[c] + kn * 32), n1[c] = ld_half8(bp[c] + kn * 32 + 32);
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                half8_t af[RF];
-#pragma unroll
-                for (int f = 0; f < RF; ++f) af[f] = ld_half8(ap + (size_t)f * 16 * LDP + (ks + u) * 32);
-#pragma unroll
-                for (int f = 0; f < RF; ++f)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) acc[f][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(u ? b1[c] : b0[c], af[f], acc[f][c], 0, 0, 0);
-            }
-#pragma unroll
-            for (int c = 0; c < 4; ++c) b0[c] = n0[c], b1[c] = n1[c];
-        }
+        walk_pairs<RF, 4>(bp, panel + (size_t)lr * LDP + lq * 8, LDP, KS, acc);
         // acc[f][c][r] = cos(m0 + 16 f + lr, t0 + 16 c + 4 lq + r)
 #pragma unroll
         for (int f = 0; f < RF; ++f)
@@ -283,6 +238,9 @@ __global__ __launch_bounds__(256) void ce_sum_chunks_kernel(const float* __restr
 }
 
 // NDF: the 16-column fragments of one wave's quarter of D the kernel is compiled for (D / 64 <= NDF of them are live)
+// Of the shared skeleton of pclip_panel_walk.h this kernel calls bwd_second_product and store_grad_panel.  Its staging, its first product and its wt0 prefetch are
+// written out (the text of bwd_first_product / bwd_prefetch_t): each of them behind the shared function re-rolled the register allocation of the RF = 4 form and
+// cost 0.5 - 0.9 % at 32768^2 (profiles/panel_walk_refactor.txt, section 5).  A change to the backward walk is made here and in the header.
 template <int NCH, int RF, int NDF>
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const half_t* __restrict__ own, int ldo, int Ro, const half_t* __restrict__ walk, int ldw, int Rw,
                                                      const half_t* __restrict__ walkT, int ldt, int D, float scale, float weight, int norm_own, int symmetric,
@@ -290,11 +248,11 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const half_t* __restrict__ 
                                                      const float* __restrict__ lse_own, const float* __restrict__ lse_walk, float* __restrict__ gout,
                                                      float* __restrict__ dsc_part) {
     extern __shared__ __attribute__((aligned(16))) char ce_smem[];
-    const int LDP = D + CE_PAD;
+    const int LDP = D + PW_PAD;
     half_t* panel = reinterpret_cast<half_t*>(ce_smem);                                      // [16 RF][D + 8]
-    half_t* etile = panel + (size_t)16 * RF * LDP;                                           // [2][16 RF][CE_PLD]: r16(E), own row x walked row
-    half_t* ytile = etile + (size_t)2 * 16 * RF * CE_PLD;                                    // [2][16 RF][CE_PLD]: -kappa at the targets
-    int* hitflag = reinterpret_cast<int*>(ytile + (size_t)2 * 16 * RF * CE_PLD);             // [2][4]: wave w saw a target in its fragment of the tile
+    half_t* etile = panel + (size_t)16 * RF * LDP;                                           // [2][16 RF][PW_PLD]: r16(E), own row x walked row
+    half_t* ytile = etile + (size_t)2 * 16 * RF * PW_PLD;                                    // [2][16 RF][PW_PLD]: -kappa at the targets
+    int* hitflag = reinterpret_cast<int*>(ytile + (size_t)2 * 16 * RF * PW_PLD);             // [2][4]: wave w saw a target in its fragment of the tile
     float* dsc_red = reinterpret_cast<float*>(hitflag + 8);                                  // [4]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i0 = blockIdx.x * 16 * RF;
@@ -386,7 +344,7 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const half_t* __restrict__ 
                 e16[r] = (half_t)(e * CE_ESCALE);
                 y16[r] = hit ? (half_t)(-kappa * CE_ESCALE) : (half_t)0.f;
             }
-            const size_t at = ((size_t)buf * 16 * RF + 16 * f + lr) * CE_PLD + 16 * wave + 4 * lq;
+            const size_t at = ((size_t)buf * 16 * RF + 16 * f + lr) * PW_PLD + 16 * wave + 4 * lq;
             *reinterpret_cast<half4_t*>(etile + at) = e16;
             *reinterpret_cast<half4_t*>(ytile + at) = y16;
         }
@@ -395,54 +353,10 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const half_t* __restrict__ 
         __syncthreads();                                                                     // the tile is whole; the other buffer is free once every wave is here
         const bool targets = (hitflag[buf * 4] | hitflag[buf * 4 + 1] | hitflag[buf * 4 + 2] | hitflag[buf * 4 + 3]) != 0;
         // ---- this wave's quarter of D: acc2 += walked'^T (E + Y), the walked index along k ------------------------------------------------
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            half8_t pf[RF], yf[RF];
-#pragma unroll
-            for (int f = 0; f < RF; ++f) {
-                const size_t at = ((size_t)buf * 16 * RF + 16 * f + lr) * CE_PLD + 32 * p + 8 * lq;
-                pf[f] = ld_half8(etile + at);
-                yf[f] = ld_half8(ytile + at);
-            }
-#pragma unroll
-            for (int g = 0; g < NDF / 8; ++g) {
-                half8_t wt[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    if (p == 0 && g == 0) wt[u] = wt0[u];
-                    else wt[u] = 8 * g + u >= ndf ? half8_t{} : ld_half8(walkT + (size_t)(dbase + 16 * (8 * g + u) + lr) * ldt + j0 + 32 * p + 8 * lq);
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int df = 8 * g + u;
-                    if (df < ndf) {                                                          // (uniform)
-#pragma unroll
-                        for (int f = 0; f < RF; ++f) acc2[f][df] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wt[u], pf[f], acc2[f][df], 0, 0, 0);
-                        if (targets) {
-#pragma unroll
-                            for (int f = 0; f < RF; ++f) acc2[f][df] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wt[u], yf[f], acc2[f][df], 0, 0, 0);
-                        }
-                    }
-                }
-            }
-        }
+        bwd_second_product<RF, NDF, true>(walkT, ldt, dbase, ndf, j0, wt0, etile, ytile, targets, buf, lr, lq, acc2);
     }
     // acc2[f][df][r] = 2^14 sum_j (E - kappa Y)[i0 + 16 f + lr, j] walked'[j, dbase + 16 df + 4 lq + r]
-    const float mul = weight * scale * (1.f / CE_ESCALE);
-#pragma unroll
-    for (int f = 0; f < RF; ++f) {
-        const int i = i0 + 16 * f + lr;
-        if (i >= Ro) continue;
-#pragma unroll
-        for (int df = 0; df < NDF; ++df) {
-            if (df < ndf) {
-                float4_t o = acc2[f][df];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[r] *= mul;
-                *reinterpret_cast<float4_t*>(gout + (size_t)i * D + dbase + 16 * df + 4 * lq) = o;
-            }
-        }
-    }
+    store_grad_panel<RF, NDF>(gout, i0, Ro, D, dbase, ndf, weight * scale * (1.f / CE_ESCALE), lr, lq, acc2);
     if (dsc_part) {
         dsc = wave_sum(dsc);
         if (lane == 0) dsc_red[wave] = dsc;
@@ -485,17 +399,11 @@ __global__ __launch_bounds__(256) void ce_norm_backward_kernel(const half_t* __r
     }
 }
 
-inline int ce_rf(int R, int D) {                       // row fragments per panel: what R asks for, capped by the accumulator panel (RF D / 16 registers per lane <= 128)
-    const int rfmax = D <= 512 ? 4 : (D <= 1024 ? 2 : 1);
-    const int rf = R <= 16 ? 1 : (R <= 32 ? 2 : 4);
-    return rf > rfmax ? rfmax : rf;
-}
 inline int ce_rf_fwd(int M, int D) {                  // the forward has no other source of workgroups than its panels: smaller ones until there are 256 (a row's bits do not depend on RF)
-    int rf = ce_rf(M, D);
+    int rf = rf_for(M, D);
     while (rf > 1 && ceil_div(M, 16 * rf) < 256) rf >>= 1;
     return rf;
 }
-inline int ce_round64(int r) { return (r + 63) / 64 * 64; }
 
 struct CeFwdWs {
     size_t bn, colpart, tgt, bytes;
@@ -516,7 +424,7 @@ inline CeFwdWs ce_fwd_ws(int M, int T, int D) {
 constexpr int CE_WG_TARGET = 512;
 inline int ce_chunks(int Ro, int Rw, int D, bool split_allowed) {
     if (!split_allowed) return 1;
-    const int npanels = ceil_div(Ro, 16 * ce_rf(Ro, D)), ntiles = ceil_div(Rw, 64);
+    const int npanels = ceil_div(Ro, 16 * rf_for(Ro, D)), ntiles = ceil_div(Rw, 64);
     int n = ceil_div(CE_WG_TARGET, npanels);
     const int cap = (int)(4 * ((size_t)Ro + Rw) / Ro);
     n = n > cap ? cap : n;
@@ -535,7 +443,7 @@ inline CeBwdWs ce_bwd_ws(int M, int T, int D) {        // either direction fits:
     CeBwdWs w;
     size_t off = 0;
     w.wn = off, off += align_up((size_t)R * D * 2, 256);
-    w.wt = off, off += align_up((size_t)D * ce_round64(R) * 2, 256);
+    w.wt = off, off += align_up((size_t)D * round64(R) * 2, 256);
     w.dsc = off, off += align_up((da > db ? da : db) * 4, 256);
     w.part = off, off += align_up((pa > pb ? pa : pb) * D * 4, 256);
     w.bytes = off;
@@ -556,9 +464,9 @@ int ce_validate(const char* fn, const void* a, int lda, int M, const void* b, in
         PCLIP_REQUIRE(labels, "%s: labelled mode needs labels", fn);
         PCLIP_REQUIRE((uintptr_t)labels % ((flags & PCLIP_CE_LABELS_I64) ? 8 : 4) == 0, "%s: misaligned labels", fn);
     }
-    PCLIP_REQUIRE(lda >= D && lda % 8 == 0, "%s: lda=%d must be >= D=%d and a multiple of 8 halves", fn, lda, D);
-    PCLIP_REQUIRE(ldb >= D && ldb % 8 == 0, "%s: ldb=%d must be >= D=%d and a multiple of 8 halves", fn, ldb, D);
-    PCLIP_REQUIRE(((uintptr_t)a | (uintptr_t)b) % 16 == 0, "%s: operands must be 16-byte aligned", fn);
+    PCLIP_REQUIRE_PITCH(fn, lda, D);
+    PCLIP_REQUIRE_PITCH(fn, ldb, D);
+    PCLIP_REQUIRE_ALIGNED(fn, (uintptr_t)a | (uintptr_t)b, 0);
     PCLIP_REQUIRE(ws != nullptr && (uintptr_t)ws % 16 == 0, "%s: needs a 16-byte aligned workspace", fn);
     if (ws_bytes < need) {
         pclip_set_error("%s: workspace %zu < %zu", fn, ws_bytes, need);
@@ -566,23 +474,6 @@ int ce_validate(const char* fn, const void* a, int lda, int M, const void* b, in
     }
     return PCLIP_OK;
 }
-
-int ce_norm_rows(const half_t* x, int ldx, half_t* y, int R, int D, hipStream_t s) {
-    int g = ceil_div(R, 4);
-    g = g > 8192 ? 8192 : g;
-    if (D <= 512) ce_norm_rows_kernel<1><<<g, 256, 0, s>>>(x, ldx, y, R, D);
-    else if (D <= 1024) ce_norm_rows_kernel<2><<<g, 256, 0, s>>>(x, ldx, y, R, D);
-    else ce_norm_rows_kernel<4><<<g, 256, 0, s>>>(x, ldx, y, R, D);
-    return pclip_check_launch("cosine_ce (row norms)");
-}
-
-// every (NCH, RF, NDF) ce_rf can ask for
-#define PCLIP_CE_DISPATCH(CALL)                                                                  \
-    do {                                                                                         \
-        if (D <= 512) { if (RF == 4) CALL(1, 4, 8); else if (RF == 2) CALL(1, 2, 8); else CALL(1, 1, 8); } \
-        else if (D <= 1024) { if (RF == 2) CALL(2, 2, 16); else CALL(2, 1, 16); }                \
-        else CALL(4, 1, 32);                                                                     \
-    } while (0)
 
 }  // namespace
 
@@ -604,24 +495,22 @@ extern "C" int pclip_cosine_ce_f16(const void* a, int lda, int M, const void* b,
     const half_t* bw = (const half_t*)b;
     int ldbw = ldb;
     if (flags & PCLIP_CE_NORMALIZE_B) {
-        if (int e = ce_norm_rows((const half_t*)b, ldb, (half_t*)(wsb + w.bn), T, D, s)) return e;
+        if (int e = launch_norm_rows<CE_DMAX>((const half_t*)b, ldb, (half_t*)(wsb + w.bn), T, D, s, "cosine_ce (row norms)")) return e;
         bw = (const half_t*)(wsb + w.bn);
         ldbw = D;
     }
     const int RF = ce_rf_fwd(M, D), npanels = ceil_div(M, 16 * RF);
-    const size_t lds = (size_t)16 * RF * (D + CE_PAD) * 2;
+    const size_t lds = (size_t)16 * RF * (D + PW_PAD) * 2;
     float* tgt = (float*)(wsb + w.tgt);
     float2* colpart = (float2*)(wsb + w.colpart);
-#define PCLIP_CE_FWD(NCH, RFV, NDF)                                                                                                               \
-    do {                                                                                                                                        \
-        static DevOnce attr;                                                                                                                    \
-        if (int e = pclip_raise_lds(attr, {(const void*)ce_fwd_kernel<NCH, RFV>}, CE_LDS_MAX, fn)) return e;                                     \
-        ce_fwd_kernel<NCH, RFV><<<npanels, 64 * CE_FW, lds, s>>>((const half_t*)a, lda, M, bw, ldbw, T, D, scale, (flags & PCLIP_CE_NORMALIZE_A) ? 1 : 0, \
-                                                       symmetric, labels, (flags & PCLIP_CE_LABELS_I64) ? 1 : 0, lse_row, tgt, row_loss, colpart); \
-    } while (0)
-    PCLIP_CE_DISPATCH(PCLIP_CE_FWD);
-#undef PCLIP_CE_FWD
-    if (int e = pclip_check_launch("cosine_ce")) return e;
+    if (int e = panel_dispatch(D, RF, [&](auto nch, auto rf, auto) -> int {
+            static DevOnce attr;
+            if (int e = pclip_raise_lds(attr, {(const void*)ce_fwd_kernel<nch, rf>}, CE_LDS_MAX, fn)) return e;
+            ce_fwd_kernel<nch, rf><<<npanels, 64 * CE_FW, lds, s>>>((const half_t*)a, lda, M, bw, ldbw, T, D, scale, (flags & PCLIP_CE_NORMALIZE_A) ? 1 : 0, symmetric, labels,
+                                                                   (flags & PCLIP_CE_LABELS_I64) ? 1 : 0, lse_row, tgt, row_loss, colpart);
+            return pclip_check_launch("cosine_ce");
+        }))
+        return e;
     if (symmetric) {
         ce_col_combine_kernel<<<ceil_div(T, 256), 256, 0, s>>>(colpart, npanels, T, lse_row, tgt, lse_col, row_loss);
         if (int e = pclip_check_launch("cosine_ce (columns)")) return e;
@@ -655,31 +544,28 @@ extern "C" int pclip_cosine_ce_backward_f16(const void* a, int lda, int M, const
     const void* lab_own = (!symmetric && direction == 0) ? labels : nullptr;
     const void* lab_walk = (!symmetric && direction == 1) ? labels : nullptr;
     if (norm_walk) {
-        if (int e = ce_norm_rows(walk, ldw, (half_t*)(wsb + w.wn), Rw, D, s)) return e;
+        if (int e = launch_norm_rows<CE_DMAX>(walk, ldw, (half_t*)(wsb + w.wn), Rw, D, s, "cosine_ce (row norms)")) return e;
         walk = (const half_t*)(wsb + w.wn);
         ldw = D;
     }
     half_t* walkT = (half_t*)(wsb + w.wt);
-    const int ldt = ce_round64(Rw);
-    ce_transpose_kernel<64><<<dim3(ldt / 64, D / 64), 256, 0, s>>>(walk, ldw, Rw, walkT, ldt);
-    if (int e = pclip_check_launch("cosine_ce_backward (transpose)")) return e;
+    const int ldt = round64(Rw);
+    if (int e = launch_transpose(walk, ldw, Rw, D, walkT, ldt, s, "cosine_ce_backward (transpose)")) return e;
 
-    const int RF = ce_rf(Ro, D), npanels = ceil_div(Ro, 16 * RF);
+    const int RF = rf_for(Ro, D), npanels = ceil_div(Ro, 16 * RF);
     const int nchunks = ce_chunks(Ro, Rw, D, symmetric || direction == 1);
     float* gpanel = nchunks > 1 ? (float*)(wsb + w.part) : grad;
     const dim3 grid(npanels, nchunks);
-    const size_t lds = (size_t)16 * RF * (D + CE_PAD) * 2 + (size_t)4 * 16 * RF * CE_PLD * 2 + 8 * sizeof(int) + 4 * sizeof(float);
+    const size_t lds = (size_t)16 * RF * (D + PW_PAD) * 2 + (size_t)4 * 16 * RF * PW_PLD * 2 + 8 * sizeof(int) + 4 * sizeof(float);
     float* dsc_part = dscale ? (float*)(wsb + w.dsc) : nullptr;
-#define PCLIP_CE_BWD(NCH, RFV, NDF)                                                                                                        \
-    do {                                                                                                                                 \
-        static DevOnce attr;                                                                                                             \
-        if (int e = pclip_raise_lds(attr, {(const void*)ce_bwd_kernel<NCH, RFV, NDF>}, CE_LDS_MAX, fn)) return e;                         \
-        ce_bwd_kernel<NCH, RFV, NDF><<<grid, 256, lds, s>>>(own, ldo, Ro, walk, ldw, Rw, walkT, ldt, D, scale, weight, norm_own, symmetric, lab_own, lab_walk, \
-                                                             (flags & PCLIP_CE_LABELS_I64) ? 1 : 0, lse_own, lse_walk, gpanel, dsc_part);   \
-    } while (0)
-    PCLIP_CE_DISPATCH(PCLIP_CE_BWD);
-#undef PCLIP_CE_BWD
-    if (int e = pclip_check_launch("cosine_ce_backward")) return e;
+    if (int e = panel_dispatch(D, RF, [&](auto nch, auto rf, auto ndf) -> int {
+            static DevOnce attr;
+            if (int e = pclip_raise_lds(attr, {(const void*)ce_bwd_kernel<nch, rf, ndf>}, CE_LDS_MAX, fn)) return e;
+            ce_bwd_kernel<nch, rf, ndf><<<grid, 256, lds, s>>>(own, ldo, Ro, walk, ldw, Rw, walkT, ldt, D, scale, weight, norm_own, symmetric, lab_own, lab_walk,
+                                                              (flags & PCLIP_CE_LABELS_I64) ? 1 : 0, lse_own, lse_walk, gpanel, dsc_part);
+            return pclip_check_launch("cosine_ce_backward");
+        }))
+        return e;
     if (nchunks > 1) {
         const size_t n = (size_t)Ro * D;
         size_t g = (n / 4 + 255) / 256;

@@ -1,6 +1,7 @@
 // Cosine-similarity logits: the contrastive forward of CLIP (clip/model.py:356-370) and the zero-shot line `100. * features @ clip_weights`, ragged in M and T.
 //   logits[m, t] = r16( sum_d r16(scale * a'[m, d]) * b'[t, d] ),  a' / b' = the rows as given or L2-normalised with the arithmetic of pclip_l2norm_rows_f16.
-// A workgroup (four waves) owns a panel of 16 RF rows of `a` (RF = 1, 2, 4 by M; at most 4 up to D = 1024, 2 up to 2048, 1 beyond) and walks the rows of `b`:
+// The panel walk of pclip_panel_walk.h (staging, operand layout; the one-step-ahead loop over FOUR walked fragments is written out here).  What is this file's own:
+// a workgroup (four waves) owns a panel of 16 RF rows of `a` (RF = 1, 2, 4 by M; at most 4 up to D = 1024, 2 up to 2048, 1 beyond) and walks the rows of `b`:
 //   * the panel goes to LDS ONCE, already normalised and scaled (one wave per row: the very loads, butterfly and division chain of l2norm_rows_kernel, then
 //     r16(scale * .) as an fp32 product rounded to fp16), rows D + 8 halves apart so that ds_read_b128 in the MFMA operand layout (lane = row l & 15, k-chunk
 //     l >> 4) spreads over the banks; rows >= M are zeros and never read from memory;
@@ -18,28 +19,11 @@
 // Only __syncthreads barriers and compiler-counted waits: nothing here for the race-stress build.
 // What bounds it: at M >> T every panel re-reads `b` through L2 (M / (16 RF) x T D 2 bytes) — see DESIGN section 3 and profiles/cosine_logits.txt
 // (the plain matrix at 50 000 x 1000 is about 30 % slower than a GEMM that stages both operands in LDS).
-#include "pclip_proto_dev.h"
+#include "pclip_panel_walk.h"
 
 namespace {
 
-constexpr int LG_PAD = 8;                      // halves between the LDS rows of the panel beyond D
 constexpr int LG_LDS_MAX = 160 * 1024;
-
-// rows of `b` normalised into the workspace (dense [R, D])
-template <int NCH>
-__global__ __launch_bounds__(256) void logits_norm_rows_kernel(const half_t* __restrict__ x, int ldx, half_t* __restrict__ y, int R, int D) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int row = blockIdx.x * 4 + wave; row < R; row += gridDim.x * 4) {
-        RowRegs<NCH> r;
-        load_row<NCH>(x + (size_t)row * ldx, D, lane, r);
-        normalise_row<NCH>(r);
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const int d = c * 512 + lane * 8;
-            if (d < D) st_half8(y + (size_t)row * D + d, r.v[c]);
-        }
-    }
-}
 
 template <int NCH, int RF, int KMAX>
 __global__ __launch_bounds__(256) void cosine_logits_kernel(const half_t* __restrict__ a, int lda, int M, const half_t* __restrict__ b, int ldb, int T, int D,
@@ -47,34 +31,12 @@ __global__ __launch_bounds__(256) void cosine_logits_kernel(const half_t* __rest
                                                             half_t* __restrict__ topk_v, int32_t* __restrict__ topk_i, int k, int keff) {
     extern __shared__ __attribute__((aligned(16))) char lg_smem[];
     half_t* panel = reinterpret_cast<half_t*>(lg_smem);                                      // [16 RF][D + 8]
-    const int LDP = D + LG_PAD;
+    const int LDP = D + PW_PAD;
     unsigned* lists = reinterpret_cast<unsigned*>(lg_smem);                                  // after the walk, over the panel: [256 threads][RF][KMAX] keys, descending, 0 = empty
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int m0 = blockIdx.x * 16 * RF;
 
-    // ---- the panel: normalised, scaled, rounded; one wave per row -------------------------------------------------------------------
-    for (int r = wave; r < 16 * RF; r += 4) {
-        const int m = m0 + r;
-        RowRegs<NCH> rr;
-        if (m < M) {                                                                         // (wave-uniform)
-            load_row<NCH>(a + (size_t)m * lda, D, lane, rr);
-            if (norm_a) normalise_row<NCH>(rr);
-#pragma unroll
-            for (int c = 0; c < NCH; ++c)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) rr.v[c][j] = scale_r16(scale, rr.v[c][j]);
-        } else {
-#pragma unroll
-            for (int c = 0; c < NCH; ++c)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) rr.v[c][j] = (half_t)0.f;
-        }
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const int d = c * 512 + lane * 8;
-            if (d < D) st_half8(panel + (size_t)r * LDP + d, rr.v[c]);
-        }
-    }
+    stage_panel<NCH, 4, true>(panel, LDP, a, lda, M, D, m0, 16 * RF, lane, wave, norm_a, scale);              // normalised, scaled, rounded
     unsigned best[RF][KMAX > 0 ? KMAX : 1];                                                  // this lane's KMAX best keys per row fragment, descending
 #pragma unroll
     for (int f = 0; f < RF; ++f)
@@ -89,11 +51,7 @@ __global__ __launch_bounds__(256) void cosine_logits_kernel(const half_t* __rest
         const int t0 = cb * 64;
         const half_t* bp[4];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            int t = t0 + 16 * c + lr;
-            t = t < T ? t : T - 1;
-            bp[c] = b + (size_t)t * ldb + lq * 8;
-        }
+        for (int c = 0; c < 4; ++c) bp[c] = walked_row(b, ldb, t0 + 16 * c + lr, T, lq);
         const half_t* ap = panel + (size_t)lr * LDP + lq * 8;
         float4_t acc[RF][4];
 #pragma unroll
@@ -189,7 +147,7 @@ __global__ __launch_bounds__(256) void cosine_logits_kernel(const half_t* __rest
 
 inline int logits_kmax(int keff) { return keff == 0 ? 0 : (keff == 1 ? 1 : (keff <= 8 ? 8 : 16)); }
 inline size_t logits_lds(int D, int RF, int kmax) {                                          // the panel, later the lists over it
-    const size_t panel = (size_t)16 * RF * (D + LG_PAD) * 2, lists = (size_t)256 * RF * kmax * 4;
+    const size_t panel = (size_t)16 * RF * (D + PW_PAD) * 2, lists = (size_t)256 * RF * kmax * 4;
     return panel > lists ? panel : lists;
 }
 
@@ -202,15 +160,15 @@ extern "C" int pclip_cosine_logits_f16(const void* a, int lda, int M, const void
     PCLIP_REQUIRE(M >= 1 && T >= 1, "%s: M=%d and T=%d must be positive", fn, M, T);
     PCLIP_REQUIRE(D > 0 && D % 64 == 0 && D <= 4096, "%s: D=%d must be a multiple of 64, <= 4096", fn, D);
     PCLIP_REQUIRE((flags & ~(PCLIP_LOGITS_NORMALIZE_A | PCLIP_LOGITS_NORMALIZE_B)) == 0, "%s: unknown flag bits 0x%x", fn, flags);
-    PCLIP_REQUIRE(lda >= D && lda % 8 == 0, "%s: lda=%d must be >= D=%d and a multiple of 8 halves", fn, lda, D);
-    PCLIP_REQUIRE(ldb >= D && ldb % 8 == 0, "%s: ldb=%d must be >= D=%d and a multiple of 8 halves", fn, ldb, D);
+    PCLIP_REQUIRE_PITCH(fn, lda, D);
+    PCLIP_REQUIRE_PITCH(fn, ldb, D);
     PCLIP_REQUIRE(k >= 0 && k <= 16 && k <= T, "%s: k=%d must be in [0, min(16, T=%d)]", fn, k, T);
     PCLIP_REQUIRE((k > 0) == (topk_v != nullptr) && (k > 0) == (topk_i != nullptr), "%s: k=%d needs both top-k outputs, k = 0 neither", fn, k);
     PCLIP_REQUIRE(logits || argmax || k > 0, "%s: no output requested", fn);
     PCLIP_REQUIRE(!logits || (ldl >= T && ldl % 8 == 0), "%s: ldl=%d must be >= T=%d and a multiple of 8 halves", fn, ldl, T);
     const bool fused = argmax || k > 0;
     PCLIP_REQUIRE(!fused || T <= 4096, "%s: argmax / top-k need T=%d <= 4096 (the logits alone have no cap)", fn, T);
-    PCLIP_REQUIRE(((uintptr_t)a | (uintptr_t)b | (uintptr_t)logits) % 16 == 0, "%s: operands must be 16-byte aligned", fn);
+    PCLIP_REQUIRE_ALIGNED(fn, (uintptr_t)a | (uintptr_t)b | (uintptr_t)logits, 0);
     const half_t* bw = (const half_t*)b;
     int ldbw = ldb;
     hipStream_t s = (hipStream_t)stream;
@@ -239,15 +197,7 @@ extern "C" int pclip_cosine_logits_f16(const void* a, int lda, int M, const void
     }
 
     if (flags & PCLIP_LOGITS_NORMALIZE_B) {
-        int g = ceil_div(T, 4);
-        g = g > 8192 ? 8192 : g;
-#define PCLIP_LG_NORM(NCH) logits_norm_rows_kernel<NCH><<<g, 256, 0, s>>>((const half_t*)b, ldb, (half_t*)ws, T, D)
-        if (D <= 512) PCLIP_LG_NORM(1);
-        else if (D <= 1024) PCLIP_LG_NORM(2);
-        else if (D <= 2048) PCLIP_LG_NORM(4);
-        else PCLIP_LG_NORM(8);
-#undef PCLIP_LG_NORM
-        if (int e = pclip_check_launch("cosine_logits (row norms)")) return e;
+        if (int e = launch_norm_rows<4096>((const half_t*)b, ldb, (half_t*)ws, T, D, s, "cosine_logits (row norms)")) return e;
         bw = (const half_t*)ws;
         ldbw = D;
     }
@@ -268,6 +218,7 @@ extern "C" int pclip_cosine_logits_f16(const void* a, int lda, int M, const void
         else PCLIP_LG(NCH, RFV, 16);                       \
     } while (0)
     // (RF <= rfmax above: 4 up to D = 1024, 2 up to 2048, 1 beyond — every (NCH, RF) that can arrive here is compiled, and RF matches `grid` and `lds`)
+    // not panel_dispatch: no accumulator panel caps RF here (4 up to D = 1024), D goes on to 4096 (NCH = 8), and every form fans out over KMAX instead of an NDF
     if (D <= 512) { if (RF == 4) PCLIP_LG_K(1, 4); else if (RF == 2) PCLIP_LG_K(1, 2); else PCLIP_LG_K(1, 1); }
     else if (D <= 1024) { if (RF == 4) PCLIP_LG_K(2, 4); else if (RF == 2) PCLIP_LG_K(2, 2); else PCLIP_LG_K(2, 1); }
     else if (D <= 2048) { if (RF == 2) PCLIP_LG_K(4, 2); else if (RF == 1) PCLIP_LG_K(4, 1); else { pclip_set_error("%s: no kernel for D=%d with %d row fragments", fn, D, RF); return PCLIP_E_INVALID; } }

@@ -60,46 +60,6 @@ __device__ __forceinline__ void normalise_row(RowRegs<NCH>& r) {
     }
 }
 
-// ---- fp16 logits: the operand scaling and the argmax / top-k keys of pclip_logits.hip, shared with pclip_tip.hip -------------------------------
-// the rounded fp16 logit and its column as one 32-bit key (order-preserving value bits | 0xFFFF - column: greater = larger value, then lower column; -0 counts as +0)
-__device__ __forceinline__ unsigned logit_key(half_t v, int t) {
-    unsigned b = __builtin_bit_cast(unsigned short, v);
-    if (b == 0x8000u) b = 0;                                                    // -0 == +0: the lower column wins
-    const unsigned o = (b & 0x8000u) ? (~b & 0xFFFFu) : (b | 0x8000u);
-    return (o << 16) | (0xFFFFu - (unsigned)t);
-}
-__device__ __forceinline__ half_t key_value(unsigned key) {
-    const unsigned o = key >> 16;
-    const unsigned b = (o & 0x8000u) ? (o & 0x7FFFu) : (~o & 0xFFFFu);
-    return __builtin_bit_cast(half_t, (unsigned short)b);
-}
-
-// r16(s * v): the fp32 product rounded to fp32, then to fp16 (torch's fp16 tensor times a scalar) — not one fused rounding
-__device__ __forceinline__ half_t scale_r16(float s, half_t v) {
-#pragma clang fp contract(off)
-    const float p = s * (float)v;
-    return (half_t)p;
-}
-
-// ---- the walked operand of a recomputing backward, transposed (pclip_cosine_ce.hip, pclip_tip.hip) --------------------------------------------------
-// y [D][ldt] = x^T, 64 x 64 tiles through LDS; rows R .. ldt - 1 of x read as zeros (ldt = R rounded up to 64: every column of y is written)
-// (a template, TS = 64 the one tile size: only the files that launch it instantiate it)
-template <int TS>
-__global__ __launch_bounds__(256) void ce_transpose_kernel(const half_t* __restrict__ x, int ldx, int R, half_t* __restrict__ y, int ldt) {
-    static_assert(TS == 64, "ce_transpose_kernel: 64 x 64 tiles");
-    __shared__ half_t tile[64][66];
-    const int r0 = blockIdx.x * 64, d0 = blockIdx.y * 64;
-    for (int i = threadIdx.x; i < 64 * 64; i += 256) {
-        const int r = i >> 6, c = i & 63;
-        tile[r][c] = r0 + r < R ? x[(size_t)(r0 + r) * ldx + d0 + c] : (half_t)0.f;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 64 * 64; i += 256) {
-        const int c = i >> 6, r = i & 63;
-        y[(size_t)(d0 + c) * ldt + r0 + r] = tile[r][c];
-    }
-}
-
 // ---- shared tail: fp32 class sum -> z=r16(sum/cnt) -> fp16 / fp32 normalised prototype ----------
 // Executed by ONE wave; acc[c][j] holds this lane's slice of the class sum.
 template <int NCH>

@@ -6,6 +6,8 @@
 //   S[q, n]    = (((0 + E[q, seg[n]]) + E[q, seg[n] + 1]) + ...) + E[q, seg[n + 1] - 1]: ONE fp32 accumulator per (q, n), strictly in ascending j
 //   c[q, n]    = the accumulator of cosine_logits_kernel before its rounding: r16(scale * f) against w, the class rows as the first MFMA operand, same k order
 //   logit[q,n] = r16(fmaf(alpha, S, c))                                                                                  (one fma, one fp16 rounding)
+// The panel walk of pclip_panel_walk.h.  The key gradient is built from its staging and its recomputing-backward skeleton; tip_kernel keeps its staging and its two
+// one-step-ahead walks written out (its schedule at the ImageNet split moved by 2 % with either of them behind a function: profiles/panel_walk_refactor.txt).
 // A workgroup (four waves) owns a panel of 16 RF query rows, in LDS once and unscaled (the zero-shot product scales its fragments on the way to the MFMA), and
 // walks the classes in blocks of 64:
 //   * zero-shot tile: wave w forms c for classes n0 + 16 w .. + 15 against the whole panel -> LDS [query][class];
@@ -15,7 +17,7 @@
 //     the value the previous tile left, so the association above holds whatever the tiles, the panel or the grid are.  Rows past the block or past NK are
 //     clamped reads whose E nobody adds;
 //   * the block's logits from S and c: written (fp16 and / or fp32) with a thread per class, so stores are contiguous, and folded into the per-query best key
-//     (logit_key of pclip_logits.hip: value, then lower column) that lives in registers across the blocks.
+//     (logit_key of pclip_panel_walk.h: value, then lower column) that lives in registers across the blocks.
 // Grid kernel: blockIdx.y is a chunk of TP_NBG betas; every (beta, alpha) pair of the chunk keeps its best key per query in registers, the keys are merged
 // across a query's threads with integer LDS maxima, compared with the label and counted; the counts are integer sums (LDS, then one global integer atomic per pair and
 // workgroup), so they carry no order.  No floating-point atomics anywhere.
@@ -29,11 +31,10 @@
 // Only __syncthreads barriers and compiler-counted waits: nothing here for the race-stress build.
 // What bounds it: the segment sums are one thread per (query, class) — with fewer than 64 / P classes in a tile (more than ~16 shots per class) threads idle there;
 // and the grid's argmax is Q N nb na fma + round + key + max on the VALU, which no tiling removes.  profiles/tip_adapter.txt.
-#include "pclip_proto_dev.h"
+#include "pclip_panel_walk.h"
 
 namespace {
 
-constexpr int TP_PAD = 8;                      // halves between the LDS rows of the panel beyond D
 constexpr int TP_CB = 64;                      // classes per block = key rows per tile
 constexpr int TP_TLD = 65;                     // floats per LDS row of the c / S / E tiles (64 + 1: a column is read by consecutive queries conflict-free)
 constexpr int TP_LDS_MAX = 160 * 1024;
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(256) void tip_kernel(const half_t* __restrict__ f, 
                                                   int32_t* __restrict__ argmax, int32_t* __restrict__ correct) {
     constexpr int R = 16 * RF, P = 256 / R, TILE = R * TP_TLD;
     extern __shared__ __attribute__((aligned(16))) char tp_smem[];
-    const int LDP = D + TP_PAD;
+    const int LDP = D + PW_PAD;
     half_t* panel = reinterpret_cast<half_t*>(tp_smem);                                      // [R][D + 8]
     float* ctile = reinterpret_cast<float*>(panel + (size_t)R * LDP);                        // [R][65]: c of the class block
     float* stile = ctile + TILE;                                                             // [NB][R][65]: S of the class block
@@ -277,8 +278,6 @@ __global__ __launch_bounds__(256) void tip_kernel(const half_t* __restrict__ f, 
 }
 
 // ---- the key gradient ---------------------------------------------------------------------------------------------------------------------------
-constexpr int TP_PLD = 72;                     // halves per LDS row of the G tile (64 queries + 8: 16-byte reads spread over the banks)
-
 // cls[j] = the class that owns key row j (the c with seg[c] <= j < seg[c + 1]; N - 1 where seg says none), and gmax = the bits of max |dL| (integer maximum)
 __global__ __launch_bounds__(256) void tip_bwd_prep_kernel(const int32_t* __restrict__ seg, int N, int NK, int32_t* __restrict__ cls, const float* __restrict__ dL,
                                                            size_t ndl, unsigned* __restrict__ gmax) {
@@ -303,27 +302,12 @@ __global__ __launch_bounds__(256) void tip_bwd_kernel(const half_t* __restrict__
                                                       const half_t* __restrict__ fT, int ldt, int D, float alpha, float beta, const int32_t* __restrict__ cls,
                                                       const float* __restrict__ dL, int N, const unsigned* __restrict__ gmax, float* __restrict__ gout) {
     extern __shared__ __attribute__((aligned(16))) char tp_smem[];
-    const int LDP = D + TP_PAD;
+    const int LDP = D + PW_PAD;
     half_t* panel = reinterpret_cast<half_t*>(tp_smem);                                      // [16 RF][D + 8]: this workgroup's key rows
-    half_t* gtile = panel + (size_t)16 * RF * LDP;                                           // [2][16 RF][TP_PLD]: r16(2^s G), key row x query
+    half_t* gtile = panel + (size_t)16 * RF * LDP;                                           // [2][16 RF][PW_PLD]: r16(2^s G), key row x query
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i0 = blockIdx.x * 16 * RF;
-    for (int r = wave; r < 16 * RF; r += 4) {
-        RowRegs<NCH> rr;
-        if (i0 + r < NK) {                                                                   // (wave-uniform)
-            load_row<NCH>(keys + (size_t)(i0 + r) * ldk, D, lane, rr);
-        } else {
-#pragma unroll
-            for (int c = 0; c < NCH; ++c)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) rr.v[c][j] = (half_t)0.f;
-        }
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const int d = c * 512 + lane * 8;
-            if (d < D) st_half8(panel + (size_t)r * LDP + d, rr.v[c]);
-        }
-    }
+    stage_panel<NCH, 4>(panel, LDP, keys, ldk, NK, D, i0, 16 * RF, lane, wave, 0);
     // 2^s: max |dL| = m 2^e with m in [0.5, 1), s = 14 - e (capped: a gradient of denormals keeps a finite scale)
     float gs = 1.f, ginv = 1.f;
     {
@@ -353,38 +337,18 @@ __global__ __launch_bounds__(256) void tip_bwd_kernel(const half_t* __restrict__
     __syncthreads();
 
     const int KS = D >> 5, ntiles = (Q + 63) >> 6;
-    const half_t* wp;                                                                        // this wave's query row of the tile at hand (clamped), and its first two k-steps
-    {
-        int qr = 16 * wave + lr;
-        qr = qr < Q ? qr : Q - 1;
-        wp = f + (size_t)qr * ldf + lq * 8;
-    }
+    // this wave's query row of the tile at hand, and its first two k-steps
+    const half_t* wp = walked_row(f, ldf, 16 * wave + lr, Q, lq);
     half8_t c0 = ld_half8(wp), c1 = ld_half8(wp + 32);
     for (int tile = 0; tile < ntiles; ++tile) {
         const int q0 = tile * 64, buf = tile & 1;
-        // ---- aff of queries q0 + 16 wave .. + 15 against the panel: k-steps in pairs (KS is even), the next pair in flight, the next tile's first under the last ----
-        int qn = q0 + 64 + 16 * wave + lr;
-        qn = qn < Q ? qn : Q - 1;
-        const half_t* wpn = f + (size_t)qn * ldf + lq * 8;
-        const half_t* ap = panel + (size_t)lr * LDP + lq * 8;
+        // ---- aff of queries q0 + 16 wave .. + 15 against the panel ----------------------------------------------------------------------------
         float4_t acc[RF];
-#pragma unroll
-        for (int fr = 0; fr < RF; ++fr) acc[fr] = float4_t{0.f, 0.f, 0.f, 0.f};
-        for (int ks = 0; ks < KS; ks += 2) {
-            const half_t* np = ks + 2 < KS ? wp + (ks + 2) * 32 : wpn;
-            const half8_t n0 = ld_half8(np), n1 = ld_half8(np + 32);
-#pragma unroll
-            for (int fr = 0; fr < RF; ++fr) acc[fr] = __builtin_amdgcn_mfma_f32_16x16x32_f16(c0, ld_half8(ap + (size_t)fr * 16 * LDP + ks * 32), acc[fr], 0, 0, 0);
-#pragma unroll
-            for (int fr = 0; fr < RF; ++fr) acc[fr] = __builtin_amdgcn_mfma_f32_16x16x32_f16(c1, ld_half8(ap + (size_t)fr * 16 * LDP + ks * 32 + 32), acc[fr], 0, 0, 0);
-            c0 = n0, c1 = n1;
-        }
+        const half_t* wpn = walked_row(f, ldf, q0 + 64 + 16 * wave + lr, Q, lq);
+        bwd_first_product<RF>(wp, wpn, c0, c1, panel + (size_t)lr * LDP + lq * 8, LDP, KS, acc);
         wp = wpn;
-        // the first eight column fragments of the second product's query operand: in flight under the exponentials and the barrier
         half8_t wt0[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-            wt0[u] = u < ndf ? ld_half8(fT + (size_t)(dbase + 16 * u + lr) * ldt + q0 + 8 * lq) : half8_t{};
+        bwd_prefetch_t(wt0, fT, ldt, dbase, ndf, q0, lr, lq);                                // in flight under the exponentials and the barrier
         // acc[fr][r] = aff(key i0 + 16 fr + lr, query q0 + 16 wave + 4 lq + r)
         const int qb = q0 + 16 * wave + 4 * lq;
 #pragma unroll
@@ -398,50 +362,14 @@ __global__ __launch_bounds__(256) void tip_bwd_kernel(const half_t* __restrict__
                 const float e = __expf(__builtin_fmaf(beta, acc[fr][r], -beta));
                 g16[r] = ok ? (half_t)((up * e) * gs) : (half_t)0.f;
             }
-            *reinterpret_cast<half4_t*>(gtile + ((size_t)buf * 16 * RF + 16 * fr + lr) * TP_PLD + 16 * wave + 4 * lq) = g16;
+            *reinterpret_cast<half4_t*>(gtile + ((size_t)buf * 16 * RF + 16 * fr + lr) * PW_PLD + 16 * wave + 4 * lq) = g16;
         }
         __syncthreads();                                                                     // the tile is whole; the other buffer is free once every wave is here
         // ---- this wave's quarter of D: acc2 += f^T G, the query index along k ----------------------------------------------------------------
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            half8_t pf[RF];
-#pragma unroll
-            for (int fr = 0; fr < RF; ++fr) pf[fr] = ld_half8(gtile + ((size_t)buf * 16 * RF + 16 * fr + lr) * TP_PLD + 32 * p + 8 * lq);
-#pragma unroll
-            for (int g = 0; g < NDF / 8; ++g) {
-                half8_t wt[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    if (p == 0 && g == 0) wt[u] = wt0[u];
-                    else wt[u] = 8 * g + u >= ndf ? half8_t{} : ld_half8(fT + (size_t)(dbase + 16 * (8 * g + u) + lr) * ldt + q0 + 32 * p + 8 * lq);
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int df = 8 * g + u;
-                    if (df < ndf) {                                                          // (uniform)
-#pragma unroll
-                        for (int fr = 0; fr < RF; ++fr) acc2[fr][df] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wt[u], pf[fr], acc2[fr][df], 0, 0, 0);
-                    }
-                }
-            }
-        }
+        bwd_second_product<RF, NDF, false>(fT, ldt, dbase, ndf, q0, wt0, gtile, nullptr, false, buf, lr, lq, acc2);
     }
     // acc2[fr][df][r] = 2^s sum_q G[i0 + 16 fr + lr, q] f[q, dbase + 16 df + 4 lq + r]
-    const float mul = (alpha * beta) * ginv;
-#pragma unroll
-    for (int fr = 0; fr < RF; ++fr) {
-        const int j = i0 + 16 * fr + lr;
-        if (j >= NK) continue;
-#pragma unroll
-        for (int df = 0; df < NDF; ++df) {
-            if (df < ndf) {
-                float4_t o = acc2[fr][df];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[r] *= mul;
-                *reinterpret_cast<float4_t*>(gout + (size_t)j * D + dbase + 16 * df + 4 * lq) = o;
-            }
-        }
-    }
+    store_grad_panel<RF, NDF>(gout, i0, NK, D, dbase, ndf, (alpha * beta) * ginv, lr, lq, acc2);
 }
 
 struct TipBwdWs {
@@ -450,7 +378,7 @@ struct TipBwdWs {
 inline TipBwdWs tip_bwd_ws(int Q, int NK, int D) {
     TipBwdWs w;
     size_t off = 0;
-    w.ft = off, off += align_up((size_t)D * ((Q + 63) / 64 * 64) * 2, 256);
+    w.ft = off, off += align_up((size_t)D * round64(Q) * 2, 256);
     w.cls = off, off += align_up((size_t)NK * 4, 256);
     w.gmax = off, off += 256;
     w.bytes = off;
@@ -458,7 +386,7 @@ inline TipBwdWs tip_bwd_ws(int Q, int NK, int D) {
 }
 
 inline size_t tip_lds(int D, int RF, int NB) {
-    return (size_t)16 * RF * (D + TP_PAD) * 2 + (size_t)(1 + 2 * NB) * 16 * RF * TP_TLD * 4 + (TP_CB + 1 + TP_NBG * TP_NA) * 4;
+    return (size_t)16 * RF * (D + PW_PAD) * 2 + (size_t)(1 + 2 * NB) * 16 * RF * TP_TLD * 4 + (TP_CB + 1 + TP_NBG * TP_NA) * 4;
 }
 
 int tip_validate(const char* fn, const void* f, int ldf, int Q, const void* keys, int ldk, int NK, const int32_t* seg, const void* w, int ldw, int N, int D) {
@@ -467,10 +395,10 @@ int tip_validate(const char* fn, const void* f, int ldf, int Q, const void* keys
     PCLIP_REQUIRE(N >= 1 && N <= 4096, "%s: N=%d must be in [1, 4096] (the fused argmax's cap)", fn, N);
     PCLIP_REQUIRE(NK >= 0 && (NK == 0 || keys), "%s: NK=%d key rows need a key pointer", fn, NK);
     PCLIP_REQUIRE(D > 0 && D % 64 == 0 && D <= 2048, "%s: D=%d must be a multiple of 64, <= 2048", fn, D);
-    PCLIP_REQUIRE(ldf >= D && ldf % 8 == 0, "%s: ldf=%d must be >= D=%d and a multiple of 8 halves", fn, ldf, D);
-    PCLIP_REQUIRE(ldk >= D && ldk % 8 == 0, "%s: ldk=%d must be >= D=%d and a multiple of 8 halves", fn, ldk, D);
-    PCLIP_REQUIRE(ldw >= D && ldw % 8 == 0, "%s: ldw=%d must be >= D=%d and a multiple of 8 halves", fn, ldw, D);
-    PCLIP_REQUIRE(((uintptr_t)f | (uintptr_t)keys | (uintptr_t)w) % 16 == 0 && (uintptr_t)seg % 4 == 0, "%s: operands must be 16-byte aligned", fn);
+    PCLIP_REQUIRE_PITCH(fn, ldf, D);
+    PCLIP_REQUIRE_PITCH(fn, ldk, D);
+    PCLIP_REQUIRE_PITCH(fn, ldw, D);
+    PCLIP_REQUIRE_ALIGNED(fn, (uintptr_t)f | (uintptr_t)keys | (uintptr_t)w, (uintptr_t)seg);
     return PCLIP_OK;
 }
 inline bool tip_coef_ok(float v) { return v >= 0.f && v <= 3.0e38f; }                       // (false for NaN and inf)
@@ -490,9 +418,9 @@ extern "C" int pclip_tip_keys_backward_f16(const void* f, int ldf, int Q, const 
     PCLIP_REQUIRE(N >= 1 && N <= 4096, "%s: N=%d must be in [1, 4096]", fn, N);
     PCLIP_REQUIRE(NK >= 0 && (NK == 0 || (keys && dkeys)), "%s: NK=%d key rows need the keys and their gradient", fn, NK);
     PCLIP_REQUIRE(D > 0 && D % 64 == 0 && D <= 2048, "%s: D=%d must be a multiple of 64, <= 2048", fn, D);
-    PCLIP_REQUIRE(ldf >= D && ldf % 8 == 0, "%s: ldf=%d must be >= D=%d and a multiple of 8 halves", fn, ldf, D);
-    PCLIP_REQUIRE(ldk >= D && ldk % 8 == 0, "%s: ldk=%d must be >= D=%d and a multiple of 8 halves", fn, ldk, D);
-    PCLIP_REQUIRE(((uintptr_t)f | (uintptr_t)keys | (uintptr_t)dkeys) % 16 == 0 && ((uintptr_t)seg | (uintptr_t)dL) % 4 == 0, "%s: operands must be 16-byte aligned", fn);
+    PCLIP_REQUIRE_PITCH(fn, ldf, D);
+    PCLIP_REQUIRE_PITCH(fn, ldk, D);
+    PCLIP_REQUIRE_ALIGNED(fn, (uintptr_t)f | (uintptr_t)keys | (uintptr_t)dkeys, (uintptr_t)seg | (uintptr_t)dL);
     PCLIP_REQUIRE(tip_coef_ok(alpha) && tip_coef_ok(beta), "%s: alpha=%g and beta=%g must be finite and >= 0", fn, (double)alpha, (double)beta);
     const TipBwdWs w = tip_bwd_ws(Q, NK, D);
     PCLIP_REQUIRE(ws != nullptr && (uintptr_t)ws % 16 == 0, "%s: needs a 16-byte aligned workspace", fn);
@@ -503,31 +431,23 @@ extern "C" int pclip_tip_keys_backward_f16(const void* f, int ldf, int Q, const 
     half_t* fT = (half_t*)(wsb + w.ft);
     int32_t* cls = (int32_t*)(wsb + w.cls);
     unsigned* gmax = (unsigned*)(wsb + w.gmax);
-    const int ldt = (Q + 63) / 64 * 64;
+    const int ldt = round64(Q);
     if (hipMemsetAsync(gmax, 0, 4, s) != hipSuccess) { pclip_set_error("%s: cannot clear the workspace", fn); return PCLIP_E_LAUNCH; }
     const size_t ndl = (size_t)Q * N;
     size_t g = ((ndl > (size_t)NK ? ndl : (size_t)NK) + 255) / 256;
     g = g > 2048 ? 2048 : g;
     tip_bwd_prep_kernel<<<(int)g, 256, 0, s>>>(seg, N, NK, cls, dL, ndl, gmax);
     if (int e = pclip_check_launch("tip_keys_backward (classes, max)")) return e;
-    ce_transpose_kernel<64><<<dim3(ldt / 64, D / 64), 256, 0, s>>>((const half_t*)f, ldf, Q, fT, ldt);
-    if (int e = pclip_check_launch("tip_keys_backward (transpose)")) return e;
-    const int rfmax = D <= 512 ? 4 : (D <= 1024 ? 2 : 1);                                   // the accumulator panel: RF D / 16 registers per lane <= 128
-    int RF = NK <= 16 ? 1 : (NK <= 32 ? 2 : 4);
-    RF = RF > rfmax ? rfmax : RF;
-    const size_t lds = (size_t)16 * RF * (D + TP_PAD) * 2 + (size_t)2 * 16 * RF * TP_PLD * 2;
+    if (int e = launch_transpose((const half_t*)f, ldf, Q, D, fT, ldt, s, "tip_keys_backward (transpose)")) return e;
+    const int RF = rf_for(NK, D);
+    const size_t lds = (size_t)16 * RF * (D + PW_PAD) * 2 + (size_t)2 * 16 * RF * PW_PLD * 2;
     const int npanels = ceil_div(NK, 16 * RF);
-#define PCLIP_TIP_BWD(NCH, RFV, NDF)                                                                                                               \
-    do {                                                                                                                                         \
-        static DevOnce attr;                                                                                                                     \
-        if (int e = pclip_raise_lds(attr, {(const void*)tip_bwd_kernel<NCH, RFV, NDF>}, TP_LDS_MAX, fn)) return e;                                \
-        tip_bwd_kernel<NCH, RFV, NDF><<<npanels, 256, lds, s>>>((const half_t*)keys, ldk, NK, (const half_t*)f, ldf, Q, fT, ldt, D, alpha, beta, cls, dL, N, gmax, dkeys); \
-    } while (0)
-    if (D <= 512) { if (RF == 4) PCLIP_TIP_BWD(1, 4, 8); else if (RF == 2) PCLIP_TIP_BWD(1, 2, 8); else PCLIP_TIP_BWD(1, 1, 8); }
-    else if (D <= 1024) { if (RF == 2) PCLIP_TIP_BWD(2, 2, 16); else PCLIP_TIP_BWD(2, 1, 16); }
-    else PCLIP_TIP_BWD(4, 1, 32);
-#undef PCLIP_TIP_BWD
-    return pclip_check_launch("tip_keys_backward");
+    return panel_dispatch(D, RF, [&](auto nch, auto rf, auto ndf) -> int {
+        static DevOnce attr;
+        if (int e = pclip_raise_lds(attr, {(const void*)tip_bwd_kernel<nch, rf, ndf>}, TP_LDS_MAX, fn)) return e;
+        tip_bwd_kernel<nch, rf, ndf><<<npanels, 256, lds, s>>>((const half_t*)keys, ldk, NK, (const half_t*)f, ldf, Q, fT, ldt, D, alpha, beta, cls, dL, N, gmax, dkeys);
+        return pclip_check_launch("tip_keys_backward");
+    });
 }
 
 extern "C" int pclip_tip_logits_f16(const void* f, int ldf, int Q, const void* keys, int ldk, int NK, const int32_t* seg, const void* w, int ldw, int N, int D,
@@ -550,18 +470,13 @@ extern "C" int pclip_tip_logits_f16(const void* f, int ldf, int Q, const void* k
         ysplit = ysplit > nblocks ? nblocks : ysplit;
     }
     const dim3 grid(npanels, ysplit);
-#define PCLIP_TIP(NCH, RFV)                                                                                                                        \
-    do {                                                                                                                                         \
-        static DevOnce attr;                                                                                                                     \
-        if (int e = pclip_raise_lds(attr, {(const void*)tip_kernel<NCH, RFV, 1, false>}, TP_LDS_MAX, fn)) return e;                               \
-        tip_kernel<NCH, RFV, 1, false><<<grid, 256, lds, s>>>((const half_t*)f, ldf, Q, (const half_t*)keys, ldk, NK, seg, (const half_t*)w, ldw, N, D, scale, alpha, \
-                                                              beta, nullptr, 0, nullptr, 0, nullptr, (half_t*)logits, ldl, logits32, argmax, nullptr); \
-    } while (0)
-    if (D <= 512) { if (RF == 4) PCLIP_TIP(1, 4); else if (RF == 2) PCLIP_TIP(1, 2); else PCLIP_TIP(1, 1); }
-    else if (D <= 1024) { if (RF == 2) PCLIP_TIP(2, 2); else PCLIP_TIP(2, 1); }
-    else PCLIP_TIP(4, 1);
-#undef PCLIP_TIP
-    return pclip_check_launch("tip_logits");
+    return panel_dispatch(D, RF, [&](auto nch, auto rf, auto) -> int {
+        static DevOnce attr;
+        if (int e = pclip_raise_lds(attr, {(const void*)tip_kernel<nch, rf, 1, false>}, TP_LDS_MAX, fn)) return e;
+        tip_kernel<nch, rf, 1, false><<<grid, 256, lds, s>>>((const half_t*)f, ldf, Q, (const half_t*)keys, ldk, NK, seg, (const half_t*)w, ldw, N, D, scale, alpha, beta,
+                                                            nullptr, 0, nullptr, 0, nullptr, (half_t*)logits, ldl, logits32, argmax, nullptr);
+        return pclip_check_launch("tip_logits");
+    });
 }
 
 extern "C" int pclip_tip_grid_f16(const void* f, int ldf, int Q, const void* keys, int ldk, int NK, const int32_t* seg, const void* w, int ldw, int N, int D,
@@ -582,16 +497,11 @@ extern "C" int pclip_tip_grid_f16(const void* f, int ldf, int Q, const void* key
     while (RF > 1 && ceil_div(Q, 16 * RF) * ceil_div(nb, TP_NBG) < 512) RF >>= 1;
     const size_t lds = tip_lds(D, RF, TP_NBG);
     const dim3 grid(ceil_div(Q, 16 * RF), ceil_div(nb, TP_NBG));
-#define PCLIP_TIP(NCH, RFV)                                                                                                                        \
-    do {                                                                                                                                         \
-        static DevOnce attr;                                                                                                                     \
-        if (int e = pclip_raise_lds(attr, {(const void*)tip_kernel<NCH, RFV, TP_NBG, true>}, TP_LDS_MAX, fn)) return e;                           \
-        tip_kernel<NCH, RFV, TP_NBG, true><<<grid, 256, lds, s>>>((const half_t*)f, ldf, Q, (const half_t*)keys, ldk, NK, seg, (const half_t*)w, ldw, N, D, scale, 0.f, \
-                                                                  0.f, betas, nb, alphas, na, labels, nullptr, 0, nullptr, nullptr, correct);       \
-    } while (0)
-    if (D <= 512) { if (RF == 2) PCLIP_TIP(1, 2); else PCLIP_TIP(1, 1); }
-    else if (D <= 1024) { if (RF == 2) PCLIP_TIP(2, 2); else PCLIP_TIP(2, 1); }
-    else PCLIP_TIP(4, 1);
-#undef PCLIP_TIP
-    return pclip_check_launch("tip_grid");
+    return panel_dispatch<2>(D, RF, [&](auto nch, auto rf, auto) -> int {            // (RF <= 2 above: the grid kernel is compiled for no wider panel)
+        static DevOnce attr;
+        if (int e = pclip_raise_lds(attr, {(const void*)tip_kernel<nch, rf, TP_NBG, true>}, TP_LDS_MAX, fn)) return e;
+        tip_kernel<nch, rf, TP_NBG, true><<<grid, 256, lds, s>>>((const half_t*)f, ldf, Q, (const half_t*)keys, ldk, NK, seg, (const half_t*)w, ldw, N, D, scale, 0.f, 0.f,
+                                                                betas, nb, alphas, na, labels, nullptr, 0, nullptr, nullptr, correct);
+        return pclip_check_launch("tip_grid");
+    });
 }

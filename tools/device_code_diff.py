@@ -1,0 +1,91 @@
+#!/usr/bin/env python3
+"""Compare the gfx950 device code of two builds kernel by kernel: the gate of a refactor that may rename registers but not change what a kernel issues.
+
+    python tools/device_code_diff.py PARENT_DIR NEW_DIR
+
+Each directory holds one `hipcc --cuda-device-only -S` listing per translation unit (NAME.s), built with the flags of proto-clip_amd/csrc/Makefile
+(pclip_train, pclip_tower_optim and pclip_preprocess with -ffp-contract=off, as there).  Kernels are matched by name through RENAMES (applied to the mangled
+name, length prefix included: no demangler that knows _Float16 ships with every ROCm); the kernel sets must be equal.  Per kernel it prints, and fails on: a change in the count of MFMA, vector-memory, LDS, barrier, transcendental or convert instructions;
+any scratch instruction, private segment or VGPR spill (but for a kernel whose every figure equals the parent's: it is the parent's kernel); a change of the LDS size; a change of the waves-per-SIMD step; a total instruction count more than
+1 % from the parent's.  Instructions are classified by the prefixes below and nothing else."""
+import os
+import re
+import sys
+
+CLASSES = {"mfma": ("v_mfma",), "vmem": ("global_", "buffer_", "flat_"), "lds": ("ds_",), "barrier": ("s_barrier",),
+           "trans": ("v_exp", "v_rcp", "v_rsq", "v_sqrt", "v_log"), "cvt": ("v_cvt",), "scratch": ("scratch_",)}
+RENAMES = (("ce_transpose_kernel", "transpose_kernel"), ("logits_norm_rows_kernel", "norm_rows_kernel"), ("ce_norm_rows_kernel", "norm_rows_kernel"))
+TOTAL_TOL = 0.01
+
+
+def short(name):
+    """kernel<1, 4, 8> from _ZN12_GLOBAL__N_1<len>kernelILi1ELi4ELi8EEEv...; other names as they are"""
+    m = re.match(r"_ZN12_GLOBAL__N_1(\d+)", name)
+    if not m:
+        return name
+    base, rest = name[m.end():m.end() + int(m.group(1))], name[m.end() + int(m.group(1)):]
+    targs = re.match(r"I((?:L[a-z]\d+E)+)E", rest)
+    return base + ("<%s>" % ", ".join(re.findall(r"L[a-z](\d+)E", targs.group(1))) if targs else "")
+
+
+def renamed(name):
+    for a, b in RENAMES:
+        name = re.sub(r"\b%s\b" % a, b, name.replace("%d%s" % (len(a), a), "%d%s" % (len(b), b)))
+    return name
+
+
+def waves_per_simd(regs):                                # 512 registers per lane and SIMD in granules of 8; .vgpr_count is the unified total, AGPRs included
+    return min(8, 512 // max(8, (regs + 7) // 8 * 8))
+
+
+def parse(path):
+    """{kernel name: {class: count, "total", "lds_bytes", "private", "spill", "waves"}} of one listing"""
+    text = open(path).read()
+    meta = {}
+    for entry in re.split(r"^  - (?=\.)", text.split("amdhsa.kernels:")[-1], flags=re.M)[1:]:
+        kv = dict(re.findall(r"^    (\.\w+):\s+(.+?)\s*$", entry, flags=re.M))     # (the kernel's own keys: its arguments' sit deeper)
+        meta[kv[".name"]] = kv
+    out = {}
+    for name, kv in meta.items():
+        body = re.search(r"^%s:.*?^\.Lfunc_end\d+:" % re.escape(name), text, flags=re.M | re.S).group(0)
+        ops = [m for m in re.findall(r"^\s+([a-z][a-z0-9_]*)\b", body, flags=re.M)]
+        k = {c: sum(op.startswith(p) for op in ops) for c, p in CLASSES.items()}
+        k.update(total=len(ops), lds_bytes=int(kv[".group_segment_fixed_size"]), private=int(kv[".private_segment_fixed_size"]),
+                 spill=int(kv.get(".vgpr_spill_count", 0)), waves=waves_per_simd(int(kv[".vgpr_count"])))
+        out[name] = k
+    return out
+
+
+def compare(parent_dir, new_dir, out=sys.stdout):
+    bad = 0
+    units = sorted(set(f for d in (parent_dir, new_dir) for f in os.listdir(d) if f.endswith(".s")))
+    for unit in units:
+        sides = []
+        for d in (parent_dir, new_dir):
+            p = os.path.join(d, unit)
+            sides.append(parse(p) if os.path.exists(p) else {})
+        old, new = {renamed(name): k for name, k in sides[0].items()}, sides[1]
+        for name in sorted(set(old) | set(new)):
+            why = []
+            if name not in old or name not in new:
+                why.append("only in the %s build" % ("new" if name in new else "parent"))
+            else:
+                o, n = old[name], new[name]
+                why += ["%s %d -> %d" % (c, o[c], n[c]) for c in ("mfma", "vmem", "lds", "barrier", "trans", "cvt", "lds_bytes", "waves") if o[c] != n[c]]
+                why += ["%s %d" % (c, n[c]) for c in ("scratch", "private", "spill") if n[c] and o != n]
+                if abs(n["total"] - o["total"]) > TOTAL_TOL * o["total"]:
+                    why.append("total beyond %g %%" % (100 * TOTAL_TOL))
+                print("%-22s %-36s total %5d -> %5d (%+.2f %%)  mfma %4d vmem %4d lds %4d bar %2d trans %3d cvt %3d  waves %d  %s" % (
+                    unit, short(name), o["total"], n["total"], 100.0 * (n["total"] - o["total"]) / o["total"], n["mfma"], n["vmem"], n["lds"], n["barrier"],
+                    n["trans"], n["cvt"], n["waves"], "same" if o == n else "ok" if not why else ""), file=out)
+            if why:
+                bad += 1
+                print("FAIL %s %s: %s" % (unit, short(name), "; ".join(why)), file=out)
+    print("%d kernel(s) failed" % bad if bad else "all kernels pass", file=out)
+    return bad
+
+
+if __name__ == "__main__":
+    if len(sys.argv) != 3:
+        sys.exit(__doc__)
+    sys.exit(1 if compare(sys.argv[1], sys.argv[2]) else 0)
