@@ -211,6 +211,39 @@ int pclip_cosine_ce_backward_f16(const void* a, int lda, int M, const void* b, i
 #define PCLIP_CE_SYMMETRIC 0x4
 #define PCLIP_CE_LABELS_I64 0x8
 
+/* ---- the pairwise sigmoid (SigLIP) loss over cosine logits, multi-positive by ids (clip/model.py:356-370 gives the logits) ------------- */
+
+/* x[m, t] = fma(scale, cos[m, t], bias) in fp32, cos = the fp32 matrix-pipe accumulation of a'[m, :] . b'[t, :], one accumulator over k = 0, 32, ... on every
+ * route (a' / b' as in pclip_cosine_ce_f16 under PCLIP_SIG_NORMALIZE_A / _B); nothing is rounded to fp16 on the way to x.
+ *   loss = 1/M sum_m sum_t softplus(-z[m, t] x[m, t]),  z = +1 on positive pairs, -1 elsewhere.
+ * Positives: ids_a [M], ids_b [T], both int32, or both int64 under PCLIP_SIG_IDS_I64 (compared in 64 bits): (m, t) is positive iff ids_a[m] == ids_b[t] and
+ * ids_a[m] >= 0.  An id is only ever compared, never used as an index; a negative id matches nothing (rows without a positive, padding).  Both NULL: the
+ * diagonal, which needs M == T (the same bits as arange ids on both sides).
+ * A term is max(-z x, 0) + log1p(exp(-|x|)) in fp32 (the hardware exp2 / log2 / rcp: the exponential within a relative (|x| + 2) 2^-22, log1p in a compensated
+ * form that keeps the term within a relative 2^-20 however small it is); row_loss[m] = sum_t term in fp32:
+ * eight waves take every eighth block of 64 columns each, merged in a fixed order — a row's bits depend on that row, b and the ids alone, not on the panel
+ * size, the grid or the other rows of a.  loss [1] = (sum_m row_loss[m]) / M, one fixed-order fp64 sum.  Rows >= M and columns >= T contribute exact zeros.
+ * Outputs (fp32, both required): row_loss [M], loss [1].  Nothing of size M x T is written; no floating-point atomics: two calls give the same bits.
+ * Any M, T >= 1; D % 64 == 0, D <= 2048; lda, ldb multiples of 8 halves >= D, 16-byte aligned bases; scale and bias finite;
+ * ws: pclip_workspace_bytes(PCLIP_OP_COSINE_SIGMOID, M, T, D) (PCLIP_E_WORKSPACE if smaller).  Everything else is PCLIP_E_INVALID before any launch. */
+int pclip_cosine_sigmoid_f16(const void* a, int lda, int M, const void* b, int ldb, int T, int D, float scale, float bias, int flags,
+                             const void* ids_a, const void* ids_b, float* row_loss, float* loss, void* ws, size_t ws_bytes, pclip_stream_t stream);
+/* The gradients of the above, recomputed tile by tile (nothing is kept from the forward):  G[m, t] = weight * ( sigma(x[m, t]) - y[m, t] ), y = 1 on positive
+ * pairs; weight = 1 / M for the mean (times the upstream gradient, if the caller folds it in), finite.
+ *   direction 0: grad [M, D] fp32 (dense) = dL/da = scale G b', chained in fp32 through the normalisation under PCLIP_SIG_NORMALIZE_A;
+ *   direction 1: grad [T, D] fp32 (dense) = dL/db = scale G^T a', chained under PCLIP_SIG_NORMALIZE_B.
+ * dscale = sum G o cos and dbias = sum G (each nullable, [1] fp32): from the unrounded fp32 sigma, per lane, per-panel partials, one fixed-order fp64 sum; the
+ * same value from either direction up to the summation order.  The sigma tile enters the second matrix product rounded to fp16 as 2^14 sigma (relative unit
+ * 2^-11 down to sigma = 2^-28, zero below 2^-39); the target tile is exact; weight and scale act in fp32.  Deterministic; a row of dL/da depends on that row,
+ * b, the ids and weight alone, not on the other rows of a.
+ * Same envelope as the forward, direction 0 or 1, grad 16-byte aligned; ws: pclip_workspace_bytes(PCLIP_OP_COSINE_SIGMOID_BACKWARD, M, T, D). */
+int pclip_cosine_sigmoid_backward_f16(const void* a, int lda, int M, const void* b, int ldb, int T, int D, float scale, float bias, int flags,
+                                      const void* ids_a, const void* ids_b, float weight, int direction, float* grad, float* dscale, float* dbias,
+                                      void* ws, size_t ws_bytes, pclip_stream_t stream);
+#define PCLIP_SIG_NORMALIZE_A 0x1
+#define PCLIP_SIG_NORMALIZE_B 0x2
+#define PCLIP_SIG_IDS_I64 0x8
+
 /* ---- Tip-Adapter's cache logits (Tip-Adapter main.py: run_tip_adapter / search_hp; the baseline the Proto-CLIP tables compare against) ------------- */
 
 /* logit[q, n] = r16( c[q, n] + alpha * S[q, n] ): `100. * features @ clip_weights + alpha * exp(-(beta - beta * features @ cache_keys)) @ cache_values`
@@ -703,6 +736,8 @@ int pclip_preprocess_u8(const void* const* srcs, const int32_t* desc, int B, int
 #define PCLIP_OP_COSINE_CE 5          /* Q = M, N = T: normalised rows of b, per-panel column partials, target logits: O(T D + panels T + M) */
 #define PCLIP_OP_COSINE_CE_BACKWARD 6 /* Q = M, N = T: the walked operand normalised and transposed, for either direction: O(max(M, T) D) */
 #define PCLIP_OP_TIP_BACKWARD 7       /* N = NK, the key rows: the queries transposed, a class per key row, the largest |dL|: O(Q D + NK) */
+#define PCLIP_OP_COSINE_SIGMOID 8          /* Q = M, N = T: the normalised rows of b: O(T D) */
+#define PCLIP_OP_COSINE_SIGMOID_BACKWARD 9 /* Q = M, N = T: the walked operand normalised and transposed, partial panels of a shared walk, per-panel scalars: O(max(M, T) D + panels) */
 size_t pclip_workspace_bytes(int op, int Q, int N, int D);
 
 #ifdef __cplusplus

@@ -11,7 +11,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpclip.so")
 
 OP_SQDIST, OP_CLASSIFY, OP_ADAPTER_FC, OP_LOGITS, OP_COSINE_CE, OP_COSINE_CE_BACKWARD, OP_TIP_BACKWARD = 1, 2, 3, 4, 5, 6, 7
+OP_COSINE_SIGMOID, OP_COSINE_SIGMOID_BACKWARD = 8, 9
 LOGITS_NORMALIZE_A, LOGITS_NORMALIZE_B = 0x1, 0x2          # flags of pclip_cosine_logits_f16
+SIG_NORMALIZE_A, SIG_NORMALIZE_B, SIG_IDS_I64 = 0x1, 0x2, 0x8          # flags of pclip_cosine_sigmoid_f16 / pclip_cosine_sigmoid_backward_f16
 CE_NORMALIZE_A, CE_NORMALIZE_B, CE_SYMMETRIC, CE_LABELS_I64 = 0x1, 0x2, 0x4, 0x8          # flags of pclip_cosine_ce_f16 / pclip_cosine_ce_backward_f16
 # routing flags of pclip_classify_ex_f16 / pclip_classify_route_ex (include/pclip.h)
 CLASSIFY_NO_SMALL, CLASSIFY_NO_MID, CLASSIFY_FORCE_MID, CLASSIFY_NO_PANELS, CLASSIFY_FORCE_PANELS = 0x1, 0x2, 0x4, 0x8, 0x10
@@ -60,6 +62,8 @@ _SIGS = {
     "pclip_cosine_logits_f16": [_P, c_int, c_int, _P, c_int, c_int, c_int, c_float, c_int, _P, c_int, _P, _P, _P, c_int, _P, c_size_t, _P],
     "pclip_cosine_ce_f16": [_P, c_int, c_int, _P, c_int, c_int, c_int, c_float, c_int, _P, _P, _P, _P, _P, _P, c_size_t, _P],
     "pclip_cosine_ce_backward_f16": [_P, c_int, c_int, _P, c_int, c_int, c_int, c_float, c_int, _P, _P, _P, c_float, c_int, _P, _P, _P, c_size_t, _P],
+    "pclip_cosine_sigmoid_f16": [_P, c_int, c_int, _P, c_int, c_int, c_int, c_float, c_float, c_int, _P, _P, _P, _P, _P, c_size_t, _P],
+    "pclip_cosine_sigmoid_backward_f16": [_P, c_int, c_int, _P, c_int, c_int, c_int, c_float, c_float, c_int, _P, _P, c_float, c_int, _P, _P, _P, _P, c_size_t, _P],
     "pclip_tip_logits_f16": [_P, c_int, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_float, c_float, c_float, _P, c_int, _P, _P, _P],
     "pclip_tip_grid_f16": [_P, c_int, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_float, _P, c_int, _P, c_int, _P, _P, _P],
     "pclip_tip_keys_backward_f16": [_P, c_int, c_int, _P, c_int, c_int, _P, c_int, c_int, c_float, c_float, _P, _P, _P, c_size_t, _P],

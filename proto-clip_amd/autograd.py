@@ -230,6 +230,53 @@ def cosine_cross_entropy(a, b, scale, labels=None, symmetric=False, normalize_a=
     return ops.cosine_cross_entropy(a16.detach(), b16.detach(), s, labels, symmetric, normalize_a, normalize_b)[0]
 
 
+class CosineSigmoidFn(torch.autograd.Function):
+    """SigLIP's pairwise sigmoid loss over scale * a' @ b'^T + bias, multi-positive by ids (ops.cosine_sigmoid).  Saves the operands and the ids — nothing of
+    size M T, and nothing from the forward; the backward recomputes logit tiles (pclip_cosine_sigmoid_backward_f16).  a, b: fp16, or fp32 (cast once; the
+    gradient comes back fp32).  scale, bias: each a Python float, or a 0-dim tensor that then receives a gradient (its VALUE is read on the host: one sync,
+    and no graph capture)."""
+
+    @staticmethod
+    def forward(ctx, a, b, scale, bias, ids_a, ids_b, normalize_a, normalize_b):
+        a16 = a if a.dtype == torch.float16 else ops.cast_f16(a.float().contiguous())
+        b16 = b if b.dtype == torch.float16 else ops.cast_f16(b.float().contiguous())
+        ctx.scale = float(scale.detach()) if isinstance(scale, torch.Tensor) else float(scale)
+        ctx.bias = float(bias.detach()) if isinstance(bias, torch.Tensor) else float(bias)
+        ctx.mode = (bool(normalize_a), bool(normalize_b))
+        ctx.refs = tuple((t.dtype, t.shape) if isinstance(t, torch.Tensor) else None for t in (a, b, scale, bias))      # what each gradient is cast back to
+        ctx.has_ids = ids_a is not None
+        loss = ops.cosine_sigmoid(a16, b16, ctx.scale, ctx.bias, ids_a, ids_b, *ctx.mode)
+        ctx.save_for_backward(*((a16, b16, ids_a, ids_b) if ctx.has_ids else (a16, b16)))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        a16, b16 = ctx.saved_tensors[:2]
+        ids_a, ids_b = ctx.saved_tensors[2:] if ctx.has_ids else (None, None)
+        need = ctx.needs_input_grad[:4]
+        got = ops.cosine_sigmoid_backward(a16, b16, ctx.scale, ctx.bias, ids_a, ids_b, *ctx.mode, want_a=need[0], want_b=need[1], want_scale=need[2],
+                                          want_bias=need[3])
+        g = g.float()
+
+        def cast(t, ref):
+            if t is None:
+                return None
+            t = (t * g).reshape(ref[1])
+            return ops.cast_f16(t.contiguous()) if ref[0] == torch.float16 else t.to(ref[0])
+        return tuple(cast(t, ref) if n else None for t, ref, n in zip(got, ctx.refs, need)) + (None, None, None, None)
+
+
+def cosine_sigmoid_loss(a, b, scale, bias, ids_a=None, ids_b=None, normalize_a=False, normalize_b=False):
+    """The loss of `CosineSigmoidFn` with a tape where one is wanted, the bare forward under torch.no_grad() or for constants."""
+    tensor = lambda v: v if isinstance(v, torch.Tensor) else None
+    if wants_grad(a, b, tensor(scale), tensor(bias)):
+        return CosineSigmoidFn.apply(a, b, scale, bias, ids_a, ids_b, normalize_a, normalize_b)
+    a16 = a if a.dtype == torch.float16 else ops.cast_f16(a.detach().float().contiguous())
+    b16 = b if b.dtype == torch.float16 else ops.cast_f16(b.detach().float().contiguous())
+    value = lambda v: float(v.detach()) if isinstance(v, torch.Tensor) else float(v)
+    return ops.cosine_sigmoid(a16.detach(), b16.detach(), value(scale), value(bias), ids_a, ids_b, normalize_a, normalize_b)
+
+
 def wants_grad(*tensors) -> bool:
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 

@@ -594,6 +594,14 @@ class CLIP(nn.Module):
         from ..utils import clip_contrastive_loss
         return clip_contrastive_loss(image_features, text_features, self.logit_scale.float().exp())
 
+    def sigmoid_loss(self, image_features, text_features, logit_bias, image_ids=None, text_ids=None):
+        """SigLIP's pairwise sigmoid loss (`utils.clip_sigmoid_loss`) under this model's temperature, logit_scale.exp() in fp32: a pair is positive iff its ids
+        agree (several images per class are several positives of that class's text); without ids the positives are the diagonal.  logit_bias is the
+        CALLER's float or 0-dim tensor (SigLIP starts it at -10): the model keeps no such parameter, its state dict stays the reference's.  Gradients
+        reach logit_scale, logit_bias and the unfrozen tails of the towers as under `contrastive_loss`."""
+        from ..utils import clip_sigmoid_loss
+        return clip_sigmoid_loss(image_features, text_features, self.logit_scale.float().exp(), logit_bias, image_ids, text_ids)
+
 
 def convert_weights(model: nn.Module):
     """fp16 for Linear/conv/attention/projection parameters, fp32 elsewhere (clip/model.py:373-394)."""

@@ -355,6 +355,83 @@ def cosine_cross_entropy_backward(a, b, scale: float, lse_row, lse_col=None, lab
     return (grads[0] if want_a else None), grads[1], ds
 
 
+def _cosine_sigmoid_args(what, a, b, scale, bias, ids_a, ids_b, normalize_a, normalize_b):
+    """The operands of the two sigmoid-loss calls as the kernels take them: (a, b, lda, ldb, M, T, D, scale, bias, ids_a, ids_b, flags)."""
+    require_cuda(a, b, ids_a, ids_b)
+    a, b = _f16_rows(a, f"{what}: a"), _f16_rows(b, f"{what}: b")
+    (M, D), (T, Db) = a.shape, b.shape
+    if D != Db:
+        raise _lib.PclipError(f"{what}: a has {D} columns, b has {Db}")
+    if M < 1 or T < 1:
+        raise _lib.PclipError(f"{what}: empty operand (M={M}, T={T})")
+    scale, bias = float(np.float32(scale)), float(np.float32(bias))
+    if not (math.isfinite(scale) and math.isfinite(bias)):
+        raise _lib.PclipError(f"{what}: scale={scale} and bias={bias} must be finite")
+    flags = (_lib.SIG_NORMALIZE_A if normalize_a else 0) | (_lib.SIG_NORMALIZE_B if normalize_b else 0)
+    if (ids_a is None) != (ids_b is None):
+        raise _lib.PclipError(f"{what}: ids_a and ids_b go together (both None: the diagonal)")
+    if ids_a is None:
+        if M != T:
+            raise _lib.PclipError(f"{what}: without ids the positives are the diagonal, which needs M == T (M={M}, T={T})")
+    else:
+        for name, t, n in (("ids_a", ids_a, M), ("ids_b", ids_b, T)):
+            if t.dtype not in (torch.int32, torch.int64) or t.dim() != 1 or t.shape[0] != n:
+                raise _lib.PclipError(f"{what}: {name} must be an int32 / int64 tensor of {n} entries")
+        if ids_a.dtype != ids_b.dtype:
+            raise _lib.PclipError(f"{what}: ids_a is {ids_a.dtype}, ids_b is {ids_b.dtype}: both int32 or both int64")
+        ids_a, ids_b = ids_a.contiguous(), ids_b.contiguous()
+        flags |= _lib.SIG_IDS_I64 if ids_a.dtype == torch.int64 else 0
+    return a, b, (a.stride(0) if M > 1 else D), (b.stride(0) if T > 1 else D), M, T, D, scale, bias, ids_a, ids_b, flags
+
+
+def cosine_sigmoid(a, b, scale: float, bias: float, ids_a=None, ids_b=None, normalize_a: bool = False, normalize_b: bool = False, want_rows: bool = False):
+    """SigLIP's pairwise sigmoid loss over x = scale * a' @ b'^T + bias without the [M, T] matrix: loss = 1/M sum_m sum_t softplus(-z x), z = +1 on positive
+    pairs, -1 elsewhere.  a [M, D], b [T, D] fp16 (row-strided views are read in place), a' / b' the rows or their `l2norm_rows`; x stays fp32.
+    ids_a [M], ids_b [T], both int32 or both int64: (m, t) is positive iff ids_a[m] == ids_b[t] >= 0 — any number of positives per row or column; a negative id
+    matches nothing; an id is compared, never used as an index.  Without ids the positives are the diagonal (M == T).
+    Returns the loss (0-dim fp32), and the per-row sums [M] (whose mean the loss is) as a second value with `want_rows`."""
+    a, b, lda, ldb, M, T, D, scale, bias, ids_a, ids_b, flags = _cosine_sigmoid_args("cosine_sigmoid", a, b, scale, bias, ids_a, ids_b, normalize_a, normalize_b)
+    dev = a.device
+    rows = torch.empty(M, dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    nws = _lib.workspace_bytes(_lib.OP_COSINE_SIGMOID, M, T, D)
+    ws = _workspace(nws, dev)
+    check(_lib.load().pclip_cosine_sigmoid_f16(ptr(a), lda, M, ptr(b), ldb, T, D, scale, bias, flags, ptr(ids_a), ptr(ids_b), ptr(rows), ptr(loss), ptr(ws), nws,
+                                               stream()), "pclip_cosine_sigmoid_f16")
+    return (loss, rows) if want_rows else loss
+
+
+def cosine_sigmoid_backward(a, b, scale: float, bias: float, ids_a=None, ids_b=None, normalize_a: bool = False, normalize_b: bool = False, want_a: bool = True,
+                            want_b: bool = True, want_scale: bool = True, want_bias: bool = True, grad: float = 1.0, mean_over: int = None):
+    """The gradients of `cosine_sigmoid`: (dL/da [M, D] fp32 | None, dL/db [T, D] fp32 | None, dL/dscale 0-dim fp32 | None, dL/dbias 0-dim fp32 | None).
+    Nothing is kept from the forward: logit tiles are recomputed and fed to a second matrix product; the sigmoid tile is rounded to fp16 on the way, the target
+    term, the weight and the scale act in fp32.  With normalize_a / normalize_b the gradient is chained in fp32 through the normalisation.
+    grad: the upstream gradient as a number; mean_over: the row count the loss was averaged over when the rows are a slice of a larger batch (default M) — a row
+    of dL/da has the same bits in any batch with the same b, ids and `grad / mean_over`."""
+    a, b, lda, ldb, M, T, D, scale, bias, ids_a, ids_b, flags = _cosine_sigmoid_args("cosine_sigmoid_backward", a, b, scale, bias, ids_a, ids_b, normalize_a,
+                                                                                    normalize_b)
+    dev = a.device
+    weight = float(np.float32(float(grad) / (mean_over or M)))
+    if not math.isfinite(weight):
+        raise _lib.PclipError(f"cosine_sigmoid_backward: grad / mean_over = {weight} must be finite")
+    nws = _lib.workspace_bytes(_lib.OP_COSINE_SIGMOID_BACKWARD, M, T, D)
+    ws = _workspace(nws, dev)
+    ds = torch.empty((), dtype=torch.float32, device=dev) if want_scale else None
+    dbi = torch.empty((), dtype=torch.float32, device=dev) if want_bias else None
+    walks = [(0, M, want_a or ((want_scale or want_bias) and not want_b)), (1, T, want_b)]      # (the scalars are by-products of a gradient walk: of dL/da's if no other runs)
+    grads, ds_left, db_left = [], ds, dbi
+    for direction, rows, run in walks:
+        if not run:
+            grads.append(None)
+            continue
+        g = torch.empty(rows, D, dtype=torch.float32, device=dev)
+        check(_lib.load().pclip_cosine_sigmoid_backward_f16(ptr(a), lda, M, ptr(b), ldb, T, D, scale, bias, flags, ptr(ids_a), ptr(ids_b), weight, direction,
+                                                            ptr(g), ptr(ds_left), ptr(db_left), ptr(ws), nws, stream()), "pclip_cosine_sigmoid_backward_f16")
+        ds_left = db_left = None
+        grads.append(g)
+    return (grads[0] if want_a else None), grads[1], ds, dbi
+
+
 def _tip_segment_table(t: torch.Tensor, N=None):
     """The checks and the table of `tip_segments` on whatever device `t` lives on: (seg [N + 1] int32, N).  One host transfer."""
     if t.dim() == 2:

@@ -154,6 +154,25 @@ def clip_contrastive_loss(image_features, text_features, logit_scale):
     return pag.cosine_cross_entropy(image_features, text_features, logit_scale, symmetric=True, normalize_a=True, normalize_b=True)
 
 
+def clip_sigmoid_loss(image_features, text_features, logit_scale, logit_bias, image_ids=None, text_ids=None):
+    """SigLIP's pairwise sigmoid loss on image features [M, D] and text features [T, D]: both sides L2-normalised, one binary term per pair over
+    `logit_scale * i' @ t'^T + logit_bias`, summed and divided by M.  A pair is positive iff image_ids[m] == text_ids[t] >= 0 (int32 or int64, both alike):
+    several images of one class are positives of its text and of nobody else — what a few-shot batch needs and the diagonal targets of
+    `clip_contrastive_loss` cannot say; a negative id matches nothing.  Without ids the positives are the diagonal (M == T).  logit_scale is the ALREADY
+    exponentiated scale; it and logit_bias are each a float or a 0-dim tensor (which then receives a gradient).  No [M, T] tensor is written, forward or
+    backward; a pair's term depends on that pair alone, so the loss of a block of a larger batch is the block's own call."""
+    return pag.cosine_sigmoid_loss(image_features, text_features, logit_scale, logit_bias, image_ids, text_ids, normalize_a=True, normalize_b=True)
+
+
+def clip_logits_sigmoid_loss(features, clip_weights, labels, scale=100., bias=0., layout=None):
+    """One-vs-rest training of a text-initialised classifier on cached features, the multi-label twin of `clip_logits_loss`: a binary term per (sample, class)
+    over `scale * features @ clip_weights + bias`, positive where the class is the sample's label (a negative label: no positive), summed and divided by the
+    sample count.  The operands are taken as they are; `layout` as in `clip_logits`; gradients for the features, the weights and tensor `scale` / `bias`."""
+    rows = _clip_weight_rows(features, clip_weights, layout, taped=True)
+    classes = torch.arange(rows.shape[0], dtype=labels.dtype, device=labels.device)
+    return pag.cosine_sigmoid_loss(features, rows, scale, bias, labels, classes)
+
+
 def get_target_inds(info):
     """Episode ground-truth labels [n_class, k_query, 1] int64 on the GPU from info = (n_class, k_support, k_query)
     (reference utils.py:112-122; no caller in the reference — kept for API completeness)."""
