@@ -354,6 +354,31 @@ int pclip_gemm4w_f16(const void* A, int lda, const void* B, int ldb, void* C, in
  * PCLIP_E_INVALID.  Test / tuning entry. */
 int pclip_gemm4w_var_f16(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
                          const void* bias, int act, const void* residual, int var, pclip_stream_t stream);
+/* Test entry: pclip_gemm_f16 / pclip_gemm_bn_f16 / pclip_gemm_bn_res_f16 through the SAME dispatch with everything that routes a call taken from the call instead of
+ * the environment, and a report of what ran (tests/test_gpu_gemm_forward.py asserts every route it claims from it).  It launches the product's kernels; no new device code.
+ *   act 0 / 1 with bias, residual as pclip_gemm_f16 (scale = shift = NULL); act 2 / 3 = BatchNorm / BatchNorm + ReLU (scale, shift; no bias), act 5 = BatchNorm +
+ *     residual + ReLU (the operand checks of the product entries);
+ *   cfg (what to run): PCLIP_ROUTE_AUTO = the cost model (and the ring kernel where it applies; no environment switch is read, PCLIP_GEMM_SMALL neither), 0 .. 4 = the persistent kernel on 128 x 128, 256 x 128, 256 x 256, 256 x 64, 256 x 32
+ *     tiles (a configuration the shape does not fit falls back to the cost model's, as in the product: read the report), PCLIP_ROUTE_GENERIC, PCLIP_ROUTE_RING
+ *     (one workgroup per 128 x 64 tile whatever their number; PCLIP_E_INVALID where the kernel does not apply);
+ *   may_split: the row split of a partial last round is allowed (never under a forced cfg);
+ *   band / band_n / rev: PCLIP_GEMM_BAND / _BAND_N / _REV of this call (product defaults 0, 0, 2);
+ *   use4w: 256 x 256 tiles on 0 the eight-wave kernel, 1 the four-wave kernel, 2 its race-stress build (where pclip_gemm4w_f16 applies);
+ *   cus: stands in for the device's CU count in the ring test, the cost model, the row split and the persistent grids (4: a few hundred rows walk several tiles per workgroup);
+ *   report (HOST memory, report_len ints): [0] = kernel launches, then PCLIP_ROUTE_FIELDS ints per launch in launch order, as many as fit:
+ *     family (what ran: 0 .. 4 persistent cfg, PCLIP_ROUTE_RAN_FOUR_WAVE / _RING / _GENERIC — numbered apart from the cfg values), K-tail / ragged-N instantiation (0 / 1), rows of the
+ *     launch, tiles descending (0 / 1), band (column tiles per band, 0 = none). */
+#define PCLIP_ROUTE_AUTO (-1)
+#define PCLIP_ROUTE_GENERIC 5
+#define PCLIP_ROUTE_RING 6
+#define PCLIP_ROUTE_FIELDS 5
+#define PCLIP_ROUTE_RAN_FOUR_WAVE 10
+#define PCLIP_ROUTE_RAN_RING 11
+#define PCLIP_ROUTE_RAN_GENERIC 12
+int pclip_gemm_route_f16(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
+                         const void* bias, int act, const void* residual, const float* scale, const float* shift,
+                         int cfg, int may_split, int band, int band_n, int rev, int use4w, int cus,
+                         int* report, int report_len, pclip_stream_t stream);
 /* Diagnostic (loop variant 8 of pclip_gemm4w_var_f16: the product loop in a kernel that keeps time stamps of its tile phases): device buffer of 260 unsigned that the
  * next variant-8 launches fill — stamps [4][64] of (workgroup 0 | gridDim / 2) x (wave 0 | 3), eight s_memrealtime stamps (100 MHz) per tile for the first eight
  * tiles, + one closing stamp per wave at [256 + w].  NULL switches it off.  tools/gemm4w_stamps.py. */

@@ -22,6 +22,9 @@ TIP_MAX_ALPHAS, TIP_MAX_CLASSES, TIP_MAX_D = 32, 4096, 2048                     
 # pclip_tower_grad_sumsq / pclip_tower_optim_finish / pclip_tower_adamw: chunk length, table row / state block sizes, row flags
 TOWER_CHUNK, TOWER_ROW_BYTES, TOWER_STATE_BYTES = 4096, 64, 64
 TOWER_PARAM_F16, TOWER_GRAD_F16, TOWER_ALIGNED, TOWER_DECAY = 0x1, 0x2, 0x4, 0x8
+# pclip_gemm_route_f16: cfg values beside 0 .. 4, ints per launch of the report, and the report's kernel families (PCLIP_ROUTE_*)
+ROUTE_AUTO, ROUTE_GENERIC, ROUTE_RING, ROUTE_FIELDS = -1, 5, 6, 5
+ROUTE_RAN = {0: "cfg0", 1: "cfg1", 2: "cfg2", 3: "cfg3", 4: "cfg4", 10: "four_wave", 11: "ring", 12: "generic"}
 EMBED_BWD_CHUNK = 128                                      # PCLIP_EMBED_BWD_CHUNK: sorted rows per chunk of pclip_text_embed_backward's segmented reduction
 PROMPT_CTX_SLICE = 16                                      # PCLIP_PROMPT_CTX_SLICE: classes per slice of pclip_prompt_ctx_grad_f32's first stage
 
@@ -76,6 +79,8 @@ _SIGS = {
     "pclip_gemm_f16": [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P],
     "pclip_gemm4w_f16": [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P],
     "pclip_gemm4w_var_f16": [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, _P],
+    "pclip_gemm_route_f16": [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                             _P, c_int, _P],
     "pclip_gemm4w_stamp_buffer": [_P],
     "pclip_gemm4w_config": [c_int],
     "pclip_gemm_splitk_workspace": [c_int, c_int, c_int],

@@ -1,5 +1,22 @@
 // Epilogue arithmetic shared by the persistent linear kernels (pclip_encoder.hip: eight waves; pclip_gemm4w.hip: four waves with the asm K-loop):
 // the reference's fp16 rounding points of nn.Linear + QuickGELU (clip/model.py:164-166, 176-178) and the output store policy.
+//
+// ROUNDING POINTS (mirrored in tests/gemm_fwd_ref.py, whose per-element tolerance has one first-order term per line; tests/test_gpu_gemm_forward.py grades every
+// GEMM kernel and epilogue against float64 with it).  u11 = 2^-11 (an fp16 rounding), u24 = 2^-24 (an fp32 rounding), 2^-25 absolute in fp16's subnormal range;
+// the instructions are what hipcc emits for gfx950 (-ffp-contract=fast).  acc = sum_k a w, z = acc + bias:
+//   accumulation   fp32 MFMA over K exact products, the fp32 copy of the bias as the accumulators' INITIAL value: A = (K + 1) u24 (|bias| + sum |a| |w|)
+//                  (generic kernel: from zero, the bias added in fp32 behind the K-loop — the same K + 1 additions; split-K: S slabs from zero, added in slice
+//                  order from zero, then the bias: K + S + 1)
+//   act 0          h = r16(z): ONE rounding (v_cvt_f16_f32), with or without bias — never r16(r16(acc) + bias)
+//   act 6          y = r16(res + h): one v_pk_add_f16 of two fp16 values
+//   act 2 / 3      c = r16(acc); y = r16(c sc + sh) is ONE v_fma_mixlo/hi_f16: no fp32 rounding of the product or the sum, the exact fma rounded to fp16 once;
+//                  ReLU (v_max_f32) exact
+//   act 5          y2 = relu(r16(y + res)): one v_add_f16 more, the ReLU behind the add
+//   act 1          h = r16(z); t = r16(1.702f h) is ONE v_fma_mixlo_f16 (1.702f is the rounded constant); the exponent's argument fma(t, -log2 e, 0) is one fp32
+//                  rounding of a value of size |t| log2 e (v_fma_mix_f32), log2 e itself a rounded fp32 constant; v_exp_f32, 1 + ex (v_pk_add_f32), v_rcp_f32;
+//                  s = r16(..); y = r16(h s) is one v_pk_mul_f16.  Where 1.702 |h| leaves fp16's range t = +-inf, s = 1 or 0 exactly, y = h or -0 (never NaN
+//                  while h is finite); h = -inf gives -inf x 0 = NaN, as the reference's own fp16 arithmetic does.
+//   overflow       every r16 above rounds to infinity from 65520 on, and an infinite intermediate stays infinite
 #pragma once
 #include "pclip_common.h"
 
@@ -44,7 +61,8 @@ __device__ __forceinline__ half4_t cvt16x4(float4_t v) {
 }
 
 // eval-mode BatchNorm (+ReLU) on four columns with their scale / shift (clip/model.py:43-52), two roundings: the convolution's output is an fp16 tensor
-// (r16(v)), and so is bn's (r16(. * sc + sh), the product and the sum in fp32); ReLU is exact.
+// (r16(v)), and so is bn's: r16(. * sc + sh) compiles to ONE v_fma_mixlo / mixhi_f16 — the exact fma rounded to fp16 once, no fp32 rounding of the product or the
+// sum (list at the top of this file); ReLU is exact.
 template <bool RELU>
 __device__ __forceinline__ half4_t bn16x4(float4_t v, float4_t sc, float4_t sh) {
     half4_t h;
@@ -57,7 +75,8 @@ __device__ __forceinline__ half4_t bn16x4(float4_t v, float4_t sc, float4_t sh) 
     return h;
 }
 
-// Residual add on one 16-byte chunk: r16(x + h) of two fp16 tensors — one rounding, the sum in fp32 — (+ exact ReLU: `out += identity; relu` of a bottleneck).
+// Residual add on one 16-byte chunk: r16(x + h) of two fp16 tensors — one rounding: hipcc emits a single v_pk_add_f16 / v_add_f16 for the widened sum, which gives
+// the same value — (+ exact ReLU: `out += identity; relu` of a bottleneck).
 template <bool RELU>
 __device__ __forceinline__ half8_t add_residual16x8(half8_t x, half8_t h) {
 #pragma unroll

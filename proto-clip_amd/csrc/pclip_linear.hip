@@ -383,40 +383,57 @@ static const TileOrder& tile_order() {
     return order;
 }
 
+// Route of ONE call, for the test entry pclip_gemm_route_f16: the tile order and the 256 x 256 kernel come from the call instead of the process-wide switches, and
+// every kernel launch is written down.  Null on the product entries: they route exactly as before.
+struct Route {
+    TileOrder order;
+    int use4w;                                    // 256 x 256 tiles: 0 eight waves, 1 the four-wave kernel, 2 its race-stress build
+    int* report;                                  // [0] launches, then PCLIP_ROUTE_FIELDS ints per launch (include/pclip.h); host memory
+    int cap;                                      // launches the report has room for
+    void note(int family, bool kt, int rows, int rev, int band) {
+        const int i = report[0]++;
+        if (i >= cap) return;
+        int* r = report + 1 + PCLIP_ROUTE_FIELDS * i;
+        r[0] = family; r[1] = kt; r[2] = rows; r[3] = rev; r[4] = band;
+    }
+};
+
 // KT: the K-tail / ragged-N instantiation of linear_fast_kernel: column tiles = ceil(N / BN)
 template <class C, bool HAS_BIAS, int ACT, bool KT>
 static int launch_fast2(const void* A, int lda, const void* B, int ldb, int M, int N, int K, const LinearEpi& epi,
-                        int slots, hipStream_t s) {
+                        int slots, hipStream_t s, Route* rt, int family) {
     static DevOnce attr;
     constexpr int LDS = C::LDS_BYTES + ((ACT == 2 || ACT == 3 || ACT == 5) ? 2 * 2 * C::BN * 4 : 2 * C::BN * 2) + 256;   // K-tile ring + double-buffered bias / affine strips + prefetch scrap
     using CK = std::conditional_t<KT, pgemm::Tail<C>, C>;
     if (int e = pclip_raise_lds(attr, {(const void*)linear_fast_kernel<CK, HAS_BIAS, ACT>}, LDS, "pclip_gemm_f16")) return e;
     const int tiles_m = ceil_div(M, C::BM), tiles_n = KT ? ceil_div(N, C::BN) : N / C::BN, ntiles = tiles_m * tiles_n;
     const int grid = ntiles < slots ? ntiles : slots;
-    const TileOrder& order = tile_order();
+    const TileOrder& order = rt ? rt->order : tile_order();
+    const int band = order.descending(K) ? -1 : (tiles_n >= 8 ? order.band : 0);
+    if (rt) rt->note(family, KT, M, band < 0, band < 0 ? 0 : band);
     linear_fast_kernel<CK, HAS_BIAS, ACT><<<grid, C::NTHREADS, LDS, s>>>(
         (const half_t*)A, lda, (const half_t*)B, ldb, M, N, K, epi.bias, epi.scale, epi.shift, epi.C, epi.ldc, tiles_n, ntiles, epi.residual,
-        order.descending(K) ? -1 : (tiles_n >= 8 ? order.band : 0), pclip_gemm_time_slot());
+        band, pclip_gemm_time_slot());
     return pclip_check_launch("gemm_f16");
 }
 
 template <class C, bool KT = false>
 static int launch_fast(const void* A, int lda, const void* B, int ldb, int M, int N, int K, const LinearEpi& epi,
-                       int slots, hipStream_t s) {
-    if (epi.act == 2) return launch_fast2<C, false, 2, KT>(A, lda, B, ldb, M, N, K, epi, slots, s);
-    if (epi.act == 3) return launch_fast2<C, false, 3, KT>(A, lda, B, ldb, M, N, K, epi, slots, s);
-    if (epi.act == 5) return launch_fast2<C, false, 5, KT>(A, lda, B, ldb, M, N, K, epi, slots, s);
-    if (epi.act == 6) return launch_fast2<C, true, 6, KT>(A, lda, B, ldb, M, N, K, epi, slots, s);
+                       int slots, hipStream_t s, Route* rt, int family) {
+    if (epi.act == 2) return launch_fast2<C, false, 2, KT>(A, lda, B, ldb, M, N, K, epi, slots, s, rt, family);
+    if (epi.act == 3) return launch_fast2<C, false, 3, KT>(A, lda, B, ldb, M, N, K, epi, slots, s, rt, family);
+    if (epi.act == 5) return launch_fast2<C, false, 5, KT>(A, lda, B, ldb, M, N, K, epi, slots, s, rt, family);
+    if (epi.act == 6) return launch_fast2<C, true, 6, KT>(A, lda, B, ldb, M, N, K, epi, slots, s, rt, family);
     if (epi.bias) {
-        if (epi.act == 1) return launch_fast2<C, true, 1, KT>(A, lda, B, ldb, M, N, K, epi, slots, s);
-        return launch_fast2<C, true, 0, KT>(A, lda, B, ldb, M, N, K, epi, slots, s);
+        if (epi.act == 1) return launch_fast2<C, true, 1, KT>(A, lda, B, ldb, M, N, K, epi, slots, s, rt, family);
+        return launch_fast2<C, true, 0, KT>(A, lda, B, ldb, M, N, K, epi, slots, s, rt, family);
     }
-    if (epi.act == 1) return launch_fast2<C, false, 1, KT>(A, lda, B, ldb, M, N, K, epi, slots, s);
-    return launch_fast2<C, false, 0, KT>(A, lda, B, ldb, M, N, K, epi, slots, s);
+    if (epi.act == 1) return launch_fast2<C, false, 1, KT>(A, lda, B, ldb, M, N, K, epi, slots, s, rt, family);
+    return launch_fast2<C, false, 0, KT>(A, lda, B, ldb, M, N, K, epi, slots, s, rt, family);
 }
 template <class C>
-static int launch_fast_k(bool kt, const void* A, int lda, const void* B, int ldb, int M, int N, int K, const LinearEpi& epi, int slots, hipStream_t s) {
-    return kt ? launch_fast<C, true>(A, lda, B, ldb, M, N, K, epi, slots, s) : launch_fast<C, false>(A, lda, B, ldb, M, N, K, epi, slots, s);
+static int launch_fast_k(bool kt, const void* A, int lda, const void* B, int ldb, int M, int N, int K, const LinearEpi& epi, int slots, hipStream_t s, Route* rt, int family) {
+    return kt ? launch_fast<C, true>(A, lda, B, ldb, M, N, K, epi, slots, s, rt, family) : launch_fast<C, false>(A, lda, B, ldb, M, N, K, epi, slots, s, rt, family);
 }
 
 }  // namespace
@@ -487,23 +504,32 @@ bool small_enabled() {                                      // A/B switch PCLIP_
     static const bool on = pclip_env_on("PCLIP_GEMM_SMALL");
     return on;
 }
-int launch_small_one(const half_t* A, int lda, const half_t* B, int ldb, int M, int N, int K, const LinearEpi& epi, hipStream_t s, bool kt = false);
+int launch_small_one(const half_t* A, int lda, const half_t* B, int ldb, int M, int N, int K, const LinearEpi& epi, hipStream_t s, bool kt = false, Route* rt = nullptr);
 
 }  // namespace
 // four-wave 256 x 256 tile with the asm K-loop (pclip_gemm4w.hip)
 bool pclip_gemm4w_supports(int M, int N, int K, int lda, int ldb, int ldc, const void* C, const void* bias, const void* residual, int act);
 int pclip_gemm4w_launch(const half_t* A, int lda, const half_t* B, int ldb, int M, int N, int K, const half_t* bias, half_t* C, int ldc, int act,
                         const half_t* residual, int slots, int rev, int band, hipStream_t s);
+int pclip_gemm4w_launch_var(const half_t* A, int lda, const half_t* B, int ldb, int M, int N, int K, const half_t* bias, half_t* C, int ldc, int act,
+                            const half_t* residual, int slots, int rev, int band, int var, hipStream_t s);
 namespace {
 // K % 64 != 0 (kt): the KT instantiations of every kernel below (K-tail chunks load zeros); with N % 8 == 0 they also take N ragged against the tile.
 // K % 64 == 0 runs exactly what it ran before.
+// forced: -1 the cost model (and the ring kernel where it applies), 0 .. 4 a tile configuration, -2 the generic kernel, -3 the ring kernel (the test entry only).
+// rt: the route of this call (pclip_gemm_route_f16), or null: the process-wide switches.
 int gemm_dispatch(const half_t* A, int lda, const half_t* B, int ldb, int M, int N, int K, LinearEpi epi, int cus, int forced,
-                  bool may_split, hipStream_t s) {
+                  bool may_split, hipStream_t s, Route* rt = nullptr) {
     const bool kt = K % pgemm::BK != 0;
     const bool aligned = (!epi.residual || ((epi.act == 5 || epi.act == 6) && ((uintptr_t)epi.residual & 15) == 0)) && epi.ldc % 8 == 0 && ((uintptr_t)epi.C & 15) == 0 &&
                          (!epi.bias || ((uintptr_t)epi.bias & 15) == 0) && (!kt || N % 8 == 0);
-    if (aligned && forced == -1 && small_enabled() && (epi.act <= 1 || epi.act == 6 || (((uintptr_t)epi.scale | (uintptr_t)epi.shift) & 15) == 0) && small_applies(M, N, cus, kt))
-        return launch_small_one(A, lda, B, ldb, M, N, K, epi, s, kt);
+    const bool ring_ok = aligned && (epi.act <= 1 || epi.act == 6 || (((uintptr_t)epi.scale | (uintptr_t)epi.shift) & 15) == 0);
+    if (ring_ok && forced == -1 && (rt || small_enabled()) && small_applies(M, N, cus, kt))      // (a routed call reads no switch: PCLIP_GEMM_SMALL neither)
+        return launch_small_one(A, lda, B, ldb, M, N, K, epi, s, kt, rt);
+    if (forced == -3) {                                        // one workgroup per 128 x 64 tile, however many there are
+        if (!ring_ok || !(kt || N % 64 == 0)) { pclip_set_error("pclip_gemm_route_f16: N=%d / alignment outside the ring kernel", N); return PCLIP_E_INVALID; }
+        return launch_small_one(A, lda, B, ldb, M, N, K, epi, s, kt, rt);
+    }
     double cost = 1e30;
     int pick = aligned ? best_cfg(M, N, cus, &cost, kt) : -1;
     if (forced == -2) { may_split = false; pick = -1; }        // generic kernel
@@ -527,29 +553,33 @@ int gemm_dispatch(const half_t* A, int lda, const half_t* B, int ldb, int M, int
             if (split < cost) { cost = split; split_cfg = i; split_rows = full_rows; }
         }
         if (split_cfg >= 0) {
-            int rc = gemm_dispatch(A, lda, B, ldb, (int)split_rows, N, K, epi, cus, split_cfg, false, s);
+            int rc = gemm_dispatch(A, lda, B, ldb, (int)split_rows, N, K, epi, cus, split_cfg, false, s, rt);
             if (rc != PCLIP_OK) return rc;
             LinearEpi tail = epi;
             tail.C = epi.C + (size_t)split_rows * epi.ldc;
             if (epi.residual) tail.residual = epi.residual + (size_t)split_rows * epi.ldc;   // act 5 / 6: same row stride as C
-            return gemm_dispatch(A + (size_t)split_rows * lda, lda, B, ldb, M - (int)split_rows, N, K, tail, cus, -1, true, s);
+            return gemm_dispatch(A + (size_t)split_rows * lda, lda, B, ldb, M - (int)split_rows, N, K, tail, cus, -1, true, s, rt);
         }
     }
     ++g_gemm_launches;
     if (pick < 0 && epi.act == 6) epi.act = 0;                  // generic kernel: bias + residual operands, same roundings
     if (pick == 2) {
         // the same tile on four waves with the hand-scheduled K-loop (bit-identical): PCLIP_GEMM_4W=1 (default: see DESIGN §3)
-        if (g_use4w < 0) { const char* e = getenv("PCLIP_GEMM_4W"); g_use4w = e ? (atoi(e) != 0) : PCLIP_GEMM_4W_DEFAULT; }
-        if (g_use4w && pclip_gemm4w_supports(M, N, K, lda, ldb, epi.ldc, epi.C, epi.bias, epi.residual, epi.act)) {
-            const TileOrder& order = tile_order();
-            return pclip_gemm4w_launch(A, lda, B, ldb, M, N, K, epi.bias, epi.C, epi.ldc, epi.act, epi.residual, cus, order.descending(K) ? 1 : 0, N / 256 >= 8 ? order.band : order.band_n, s);
+        if (!rt && g_use4w < 0) { const char* e = getenv("PCLIP_GEMM_4W"); g_use4w = e ? (atoi(e) != 0) : PCLIP_GEMM_4W_DEFAULT; }
+        if ((rt ? rt->use4w : g_use4w) && pclip_gemm4w_supports(M, N, K, lda, ldb, epi.ldc, epi.C, epi.bias, epi.residual, epi.act)) {
+            const TileOrder& order = rt ? rt->order : tile_order();
+            const int rev = order.descending(K) ? 1 : 0, band = N / 256 >= 8 ? order.band : order.band_n;
+            if (!rt) return pclip_gemm4w_launch(A, lda, B, ldb, M, N, K, epi.bias, epi.C, epi.ldc, epi.act, epi.residual, cus, rev, band, s);
+            rt->note(PCLIP_ROUTE_RAN_FOUR_WAVE, false, M, rev, band);
+            return pclip_gemm4w_launch_var(A, lda, B, ldb, M, N, K, epi.bias, epi.C, epi.ldc, epi.act, epi.residual, cus, rev, band, rt->use4w == 2 ? 1 : 0, s);
         }
-        return launch_fast_k<CfgBig>(kt, A, lda, B, ldb, M, N, K, epi, cus, s);
+        return launch_fast_k<CfgBig>(kt, A, lda, B, ldb, M, N, K, epi, cus, s, rt, 2);
     }
-    if (pick == 1) return launch_fast_k<CfgWide>(kt, A, lda, B, ldb, M, N, K, epi, cus, s);
-    if (pick == 0) return launch_fast_k<CfgSmall>(kt, A, lda, B, ldb, M, N, K, epi, 2 * cus, s);
-    if (pick == 3) return launch_fast_k<CfgNarrow>(kt, A, lda, B, ldb, M, N, K, epi, cus, s);
-    if (pick == 4) return launch_fast_k<CfgThin>(kt, A, lda, B, ldb, M, N, K, epi, 2 * cus, s);
+    if (pick == 1) return launch_fast_k<CfgWide>(kt, A, lda, B, ldb, M, N, K, epi, cus, s, rt, 1);
+    if (pick == 0) return launch_fast_k<CfgSmall>(kt, A, lda, B, ldb, M, N, K, epi, 2 * cus, s, rt, 0);
+    if (pick == 3) return launch_fast_k<CfgNarrow>(kt, A, lda, B, ldb, M, N, K, epi, cus, s, rt, 3);
+    if (pick == 4) return launch_fast_k<CfgThin>(kt, A, lda, B, ldb, M, N, K, epi, 2 * cus, s, rt, 4);
+    if (rt) rt->note(PCLIP_ROUTE_RAN_GENERIC, kt, M, 0, 0);
     const int tiles_m = ceil_div(M, 128), tiles_n = ceil_div(N, 128);
     if (kt)
         linear_generic_kernel<true><<<tiles_m * tiles_n, 256, CfgSmall::LDS_BYTES, s>>>(A, lda, B, ldb, M, N, K, epi, tiles_n);
@@ -583,6 +613,35 @@ extern "C" int pclip_gemm_f16(const void* A, int lda, const void* B, int ldb, vo
         nosplit = getenv("PCLIP_GEMM_NOSPLIT") != nullptr;
     }
     return gemm_dispatch((const half_t*)A, lda, (const half_t*)B, ldb, M, N, K, epi, cus, forced, !nosplit, (hipStream_t)stream);
+}
+
+// Test entry (include/pclip.h): the dispatch of the entry above and of the BatchNorm entries below with everything that routes a call taken from the call, and a report
+// of the kernels that ran.  Host code only: it launches the product's kernels.
+extern "C" int pclip_gemm_route_f16(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K, const void* bias, int act,
+                                    const void* residual, const float* scale, const float* shift, int cfg, int may_split, int band, int band_n, int rev,
+                                    int use4w, int cus, int* report, int report_len, pclip_stream_t stream) {
+    PCLIP_REQUIRE(A && B && C && report, "pclip_gemm_route_f16: null pointer");
+    PCLIP_REQUIRE(M >= 0 && N > 0 && K > 0, "pclip_gemm_route_f16: bad shape M=%d N=%d K=%d", M, N, K);
+    PCLIP_REQUIRE(K % 8 == 0, "pclip_gemm_route_f16: K=%d must be a multiple of 8", K);
+    PCLIP_REQUIRE(lda >= K && ldb >= K && ldc >= N && lda % 8 == 0 && ldb % 8 == 0, "pclip_gemm_route_f16: bad leading dims");
+    PCLIP_REQUIRE(act == 0 || act == 1 || act == 2 || act == 3 || act == 5, "pclip_gemm_route_f16: unknown activation %d", act);
+    PCLIP_REQUIRE(cfg >= PCLIP_ROUTE_AUTO && cfg <= PCLIP_ROUTE_RING, "pclip_gemm_route_f16: unknown configuration %d", cfg);
+    PCLIP_REQUIRE(use4w >= 0 && use4w <= 2 && cus >= 1 && rev >= 0 && rev <= 2 && band >= 0 && band_n >= 0, "pclip_gemm_route_f16: bad route arguments");
+    PCLIP_REQUIRE(report_len >= 1, "pclip_gemm_route_f16: the report needs room for the launch count");
+    const bool affine = act >= 2;
+    PCLIP_REQUIRE(!affine || (scale && shift && !bias), "pclip_gemm_route_f16: act %d takes scale and shift, no bias", act);
+    PCLIP_REQUIRE(affine || (!scale && !shift), "pclip_gemm_route_f16: scale / shift without a BatchNorm epilogue");
+    PCLIP_REQUIRE(act != 5 || (residual && N % 64 == 0 && (((uintptr_t)scale | (uintptr_t)shift) & 15) == 0), "pclip_gemm_route_f16: act 5 as pclip_gemm_bn_res_f16");
+    PCLIP_REQUIRE(act == 5 || !affine || !residual, "pclip_gemm_route_f16: a residual with BatchNorm is act 5");
+    PCLIP_REQUIRE(act != 1 || !residual, "pclip_gemm_route_f16: no residual behind QuickGELU");
+    report[0] = 0;
+    if (M == 0) return PCLIP_OK;
+    LinearEpi epi{(const half_t*)bias, (const half_t*)residual, (half_t*)C, ldc, act, scale, shift};
+    if (residual && bias && act == 0) epi.act = 6;              // as pclip_gemm_f16
+    int forced = cfg == PCLIP_ROUTE_GENERIC ? -2 : cfg == PCLIP_ROUTE_RING ? -3 : cfg;
+    if ((act == 2 || act == 3) && !(N % 4 == 0 && (((uintptr_t)scale | (uintptr_t)shift) & 15) == 0)) forced = -2;      // as pclip_gemm_bn_f16
+    Route rt{TileOrder{band, rev, band_n}, use4w, report, (report_len - 1) / PCLIP_ROUTE_FIELDS};
+    return gemm_dispatch((const half_t*)A, lda, (const half_t*)B, ldb, M, N, K, epi, cus, forced, may_split != 0, (hipStream_t)stream, &rt);
 }
 
 namespace {
@@ -768,8 +827,9 @@ bool small_applies(int M, int N, int cus, bool ragged) {
 
 // KT: K % 64 != 0 — the KT instantiation, ceil(N / BN) column tiles and a K-tail (no split-K either way: S == 1)
 template <bool KT>
-int launch_small_kt(const half_t* A, int lda, const half_t* B, int ldb, int M, int N, int K, const LinearEpi& epi, hipStream_t s) {
+int launch_small_kt(const half_t* A, int lda, const half_t* B, int ldb, int M, int N, int K, const LinearEpi& epi, hipStream_t s, Route* rt) {
     if (int e = small_attr()) return e;
+    if (rt) rt->note(PCLIP_ROUTE_RAN_RING, KT, M, 0, 0);
     constexpr int FLAGS = KT ? ACT_KT : 0;
     const int tiles_n = KT ? ceil_div(N, CfgSplit::BN) : N / CfgSplit::BN, grid = ceil_div(M, CfgSplit::BM) * tiles_n;
     const int steps = KT ? ceil_div(K, pgemm::BK) : K / pgemm::BK;
@@ -787,8 +847,8 @@ int launch_small_kt(const half_t* A, int lda, const half_t* B, int ldb, int M, i
 #undef PCLIP_SMALL_LAUNCH
     return pclip_check_launch("gemm_f16 (small M)");
 }
-int launch_small_one(const half_t* A, int lda, const half_t* B, int ldb, int M, int N, int K, const LinearEpi& epi, hipStream_t s, bool kt) {
-    return kt ? launch_small_kt<true>(A, lda, B, ldb, M, N, K, epi, s) : launch_small_kt<false>(A, lda, B, ldb, M, N, K, epi, s);
+int launch_small_one(const half_t* A, int lda, const half_t* B, int ldb, int M, int N, int K, const LinearEpi& epi, hipStream_t s, bool kt, Route* rt) {
+    return kt ? launch_small_kt<true>(A, lda, B, ldb, M, N, K, epi, s, rt) : launch_small_kt<false>(A, lda, B, ldb, M, N, K, epi, s, rt);
 }
 
 // The ring convolution (conv3x3_small_kernel) for a request of a few images.  TAIL: the channel-tail instantiation, ceil(Cout / BN) column tiles.

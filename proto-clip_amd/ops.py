@@ -2,6 +2,7 @@
 and streams; every arithmetic step below is a libpclip kernel.  All functions require CUDA (ROCm)
 tensors and raise PclipError otherwise — there is deliberately no CPU path."""
 import contextvars
+import ctypes
 import math
 import os
 
@@ -789,6 +790,33 @@ def gemm4w(a, w, bias=None, act: int = 0, residual=None, out=None, var: int = 0)
     check(_lib.load().pclip_gemm4w_var_f16(ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(out), out.stride(0), M, N, K, ptr(bias), act, ptr(residual), var,
                                            stream()), "pclip_gemm4w_f16")
     return out
+
+
+ROUTE_AUTO, ROUTE_GENERIC, ROUTE_RING = _lib.ROUTE_AUTO, _lib.ROUTE_GENERIC, _lib.ROUTE_RING      # cfg of gemm_route (0 .. 4: 128x128, 256x128, 256x256, 256x64, 256x32 tiles)
+
+
+def gemm_route(a, w, bias=None, act: int = 0, residual=None, scale=None, shift=None, out=None, cfg: int = ROUTE_AUTO, may_split: bool = True,
+               band: int = 0, band_n: int = 0, rev: int = 2, use4w: int = 1, cus: int = 0):
+    """Test entry (pclip_gemm_route_f16): ops.gemm / gemm_bn / gemm_bn_res_relu through the product's dispatch with the route taken from THIS call — act 0 / 1
+    (bias, residual), 2 / 3 BatchNorm (+ReLU), 5 BatchNorm + residual + ReLU; cfg, row split, tile order, the 256 x 256 kernel and `cus`, which stands in for the
+    device's CU count (0: the device's).  Returns (out, launches): one dict per kernel launch — family (a name of _lib.ROUTE_RAN), kt, rows, rev, band."""
+    require_cuda(a, w, bias, residual, scale, shift, out)
+    M, K = a.shape
+    N = w.shape[0]
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float16, device=a.device)
+    lib = _lib.load()
+    fields, cap = _lib.ROUTE_FIELDS, 8
+    report = (ctypes.c_int * (1 + fields * cap))()
+    check(lib.pclip_gemm_route_f16(ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(out), out.stride(0), M, N, K, ptr(bias), act, ptr(residual), ptr(scale), ptr(shift),
+                                   cfg, int(may_split), band, band_n, rev, use4w, cus or lib.pclip_device_cus(), report, len(report), stream()), "pclip_gemm_route_f16")
+    if report[0] > cap:
+        raise _lib.PclipError(f"pclip_gemm_route_f16: {report[0]} launches, the report holds {cap}")
+    launches = []
+    for i in range(report[0]):
+        family, kt, rows, rv, bd = report[1 + fields * i:1 + fields * (i + 1)]
+        launches.append(dict(family=_lib.ROUTE_RAN[family], kt=bool(kt), rows=rows, rev=bool(rv), band=bd))
+    return out, launches
 
 
 class gemm_eight_wave:

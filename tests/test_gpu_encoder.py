@@ -71,27 +71,31 @@ def test_gemm_row_split(ops, M, N, K):
         assert launches == 2                                # 2 full rounds of 256x256 tiles + the last 6912 rows
 
 
-def test_gemm_banded_tile_order_is_bit_identical(ops, monkeypatch):
+def test_gemm_banded_tile_order_is_bit_identical(ops):
     """PCLIP_GEMM_BAND (tile order in bands of column tiles): a pure speed knob — same bits, including a
-    ragged last band (12 column tiles in bands of 5) and a partial last row block."""
+    ragged last band (12 column tiles in bands of 5) and a partial last row block.  The orders are taken per call through the test entry
+    (the process reads PCLIP_GEMM_BAND / _REV once, at its first GEMM: setting them here compared the default order with itself) and every
+    launch's order is asserted from the entry's report."""
     M, N, K = 70001, 3072, 128
     g = torch.Generator(device="cuda").manual_seed(3)
     a = torch.randn(M, K, device="cuda", generator=g).half()
     w = (torch.randn(N, K, device="cuda", generator=g) * K ** -0.5).half()
     b = torch.randn(N, device="cuda", generator=g).half()
-    monkeypatch.setenv("PCLIP_GEMM_CFG_LIVE", "1")
-    ref = ops.gemm(a, w, b, act=1)
+    ref, plain = ops.gemm_route(a, w, b, act=1, band=0, rev=0)                # column tiles fastest, ascending
+    assert plain and all((l["rev"], l["band"]) == (False, 0) for l in plain), plain
+    assert torch.equal(ops.gemm(a, w, b, act=1), ref)                        # the product entry: the same bits in its own order
     for band in (6, 5, 1):
-        monkeypatch.setenv("PCLIP_GEMM_BAND", str(band))
-        assert torch.equal(ops.gemm(a, w, b, act=1), ref), band
-    monkeypatch.delenv("PCLIP_GEMM_BAND")
+        got, launches = ops.gemm_route(a, w, b, act=1, band=band, rev=0)
+        assert [(l["family"], l["rows"]) for l in launches] == [(l["family"], l["rows"]) for l in plain]
+        assert all((l["rev"], l["band"]) == (False, band) for l in launches), launches        # every launch has >= 12 column tiles: all of them banded
+        assert torch.equal(got, ref), band
     for rev in (0, 1, 2):                                   # PCLIP_GEMM_REV: tiles in descending order (default 2: launches with K <= 1024) — same bits
-        monkeypatch.setenv("PCLIP_GEMM_REV", str(rev))
-        assert torch.equal(ops.gemm(a, w, b, act=1), ref), rev
-    monkeypatch.delenv("PCLIP_GEMM_REV")
+        got, launches = ops.gemm_route(a, w, b, act=1, rev=rev)
+        assert all(l["rev"] == (rev != 0) and l["band"] == 0 for l in launches), launches
+        assert torch.equal(got, ref), rev
 
 
-def test_gemm_quickgelu_pipelined_epilogue_is_the_two_slab_epilogue(ops, monkeypatch):
+def test_gemm_quickgelu_pipelined_epilogue_is_the_two_slab_epilogue(ops):
     """256 x 256 tiles stage a QuickGELU epilogue as a four-slab pipeline (pgemm::epilogue_pipe: slab k = 32-row block k of every wave, two halves of the
     staging buffer, the activation arithmetic of slab k + 1 under the stores of slab k); every other tile shape keeps the two-slab pass.  Same bits —
     on a shape with a partial last row block — and within 3 fp16 ulp of the fp32 reference with the reference's three roundings."""
@@ -100,12 +104,10 @@ def test_gemm_quickgelu_pipelined_epilogue_is_the_two_slab_epilogue(ops, monkeyp
     a = torch.randn(M, K, device="cuda", generator=g).half()
     w = (torch.randn(N, K, device="cuda", generator=g) * K ** -0.5).half()
     b = torch.randn(N, device="cuda", generator=g).half()
-    monkeypatch.setenv("PCLIP_GEMM_CFG_LIVE", "1")
-    monkeypatch.setenv("PCLIP_GEMM_CFG", "2")               # 256 x 256 tiles
-    big = ops.gemm(a, w, b, act=1)
-    monkeypatch.setenv("PCLIP_GEMM_CFG", "0")               # 128 x 128 tiles: epilogue_f16
-    assert torch.equal(ops.gemm(a, w, b, act=1), big)
-    monkeypatch.delenv("PCLIP_GEMM_CFG")
+    big, l_big = ops.gemm_route(a, w, b, act=1, cfg=2, use4w=0)      # 256 x 256 tiles on eight waves (forced per call: PCLIP_GEMM_CFG is read once per process)
+    small, l_small = ops.gemm_route(a, w, b, act=1, cfg=0)           # 128 x 128 tiles: epilogue_f16
+    assert [(l["family"], l["rows"]) for l in l_big] == [("cfg2", M)] and [(l["family"], l["rows"]) for l in l_small] == [("cfg0", M)], (l_big, l_small)
+    assert torch.equal(small, big)
     rows = torch.cat([torch.arange(0, 600), torch.arange(M - 300, M)]).cuda()
     h = po.r16((a[rows].float() @ w.float().t() + b.float()).cpu())
     ref = po.r16(h * po.r16(torch.sigmoid(po.r16(1.702 * h))))
@@ -637,32 +639,51 @@ def test_resnet_tower_against_reference(ops, tag):
     assert torch.equal(model.encode_image(imgs.cuda()).cpu(), f.cpu())
 
 
-@pytest.mark.parametrize("M,N,K,relu", [(5000, 64, 576, True), (3136 * 4, 64, 64, True), (2000, 32, 64, True), (4096, 256, 64, False),
-                                        (70000, 128, 1152, True), (777, 2048, 512, True), (50432, 512, 128, False)])
-def test_gemm_bn_equals_gemm_then_bn_act(ops, M, N, K, relu):
+BN_TILES = ((128, 128), (256, 128), (256, 256), (256, 64), (256, 32))      # the tile configurations PCLIP_GEMM_BN_CFG forces (read once per process: never in a test)
+
+
+def _with_forced_cfgs(cases):
+    """The cases as they were (cfg None: the product entry, ids unchanged) + every tile configuration that fits N, forced per call."""
+    out = [pytest.param(*c, None, id="-".join(str(v) for v in c)) for c in cases]
+    return out + [pytest.param(*c, cfg, id="-".join(str(v) for v in c) + f"-cfg{cfg}") for c in cases for cfg, (_, bn) in enumerate(BN_TILES) if c[1] % bn == 0]
+
+
+@pytest.mark.parametrize("M,N,K,relu,cfg", _with_forced_cfgs([(5000, 64, 576, True), (3136 * 4, 64, 64, True), (2000, 32, 64, True), (4096, 256, 64, False),
+                                                              (70000, 128, 1152, True), (777, 2048, 512, True), (50432, 512, 128, False)]))
+def test_gemm_bn_equals_gemm_then_bn_act(ops, M, N, K, relu, cfg):
     """conv + eval BatchNorm (+ ReLU) as one GEMM launch (scale / shift strips in the epilogue; 256x64 tiles for 64-channel
-    convolutions, the generic kernel for 32) must reproduce conv-GEMM followed by pclip_bn_act_f16 bit for bit."""
+    convolutions, the generic kernel for 32) must reproduce conv-GEMM followed by pclip_bn_act_f16 bit for bit.  cfg: the tile
+    configuration forced through the test entry, asserted from its report."""
     g = torch.Generator(device="cuda").manual_seed(M + N)
     a = (torch.randn(M, K, device="cuda", generator=g) * 0.5).half()
     w = (torch.randn(N, K, device="cuda", generator=g) * K ** -0.5).half()
     ss = torch.stack([1 + 0.3 * torch.randn(N, device="cuda", generator=g), 0.2 * torch.randn(N, device="cuda", generator=g)]).contiguous()
     ref = ops.bn_act(ops.gemm(a, w), ss[0], ss[1], relu=relu)
-    got = ops.gemm_bn(a, w, ss[0], ss[1], relu=relu)
+    if cfg is None:
+        got = ops.gemm_bn(a, w, ss[0], ss[1], relu=relu)
+    else:
+        got, launches = ops.gemm_route(a, w, act=3 if relu else 2, scale=ss[0], shift=ss[1], cfg=cfg)
+        assert [(l["family"], l["rows"]) for l in launches] == [(f"cfg{cfg}", M)], launches
     assert torch.equal(got, ref)
 
 
-@pytest.mark.parametrize("M,N,K", [(5000, 256, 64), (3136 * 8, 256, 64), (70000, 512, 128), (777, 2048, 512), (49, 2048, 512), (200, 64, 64),
-                                   (50432, 1024, 256)])
-def test_gemm_bn_residual_relu_equals_separate(ops, M, N, K):
+@pytest.mark.parametrize("M,N,K,cfg", _with_forced_cfgs([(5000, 256, 64), (3136 * 8, 256, 64), (70000, 512, 128), (777, 2048, 512), (49, 2048, 512), (200, 64, 64),
+                                                         (50432, 1024, 256)]))
+def test_gemm_bn_residual_relu_equals_separate(ops, M, N, K, cfg):
     """conv3 + bn3 + identity add + ReLU of a bottleneck in one launch (pclip_gemm_bn_res_f16: persistent kernels incl. the row
-    split, and the ring kernel for small M) against GEMM followed by pclip_bn_act_f16: bit for bit."""
+    split, and the ring kernel for small M) against GEMM followed by pclip_bn_act_f16: bit for bit.  cfg: the tile configuration forced
+    through the test entry, asserted from its report."""
     g = torch.Generator(device="cuda").manual_seed(M + N + K)
     a = (torch.randn(M, K, device="cuda", generator=g) * 0.5).half()
     w = (torch.randn(N, K, device="cuda", generator=g) * K ** -0.5).half()
     res = torch.randn(M, N, device="cuda", generator=g).half()
     ss = torch.stack([1 + 0.3 * torch.randn(N, device="cuda", generator=g), 0.2 * torch.randn(N, device="cuda", generator=g)]).contiguous()
     ref = ops.bn_act(ops.gemm(a, w), ss[0], ss[1], residual=res, relu=True)
-    got = ops.gemm_bn_res_relu(a, w, ss[0], ss[1], res)
+    if cfg is None:
+        got = ops.gemm_bn_res_relu(a, w, ss[0], ss[1], res)
+    else:
+        got, launches = ops.gemm_route(a, w, act=5, residual=res, scale=ss[0], shift=ss[1], cfg=cfg)
+        assert [(l["family"], l["rows"]) for l in launches] == [(f"cfg{cfg}", M)], launches
     assert torch.equal(got, ref)
     assert (got >= 0).all()
 
