@@ -666,6 +666,30 @@ int pclip_prompt_embed_f16(const int64_t* tokens, int L_tok, const void* tok_emb
 int pclip_prompt_ctx_grad_f32(const void* dx, int N, int L_out, int n_ctx, int W, int class_specific, float* dctx, float* part, int nslice,
                               pclip_stream_t stream);
 
+/* ---- visual prompt tuning (VPT: token rows trained through the frozen vision tower; csrc/pclip_vpt.hip lists the rounding points) ---------- */
+
+/* A sequence of the vision tower with P learned rows BEHIND its L0 stem rows (class token, patches): L = L0 + P rows, L <= PCLIP_VPT_MAX_L (the
+ * attention kernels' resident-K/V envelope).  ctx is fp32 [P, W]; a prompt element enters the fp16 stream rounded once, round to nearest even, with
+ * no positional embedding.  All three entries: W % 8 == 0, P >= 1, L0 >= 0, B >= 0 (B == 0 returns PCLIP_OK and touches nothing), B * L * W within
+ * an int, operands 16-byte aligned; flat passes of 16-byte vectors, no atomics: two calls give the same bits. */
+#define PCLIP_VPT_MAX_L 288
+#define PCLIP_VPT_SLICE 16
+
+/* out [B * L, W] fp16 = cat(t.view(B, L0, W), r16(ctx) broadcast over the batch) along the rows of every sequence; t [B * L0, W] fp16 is copied bit
+ * for bit (t may be NULL when L0 == 0).  out must not alias t. */
+int pclip_vpt_append_f16(const void* t, const float* ctx, int B, int L0, int P, int W, void* out, pclip_stream_t stream);
+
+/* In place on the stream x [B * L, W] fp16: rows L0 .. L - 1 of every sequence become r16(ctx); the other rows are not touched. */
+int pclip_vpt_replace_f16(void* x, const float* ctx, int B, int L0, int P, int W, pclip_stream_t stream);
+
+/* dctx [P, W] fp32 = sum over the B sequences of f32(g[b, L0 + j, :]), g [B * L, W] fp16 (L0 == 0: a compact [B * P, W]), in ONE fixed order: slices
+ * of PCLIP_VPT_SLICE consecutive images; inside a slice, ascending image order into one fp32 accumulator per column -> part [nslice][P * W]; then the
+ * slices in ascending order into one accumulator; every sum starts from its first term.  nslice must be ceil(B / PCLIP_VPT_SLICE); part may be NULL
+ * when that is 1 (dctx is then the first stage's output).  This is pclip_prompt_ctx_grad_f32's rule.  clear != 0: the same pass writes exact zeros
+ * over the prompt rows of g it has read (the lane that loaded an element stores the zero, after its load); rows l < L0 are neither read nor
+ * written. */
+int pclip_vpt_grad_f32(void* g, int B, int L0, int P, int W, int clear, float* dctx, float* part, int nslice, pclip_stream_t stream);
+
 /* ---- backward of the embedding stages in front of block 0 (whole-tower fine-tuning; csrc/pclip_embed_bwd.hip lists every rounding) ---------- */
 
 /* Envelope of both entry points: B >= 1, 1 <= L <= 4096, W % 64 == 0, W <= 2048 (and V >= 1); operands 16-byte aligned.  fp32 accumulation, no atomics:

@@ -8,3 +8,4 @@ __version__ = "0.1.0"
 from . import _lib  # noqa: F401  (ctypes binding; the shared library is loaded on first use)
 from ._lib import PclipError  # noqa: F401
 from . import tip_adapter  # noqa: F401,E402  (the Tip-Adapter / Tip-Adapter-F baselines: tip_logits, tip_classify, search_hp, TipAdapterF, run_tip_adapter[_F])
+from . import vpt  # noqa: F401,E402  (visual prompt tuning through the frozen vision tower: VisualPromptLearner, VPT, run_vpt)

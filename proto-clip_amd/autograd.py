@@ -318,14 +318,23 @@ class TowerTailFn(torch.autograd.Function):
     which then receives the stream gradient that leaves the first block) -> features [B, E] through `len(blocks)` residual blocks, the row pick
     (class token / EOT row), the final LayerNorm and the projection.  Arguments after the bookkeeping: the 12 parameters of every taped block (block
     order, each in _block_params' order), then ln.weight, ln.bias, proj.  The backward issues a weight / bias gradient only for a parameter that
-    requires one: a frozen tower under a trainable input pays for none."""
+    requires one: a frozen tower under a trainable input pays for none.
+
+    deep (visual prompt tuning; None otherwise): fp32 [n_deep, P, W], a tensor on the tape.  Before taped block i's ln_1, 1 <= i <= n_deep, the last P rows
+    of every sequence are REPLACED by r16(deep[i - 1]) (ops.vpt_replace_); the backward sums those rows of the stream gradient that leaves block i's ln_1
+    backward into ddeep[i - 1] and clears them in the same pass (ops.vpt_grad, clear): a replaced row passes no gradient to the block below.  Called
+    with nothing that requires a gradient (under torch.no_grad()) the forward issues the same kernels and keeps nothing for a backward."""
 
     @staticmethod
-    def forward(ctx, x, h0, meta, *params):
+    def forward(ctx, x, h0, deep, meta, *params):
         B, L, heads, causal, select, sel_rows, first_token, cache = meta
         nb = (len(params) - 3) // 12
         W = x.shape[1]
         ctx.meta, ctx.nb = meta, nb
+        n_deep = 0 if deep is None else deep.shape[0]
+        ctx.deep_shape = None if deep is None else tuple(deep.shape)
+        taping = any(ctx.needs_input_grad)                                     # under torch.no_grad() nothing is kept: no copies, no tape
+        keep = (lambda t: t.clone()) if taping else (lambda t: None)
         if ctx.needs_input_grad[0] and nb > 0:                                 # the blocks update the stream in place: a taped input keeps its values
             x = x.clone()
         tape = []
@@ -335,7 +344,7 @@ class TowerTailFn(torch.autograd.Function):
         for i in range(nb):
             ln1w, ln1b, win, bin_, wout, bout, ln2w, ln2b, wfc, bfc, wpr, bpr = params[12 * i:12 * i + 12]
             last = i == nb - 1
-            rec = {"x_in": x.clone(), "h1": h, "picked": False}
+            rec = {"x_in": keep(x), "h1": h, "picked": False}
             if select is not None and last and first_token and not causal:
                 kv = ops.gemm(h, win[W:3 * W], bin_[W:3 * W])
                 q = ops.gemm(select(h), win[0:W], bin_[0:W])
@@ -350,13 +359,16 @@ class TowerTailFn(torch.autograd.Function):
                     rec.update(picked=True)
             ops.gemm(a, wout, bout, residual=x, out=x)
             h = ops.layernorm(x, ln2w, ln2b)
-            rec.update(a=a, x_mid=x.clone(), h2=h)
+            rec.update(a=a, x_mid=keep(x), h2=h)
             f = ops.gemm(h, wfc, bfc, act=1)
             rec.update(f=f)
             ops.gemm(f, wpr, bpr, residual=x, out=x)
             if not last:
+                if i < n_deep:                                                 # block i + 1 reads its own prompt rows: replaced before its ln_1
+                    ops.vpt_replace_(x, deep[i], B, L - deep.shape[1])
                 h = ops.layernorm(x, params[12 * (i + 1)], params[12 * (i + 1) + 1])
-            tape.append(rec)
+            if taping:
+                tape.append(rec)
         if select is not None and nb == 0:
             x = select(x)
         lnw, lnb, proj = params[-3:]
@@ -372,7 +384,11 @@ class TowerTailFn(torch.autograd.Function):
         params = ctx.saved_tensors
         nb = ctx.nb
         grads = [None] * len(params)
-        need = ctx.needs_input_grad[3:]
+        need = ctx.needs_input_grad[4:]
+        ddeep = None
+        if ctx.deep_shape is not None and ctx.needs_input_grad[2]:
+            ddeep = torch.zeros(ctx.deep_shape, dtype=torch.float32, device=g.device)
+        n_deep = 0 if ctx.deep_shape is None else ctx.deep_shape[0]
         wgrad = lambda k, dy, x: _weight_grad(dy, x) if need[k] else None      # a frozen parameter's gradient is not computed at all
         bgrad = lambda k, dy: _bias_grad(dy) if need[k] else None
         lnw, lnb, proj = params[-3:]
@@ -426,6 +442,11 @@ class TowerTailFn(torch.autograd.Function):
             dh1 = ops.gemm(dqkv, wT(("tail_wT", i, "in"), win))
             del dqkv
             gx, grads[o + 0], grads[o + 1] = ops.layernorm_backward_f32(rec["x_in"], ln1w, dh1, residual=gx)
+            if 1 <= i <= n_deep:                                               # the replaced rows: their gradient is deep[i - 1]'s and goes no further
+                P = ctx.deep_shape[1]
+                d = ops.vpt_grad(gx, B, L - P, P, clear=True)
+                if ddeep is not None:
+                    ddeep[i - 1] = d
         dx = None
         if ctx.needs_input_grad[0]:                                            # the stream gradient that leaves the first taped block (block 0's ln_1 backward)
             dx = gx
@@ -433,7 +454,7 @@ class TowerTailFn(torch.autograd.Function):
                 dx = torch.zeros(B * L, W, dtype=torch.float16, device=gx.device)
                 dx[sel_rows] = gx
         out = [gr.reshape(p.shape) if n else None for p, gr, n in zip(params, grads, need)]
-        return (dx, None, None) + tuple(out)
+        return (dx, None, ddeep, None) + tuple(out)
 
 
 def tower_plan(tower_name, blocks, prefix_params, head_params):
@@ -454,8 +475,9 @@ def tower_plan(tower_name, blocks, prefix_params, head_params):
     return first
 
 
-def run_tower_tail(x, h0, blocks, first, B, L, heads, causal, select, sel_rows, first_token, ln, proj, cache, what):
-    """The taped tail: blocks[first:] + ln + proj on the residual stream x [B*L, W] (h0: ln_1 of blocks[first] when the caller already has it)."""
+def run_tower_tail(x, h0, blocks, first, B, L, heads, causal, select, sel_rows, first_token, ln, proj, cache, what, deep=None):
+    """The taped tail: blocks[first:] + ln + proj on the residual stream x [B*L, W] (h0: ln_1 of blocks[first] when the caller already has it).
+    deep: TowerTailFn's pack of deep visual prompts, fp32 [n_deep, P, W] with n_deep < len(blocks) - first and P < L."""
     if ops.splitk_active(B) or ops.splitk_active(B * L):
         raise PclipError(f"{what}: a differentiable pass inside ops.low_latency() is not supported (the split-K linears have no backward); "
                          f"leave the context or freeze the tower (B={B}, L={L})")
@@ -466,8 +488,13 @@ def run_tower_tail(x, h0, blocks, first, B, L, heads, causal, select, sel_rows, 
     for p in params:
         if p.requires_grad and p.dtype not in (torch.float16, torch.float32):
             raise PclipError(f"{what}: unsupported parameter dtype {p.dtype}")
+    if deep is not None:
+        if deep.dtype != torch.float32 or deep.dim() != 3 or deep.shape[2] != x.shape[1] or not 1 <= deep.shape[1] < L:
+            raise PclipError(f"{what}: deep prompts {deep.dtype} {tuple(deep.shape)} are not float32 [n_deep, P, {x.shape[1]}] with 1 <= P < L={L}")
+        if not 1 <= deep.shape[0] < len(blocks) - first:
+            raise PclipError(f"{what}: {deep.shape[0]} deep prompt layers, but only blocks {first + 1}..{len(blocks) - 1} can take one")
     meta = (B, L, heads, causal, select, sel_rows, first_token, cache)
-    return TowerTailFn.apply(x, h0, meta, *params)
+    return TowerTailFn.apply(x, h0, deep, meta, *params)
 
 
 # ---- the stages in front of block 0: whole-tower fine-tuning (CLIP.unfreeze(stem=...)) ---------------------------------------------------------------
@@ -576,3 +603,31 @@ class PromptEmbedFn(torch.autograd.Function):
         if dx.dtype != torch.float16:
             dx = ops.cast_f16(dx.float())
         return ops.prompt_ctx_grad(dx, N, L_out, n_ctx, per_class), None, None, None, None, None
+
+
+# ---- visual prompt tuning (VPT): the stream that enters block 0 as a function of the first layer's fp32 prompt rows ------------------------------------
+
+class VptEmbedFn(torch.autograd.Function):
+    """(ctx0 [P, W] fp32, t [B * L0, W] fp16, ln_pre.weight, ln_pre.bias, B, L0) -> x [B * (L0 + P), W] fp16 = ln_pre(append(t, ctx0)): the stem's
+    tokens (class + patches + positional embedding, a constant of the frozen stem) with the prompt rows behind them, then ln_pre (clip/model.py:227).
+    backward: only the B * P prompt rows of dx have a consumer while the stem is frozen — they are gathered into a compact buffer, taken through the
+    LayerNorm backward against their pre-LayerNorm values (r16(ctx0) in every sequence: rebuilt, not kept) and summed over the batch in
+    pclip_vpt_grad_f32's fixed order.  ln_pre's parameters and t get no gradient here."""
+
+    @staticmethod
+    def forward(ctx, ctx0, t, lnw, lnb, B, L0):
+        ctx.shape = (int(B), int(L0), ctx0.shape[0])
+        ctx.save_for_backward(ctx0, lnw)
+        return ops.layernorm(ops.vpt_append(t, ctx0, B, L0), _f32(lnw), _f32(lnb))
+
+    @staticmethod
+    def backward(ctx, dx):
+        ctx0, lnw = ctx.saved_tensors
+        B, L0, P = ctx.shape
+        W = ctx0.shape[1]
+        if any(ctx.needs_input_grad[1:4]):
+            raise NotImplementedError("VptEmbedFn: only the prompt rows get a gradient (the stem and ln_pre are frozen under visual prompt tuning)")
+        dy = _stem_dx(dx).view(B, L0 + P, W)[:, L0:, :].reshape(B * P, W)        # the prompt rows, compact
+        rows = ops.vpt_append(None, ctx0, B, 0)                                   # what ln_pre read on those rows
+        dt, _, _ = ops.layernorm_backward_f32(rows, _f32(lnw), dy)
+        return ops.vpt_grad(dt, B, 0, P), None, None, None, None, None

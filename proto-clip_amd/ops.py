@@ -1180,6 +1180,59 @@ def prompt_ctx_grad(dx, N: int, L_out: int, n_ctx: int, class_specific: bool = F
     return dctx
 
 
+def _vpt_ctx(who: str, ctx, W: int):
+    """The fp32 [P, W] prompt rows of one layer, contiguous."""
+    if ctx.dtype != torch.float32:
+        raise _lib.PclipError(f"{who}: visual prompt rows must be float32, got {ctx.dtype}")
+    if ctx.dim() != 2 or ctx.shape[1] != W or ctx.shape[0] < 1:
+        raise _lib.PclipError(f"{who}: visual prompt rows {tuple(ctx.shape)} are not [P, {W}] with P >= 1")
+    return ctx.contiguous()
+
+
+def vpt_append(t, ctx, B: int, L0: int) -> torch.Tensor:
+    """[B * (L0 + P), W] fp16: every sequence's L0 rows of t [B * L0, W] followed by the fp32 prompt rows ctx [P, W] rounded once to fp16 — the bits of
+    torch.cat([t.view(B, L0, W), ctx.half().expand(B, P, W)], 1) (pclip_vpt_append_f16).  L0 == 0 (t may be None): the broadcast rows alone."""
+    require_cuda(t, ctx)
+    W = ctx.shape[-1]
+    ctx = _vpt_ctx("vpt_append", ctx, W)
+    P = ctx.shape[0]
+    if L0 > 0:
+        t = _f16c(t)
+        if t.dim() != 2 or t.shape != (B * L0, W):
+            raise _lib.PclipError(f"vpt_append: t {tuple(t.shape)} is not [B * L0, W] = [{B * L0}, {W}]")
+    out = torch.empty(B * (L0 + P), W, dtype=torch.float16, device=ctx.device)
+    check(_lib.load().pclip_vpt_append_f16(ptr(t) if L0 > 0 else None, ptr(ctx), B, L0, P, W, ptr(out), stream()), "pclip_vpt_append_f16")
+    return out
+
+
+def vpt_replace_(x, ctx, B: int, L0: int) -> torch.Tensor:
+    """In place on the stream x [B * (L0 + P), W] fp16: the last P rows of every sequence become the fp32 rows ctx [P, W] rounded once to fp16
+    (pclip_vpt_replace_f16).  Returns x."""
+    require_cuda(x, ctx)
+    W = x.shape[-1]
+    ctx = _vpt_ctx("vpt_replace_", ctx, W)
+    P = ctx.shape[0]
+    if x.dtype != torch.float16 or not x.is_contiguous() or x.dim() != 2 or x.shape[0] != B * (L0 + P):
+        raise _lib.PclipError(f"vpt_replace_: x {x.dtype} {tuple(x.shape)} is not a contiguous float16 [B * (L0 + P), W] = [{B * (L0 + P)}, {W}]")
+    check(_lib.load().pclip_vpt_replace_f16(ptr(x), ptr(ctx), B, L0, P, W, stream()), "pclip_vpt_replace_f16")
+    return x
+
+
+def vpt_grad(g, B: int, L0: int, P: int, clear: bool = False) -> torch.Tensor:
+    """fp32 [P, W]: the prompt rows (L0 .. L0 + P - 1 of every sequence) of the gradient stream g [B * (L0 + P), W] fp16 summed over the B sequences
+    in pclip_vpt_grad_f32's fixed order (slices of 16 images, then the slices).  L0 == 0: g is a compact [B * P, W].  clear: the pass also writes
+    exact zeros over those rows of g, IN PLACE — the rows of a replaced deep prompt pass no gradient to the block below."""
+    require_cuda(g)
+    if g.dtype != torch.float16 or not g.is_contiguous() or g.dim() != 2 or g.shape[0] != B * (L0 + P):
+        raise _lib.PclipError(f"vpt_grad: g {g.dtype} {tuple(g.shape)} is not a contiguous float16 [B * (L0 + P), W] with B={B}, L0={L0}, P={P}")
+    W = g.shape[1]
+    dctx = torch.empty(P, W, dtype=torch.float32, device=g.device) if B > 0 else torch.zeros(P, W, dtype=torch.float32, device=g.device)
+    nslice = (B + _lib.VPT_SLICE - 1) // _lib.VPT_SLICE
+    part = torch.empty(nslice, P * W, dtype=torch.float32, device=g.device) if nslice > 1 else None      # the kernel's workspace
+    check(_lib.load().pclip_vpt_grad_f32(ptr(g), B, L0, P, W, int(bool(clear)), ptr(dctx), ptr(part), nslice, stream()), "pclip_vpt_grad_f32")
+    return dctx
+
+
 def gather_eot(x, tokens, B: int, L: int, W: int) -> torch.Tensor:
     tokens = tokens.to(torch.int64).contiguous()
     out = torch.empty(B, W, dtype=torch.float16, device=x.device)
