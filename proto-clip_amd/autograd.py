@@ -18,6 +18,7 @@ import torch
 
 from . import ops
 from ._lib import PclipError
+from .tower import _block_params, residual_block, vit_stem
 
 INFO_NCE_TEMPERATURE = 0.1      # info-nce-pytorch default
 
@@ -282,20 +283,15 @@ def wants_grad(*tensors) -> bool:
 
 
 # ---- fine-tuning the transformer towers: a differentiable tail of residual blocks + final LayerNorm + projection ---------------------------------
-# (clip/model.py:171-190 per block, 233-236 / 348-352 for the heads.)  The taped forward issues the SAME kernel calls as clip.model._run_blocks'
-# batch path, so its features equal the untaped ones bit for bit, and keeps the tensors the backward reads (copies where the residual stream is
-# updated in place).  The backward is a sequence of library kernels: pclip_gemm_f16 for dX = dY W (W^T cached per weight version) and dW = dY^T X
-# (transposed operands, the token count padded to a multiple of 8 with zero rows), pclip_colsum_f16 for the bias gradients,
-# pclip_quick_gelu_backward_f16 on the recomputed c_fc pre-activation, pclip_layernorm_backward_g32_f16 (which also adds the gradient that passes
-# the LayerNorm on the residual stream: one rounding per add) and pclip_attention_backward_f16.  The activation-gradient stream is fp16; parameter
-# gradients arrive in the parameter's dtype.
+# (clip/model.py:171-190 per block, 233-236 / 348-352 for the heads.)  The taped forward walks the blocks with tower.residual_block, the one statement of a
+# block that the frozen walk (tower._run_blocks) issues too, so its features equal the untaped ones bit for bit; its recorder keeps the tensors the
+# backward reads (copies where the residual stream is updated in place).  The backward is a sequence of library kernels: pclip_gemm_f16 for dX = dY W
+# (W^T cached per weight version) and dW = dY^T X (transposed operands, the token count padded to a multiple of 8 with zero rows), pclip_colsum_f16
+# for the bias gradients, pclip_quick_gelu_backward_f16 on the recomputed c_fc pre-activation, pclip_layernorm_backward_g32_f16 (which also adds the
+# gradient that passes the LayerNorm on the residual stream: one rounding per add) and pclip_attention_backward_f16.  The activation-gradient stream is
+# fp16; parameter gradients arrive in the parameter's dtype.
 
 TOWER_MAX_L = 288      # the attention backward's envelope (the forward's resident-K/V kernels)
-
-def _block_params(blk):
-    """The 12 parameters of a residual block in the order TowerTailFn takes them."""
-    return [blk.ln_1.weight, blk.ln_1.bias, blk.attn.in_proj_weight, blk.attn.in_proj_bias, blk.attn.out_proj.weight, blk.attn.out_proj.bias,
-            blk.ln_2.weight, blk.ln_2.bias, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias, blk.mlp.c_proj.weight, blk.mlp.c_proj.bias]
 
 
 def _pad_rows8(t):
@@ -329,40 +325,19 @@ class TowerTailFn(torch.autograd.Function):
     def forward(ctx, x, h0, deep, meta, *params):
         B, L, heads, causal, select, sel_rows, first_token, cache = meta
         nb = (len(params) - 3) // 12
-        W = x.shape[1]
         ctx.meta, ctx.nb = meta, nb
         n_deep = 0 if deep is None else deep.shape[0]
         ctx.deep_shape = None if deep is None else tuple(deep.shape)
         taping = any(ctx.needs_input_grad)                                     # under torch.no_grad() nothing is kept: no copies, no tape
-        keep = (lambda t: t.clone()) if taping else (lambda t: None)
         if ctx.needs_input_grad[0] and nb > 0:                                 # the blocks update the stream in place: a taped input keeps its values
             x = x.clone()
         tape = []
-        h = None
         if nb > 0:
             h = h0 if h0 is not None else ops.layernorm(x, params[0], params[1])
         for i in range(nb):
-            ln1w, ln1b, win, bin_, wout, bout, ln2w, ln2b, wfc, bfc, wpr, bpr = params[12 * i:12 * i + 12]
             last = i == nb - 1
-            rec = {"x_in": keep(x), "h1": h, "picked": False}
-            if select is not None and last and first_token and not causal:
-                kv = ops.gemm(h, win[W:3 * W], bin_[W:3 * W])
-                q = ops.gemm(select(h), win[0:W], bin_[0:W])
-                a, x = ops.attention_first_queries(q, kv, B, L, 1, heads), select(x)
-                rec.update(q=q, kv=kv, picked=True)
-            else:
-                qkv = ops.gemm(h, win, bin_)
-                a = ops.attention(qkv, B, L, heads, causal=causal)
-                rec.update(qkv=qkv)
-                if select is not None and last:
-                    a, x = select(a), select(x)
-                    rec.update(picked=True)
-            ops.gemm(a, wout, bout, residual=x, out=x)
-            h = ops.layernorm(x, ln2w, ln2b)
-            rec.update(a=a, x_mid=keep(x), h2=h)
-            f = ops.gemm(h, wfc, bfc, act=1)
-            rec.update(f=f)
-            ops.gemm(f, wpr, bpr, residual=x, out=x)
+            rec = {} if taping else None
+            x, _ = residual_block(x, h, params[12 * i:12 * i + 12], B, L, heads, causal, select if last else None, first_token, rec=rec)
             if not last:
                 if i < n_deep:                                                 # block i + 1 reads its own prompt rows: replaced before its ln_1
                     ops.vpt_replace_(x, deep[i], B, L - deep.shape[1])
@@ -457,34 +432,18 @@ class TowerTailFn(torch.autograd.Function):
         return (dx, None, ddeep, None) + tuple(out)
 
 
-def tower_plan(tower_name, blocks, prefix_params, head_params):
-    """Index of the first block that owns a trainable parameter (len(blocks) when only the heads train), or None when nothing of the tower trains.
-    Raises for a trainable parameter in the frozen prefix (`prefix_params`: (name, parameter) pairs of the stem / embeddings)."""
-    first = None
-    for i, blk in enumerate(blocks):
-        if any(p.requires_grad for p in blk.parameters()):
-            first = i
-            break
-    heads = any(p.requires_grad for _, p in head_params)
-    for name, p in prefix_params:
-        if p.requires_grad:
-            raise PclipError(f"{tower_name}: parameter {name} requires grad but lies in the frozen prefix of the tower (only a tail of residual "
-                             "blocks, the final LayerNorm and the projection are differentiable)")
-    if first is None:
-        return len(blocks) if heads else None
-    return first
-
-
-def run_tower_tail(x, h0, blocks, first, B, L, heads, causal, select, sel_rows, first_token, ln, proj, cache, what, deep=None):
-    """The taped tail: blocks[first:] + ln + proj on the residual stream x [B*L, W] (h0: ln_1 of blocks[first] when the caller already has it).
+def run_tower_tail(tw, x, h0, first, B, L, pick, what, deep=None):
+    """The taped tail of tower `tw` (a tower.Tower): blocks[first:] + final LayerNorm + projection on the residual stream x [B*L, W] (h0: ln_1 of
+    blocks[first] when the caller already has it).  pick = (select, rows) from `tw.pick`, or (None, None) when x already holds the picked rows.
     deep: TowerTailFn's pack of deep visual prompts, fp32 [n_deep, P, W] with n_deep < len(blocks) - first and P < L."""
+    blocks, (select, rows) = tw.blocks, pick
     if ops.splitk_active(B) or ops.splitk_active(B * L):
         raise PclipError(f"{what}: a differentiable pass inside ops.low_latency() is not supported (the split-K linears have no backward); "
                          f"leave the context or freeze the tower (B={B}, L={L})")
     if L > TOWER_MAX_L and first < len(blocks):
         raise PclipError(f"{what}: sequences of L={L} tokens exceed the attention backward's envelope (L <= {TOWER_MAX_L}); "
                          "this tower can only run frozen")
-    params = [p for blk in blocks[first:] for p in _block_params(blk)] + [ln.weight, ln.bias, proj]
+    params = [p for blk in blocks[first:] for p in _block_params(blk)] + [tw.ln.weight, tw.ln.bias, tw.proj]
     for p in params:
         if p.requires_grad and p.dtype not in (torch.float16, torch.float32):
             raise PclipError(f"{what}: unsupported parameter dtype {p.dtype}")
@@ -493,7 +452,7 @@ def run_tower_tail(x, h0, blocks, first, B, L, heads, causal, select, sel_rows, 
             raise PclipError(f"{what}: deep prompts {deep.dtype} {tuple(deep.shape)} are not float32 [n_deep, P, {x.shape[1]}] with 1 <= P < L={L}")
         if not 1 <= deep.shape[0] < len(blocks) - first:
             raise PclipError(f"{what}: {deep.shape[0]} deep prompt layers, but only blocks {first + 1}..{len(blocks) - 1} can take one")
-    meta = (B, L, heads, causal, select, sel_rows, first_token, cache)
+    meta = (B, L, tw.heads, tw.causal, select, None if select is None else rows(), tw.first_token, tw.cache)
     return TowerTailFn.apply(x, h0, deep, meta, *params)
 
 
@@ -519,15 +478,10 @@ class VitStemFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, img, wconv, cls, pos, lnw, lnb, P, cache):
-        from .clip.model import _pad_patch_weight
         B, W = img.shape[0], wconv.shape[0]
         G2 = (img.shape[2] // P) ** 2
         kp = 3 * P * P
-        w16 = cache.get("conv1", wconv, _pad_patch_weight)
-        cls16 = cache.get("cls", cls, lambda t: t.half())
-        pos16 = cache.get("pos", pos, lambda t: t.half().contiguous())
-        patch = ops.gemm(ops.im2col_patches(img, P), w16 if w16.dtype == torch.float16 else w16.half())
-        tokens = ops.vit_assemble_tokens(patch, cls16, pos16, B, G2, W)
+        tokens = vit_stem(cache, img, wconv, cls, pos, P)
         ctx.shape = (B, G2 + 1, W, P, kp)
         ctx.save_for_backward(img, tokens, wconv, cls, pos, lnw, lnb)
         return ops.layernorm(tokens, _f32(lnw), _f32(lnb))
@@ -566,19 +520,6 @@ class TextEmbedFn(torch.autograd.Function):
         tokens, emb, pos = ctx.saved_tensors
         dE, dpos = ops.text_embed_backward(_stem_dx(dx), tokens, emb.shape[0], want_emb=ctx.needs_input_grad[1], want_pos=ctx.needs_input_grad[2])
         return None, _like(dE, emb), _like(dpos, pos), None
-
-
-def stem_plan(tower_name, blocks, prefix_params, head_params, opted_in):
-    """(first, stem) for a tower whose prefix parameters may have been opted in through CLIP.unfreeze(stem=...): stem is True when an opted-in prefix
-    parameter requires grad — the whole tower is then taped, first = 0.  Without the opt-in this is `tower_plan`, refusals included."""
-    if not opted_in:
-        return tower_plan(tower_name, blocks, prefix_params, head_params), False
-    if any(p.requires_grad for _, p in prefix_params):
-        for name, p in prefix_params:
-            if p.requires_grad and p.dtype not in (torch.float16, torch.float32):
-                raise PclipError(f"{tower_name}: unsupported dtype {p.dtype} of parameter {name}")
-        return 0, True
-    return tower_plan(tower_name, blocks, [], head_params), False
 
 
 # ---- learned prompt context (CoOp): the embedded prompts as a function of the fp32 context rows ---------------------------------------------------

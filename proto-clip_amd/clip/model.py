@@ -21,6 +21,7 @@ from torch import nn
 
 from .. import ops
 from .._lib import PclipError
+from ..tower import Tower, _run_blocks, class_row_pick, eot_row_pick, run_tower, vit_stem  # noqa: F401  (_run_blocks: tools/tower_backward_bench.py imports it here)
 
 
 class _Box(nn.Module):
@@ -68,75 +69,6 @@ def _transformer(width, layers):
 # were removed in round 6: profiles/r03_e2e_fold_study.json, r04_ab_res_ln.txt, r06_bench_v0.json.)
 
 
-def _run_blocks(x, blocks, B, L, heads, causal, select=None, first_token=False, h0=None):
-    """ResidualAttentionBlock.forward (clip/model.py:187-190) per layer on x [B*L, W] fp16 (updated IN PLACE).
-    Both residual adds ride in the epilogue of the GEMM that produces the addend (pclip_gemm_f16 with `residual`: the residual
-    rows are read in the coalesced store pass, r16(x + r16(acc + bias)) — the reference's two roundings); each LayerNorm is a
-    read-x / write-h pass (the reference's rounding point h = r16(LN(x))) followed by the ordinary linear:
-        h = ln_1(x)   qkv = in_proj(h)   a = attention(qkv)   x += out_proj(a)
-        h = ln_2(x)   f = QuickGELU(c_fc(h))                  x += c_proj(f)
-    In low-latency mode (ops.low_latency: split-K linears of a serving request) the addend is produced by the split-K kernel
-    and the add stays in the LayerNorm pass (pclip_add_layernorm_f16).
-    Returns (x, d): the stack's output is x (+ d when d is not None — low-latency mode leaves the last add to the caller's
-    final LayerNorm), [B, W] rows picked by `select` when given.
-
-    `select(t)` picks, from a [B*L, W] tensor, the B rows the caller reads after the stack (the class token of the vision
-    tower, clip/model.py:233; the EOT token of the text tower, :350).  The reference pushes every token through the last
-    block and then discards all but that row; here the last block's out_proj, LN2 and MLP run on those B rows only — the
-    same arithmetic for the rows that matter (a GEMM row does not depend on the other rows), 9/12 of one layer's linear
-    FLOPs saved (6 % of a 12-layer tower).  `first_token` (vision tower: the
-    selected row is token 0 of every sequence) additionally projects the last block's QUERIES for those B rows only and runs
-    its attention for that one query per image (keys / values still come from every token).
-    `h0`: the first block's ln_1 output when the caller's stem produced it."""
-    n = len(blocks)
-    d = None
-
-    def norm_of(x_, ln):
-        return None if ln is None else ops.layernorm(x_, ln.weight, ln.bias)
-
-    def linear(h, w, bias, act=0, rows=None):
-        """act(h w^T + bias); `rows` = a row range of (w, bias) (the q / kv thirds of in_proj)."""
-        sl = slice(None) if rows is None else rows
-        return ops.gemm(h, w[sl], bias[sl], act=act)
-
-    def add_linear(x_, a_, lin, ln):
-        """x_ += lin(a_) ; returns (x_, ln(x_))."""
-        if ops.splitk_active(a_.shape[0]):
-            dd = ops.gemm(a_, lin.weight, lin.bias)
-            return x_, ops.add_layernorm(x_, dd, ln.weight, ln.bias)
-        ops.gemm(a_, lin.weight, lin.bias, residual=x_, out=x_)
-        return x_, norm_of(x_, ln)
-
-    h = None
-    if n > 0:
-        h = h0 if h0 is not None else norm_of(x, blocks[0].ln_1)
-    for i, blk in enumerate(blocks):
-        last = i == n - 1
-        w, bias = blk.attn.in_proj_weight, blk.attn.in_proj_bias
-        if select is not None and last and first_token and not causal:
-            W = x.shape[1]
-            kv = linear(h, w, bias, rows=slice(W, 3 * W))                           # keys | values of every token
-            q = linear(select(h), w, bias, rows=slice(0, W))                        # queries of the class tokens
-            a, x = ops.attention_first_queries(q, kv, B, L, 1, heads), select(x)
-        else:
-            qkv = linear(h, w, bias)
-            a = ops.attention(qkv, B, L, heads, causal=causal)
-            if select is not None and last:
-                a, x = select(a), select(x)              # x holds the residual stream entering this block's out_proj add
-        x, h = add_linear(x, a, blk.attn.out_proj, blk.ln_2)
-        f = linear(h, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias, act=1)
-        if last:
-            if ops.splitk_active(f.shape[0]):
-                d = ops.gemm(f, blk.mlp.c_proj.weight, blk.mlp.c_proj.bias)      # the caller's final LayerNorm adds it
-            else:
-                ops.gemm(f, blk.mlp.c_proj.weight, blk.mlp.c_proj.bias, residual=x, out=x)
-        else:
-            x, h = add_linear(x, f, blk.mlp.c_proj, blocks[i + 1].ln_1)
-    if select is not None and n == 0:
-        x = select(x)
-    return x, d
-
-
 class _Cached:
     """Derived (cast / transposed / padded) copies of parameters, refreshed when the source changes."""
 
@@ -150,16 +82,6 @@ class _Cached:
             hit = (tag, fn(src.detach()))
             self._c[key] = hit
         return hit[1]
-
-
-def _pad_patch_weight(w):
-    """conv1.weight [W, 3, P, P] -> GEMM rows [W, kpad]: zero columns up to the K-tile, as ops.im2col_patches pads its matrix."""
-    kp = w.shape[1] * w.shape[2] * w.shape[3]
-    kpad = (kp + 63) // 64 * 64
-    w2 = w.reshape(w.shape[0], kp)
-    if kpad != kp:
-        w2 = torch.cat([w2, w2.new_zeros(w.shape[0], kpad - kp)], dim=1)
-    return w2.contiguous()
 
 
 class VisionTransformer(nn.Module):
@@ -179,7 +101,12 @@ class VisionTransformer(nn.Module):
         self.ln_post = _ln(width)
         self.proj = nn.Parameter(torch.empty(width, output_dim), requires_grad=False)
         self._cache = _Cached()
-        self._stem_opt_in = False                                           # CLIP.unfreeze(stem=...): conv1 / embeddings / ln_pre may train
+        prefix = [("visual.conv1.weight", self.conv1.weight), ("visual.class_embedding", self.class_embedding),           # VitStemFn's argument order
+                  ("visual.positional_embedding", self.positional_embedding), ("visual.ln_pre.weight", self.ln_pre.weight),
+                  ("visual.ln_pre.bias", self.ln_pre.bias)]
+        head = [("visual.ln_post.weight", self.ln_post.weight), ("visual.ln_post.bias", self.ln_post.bias), ("visual.proj", self.proj)]
+        self.tower = Tower("encode_image", "visual tower", "stem", blocks=self.transformer.resblocks, heads=heads, causal=False, ln=self.ln_post,
+                           proj=self.proj, cache=self._cache, projT_key="projT", prefix=prefix, head=head, pick=class_row_pick)
         # images per pass: bounds activation memory (c_fc output = chunk*L*4W*2 B = 1.2 GB for ViT-B/16 at 1024);
         # larger passes waste less of the GEMMs' last round of persistent tiles (measured on MI355X: 1024 > 512 > 256)
         self.chunk = int(os.environ.get("PCLIP_VIT_CHUNK", "1024"))
@@ -190,75 +117,43 @@ class VisionTransformer(nn.Module):
         outs = [self._forward_chunk(x[i:i + self.chunk]) for i in range(0, x.shape[0], self.chunk)]
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
 
-    def _prefix_params(self):
-        """(name, parameter) of everything in front of block 0, in VitStemFn's argument order."""
-        return [("visual.conv1.weight", self.conv1.weight), ("visual.class_embedding", self.class_embedding),
-                ("visual.positional_embedding", self.positional_embedding), ("visual.ln_pre.weight", self.ln_pre.weight),
-                ("visual.ln_pre.bias", self.ln_pre.bias)]
+    @property
+    def _stem_opt_in(self):
+        """CLIP.unfreeze(stem=...) has opted the prefix in: conv1 / embeddings / ln_pre may train."""
+        return self.tower.stem_opt_in
 
-    def _head_params(self):
-        return [("visual.ln_post.weight", self.ln_post.weight), ("visual.ln_post.bias", self.ln_post.bias), ("visual.proj", self.proj)]
+    @_stem_opt_in.setter
+    def _stem_opt_in(self, value):
+        self.tower.stem_opt_in = bool(value)
 
     def _tape_from(self):
         """Index of the first residual block with a trainable parameter (layers: only ln_post / proj train), None when the tower is frozen.
         Refuses a trainable prefix parameter, opted in or not: the taped passes plan with `_tape_plan`."""
-        from ..autograd import tower_plan
-        return tower_plan("visual tower", self.transformer.resblocks, self._prefix_params(), self._head_params())
+        return self.tower.tape_from()
 
     def _tape_plan(self):
         """(first, stem): `_tape_from`, except that prefix parameters opted in through CLIP.unfreeze(stem=...) put the whole tower on the tape."""
-        from ..autograd import stem_plan
-        return stem_plan("visual tower", self.transformer.resblocks, self._prefix_params(), self._head_params(), self._stem_opt_in)
+        return self.tower.tape_plan()
 
     def _forward_chunk(self, img):
-        B, P, W = img.shape[0], self.patch_size, self.width
+        P, tw = self.patch_size, self.tower
         G = self.input_resolution // P
-        L = G * G + 1
         if img.dtype not in (torch.float32, torch.float16):   # fp32: image.type(self.dtype) (clip/model.py:339) rides on the im2col gather
             raise PclipError(f"unsupported image dtype {img.dtype}")
         img = img.contiguous()
-        first, stem = self._tape_plan() if torch.is_grad_enabled() else (None, False)
-        if stem:                                                            # whole-tower fine-tuning: the stem and every block on the tape
-            from ..autograd import VitStemFn, run_tower_tail
-            blocks = self.transformer.resblocks
-            x = VitStemFn.apply(img, self.conv1.weight, self.class_embedding, self.positional_embedding, self.ln_pre.weight, self.ln_pre.bias,
-                                P, self._cache)
-            rows = torch.arange(B, device=x.device) * L
-            what = f"encode_image (visual tower, stem + blocks 0..{len(blocks) - 1} + heads on the tape)"
-            return run_tower_tail(x, None, blocks, 0, B, L, self.heads, False, lambda t: t.view(B, L, W)[:, 0, :].contiguous(), rows, True,
-                                  self.ln_post, self.proj, self._cache, what)
-        wconv = self._cache.get("conv1", self.conv1.weight, _pad_patch_weight)
-        cls16 = self._cache.get("cls", self.class_embedding, lambda t: t.half())
-        pos16 = self._cache.get("pos", self.positional_embedding, lambda t: t.half().contiguous())
-        projT = self._cache.get("projT", self.proj, lambda t: t.t().contiguous())
-        cols = ops.im2col_patches(img, P)                                   # conv1 as GEMM (clip/model.py:222)
-        patch = ops.gemm(cols, wconv)
-        blocks = self.transformer.resblocks
+        plan = tw.tape_plan() if torch.is_grad_enabled() else (None, False)
+        stem_in = (img, self.conv1.weight, self.class_embedding, self.positional_embedding)
         h0 = None
-        if len(blocks) > 0:                                                 # tokens + ln_pre + the first block's ln_1 in one pass
-            x, h0 = ops.vit_embed_ln(patch, cls16, pos16, B, G * G, W, self.ln_pre.weight, self.ln_pre.bias, blocks[0].ln_1.weight,
-                                     blocks[0].ln_1.bias)                   # clip/model.py:225-227, 188
+        if plan[1]:                                                         # whole-tower fine-tuning: the stem and every block on the tape
+            from ..autograd import VitStemFn
+            x = VitStemFn.apply(*stem_in, self.ln_pre.weight, self.ln_pre.bias, P, self._cache)
+        elif len(tw.blocks) > 0:                                            # tokens + ln_pre + the first block's ln_1 in one pass
+            ln_1 = tw.blocks[0].ln_1
+            x, h0 = vit_stem(self._cache, *stem_in, P, fused=(self.ln_pre.weight, self.ln_pre.bias, ln_1.weight, ln_1.bias))
         else:
-            x = ops.vit_assemble_tokens(patch, cls16, pos16, B, G * G, W)   # clip/model.py:225-226
-            x = ops.layernorm(x, self.ln_pre.weight, self.ln_pre.bias)      # 227
-        pick_cls = lambda t: t.view(B, L, W)[:, 0, :].contiguous()          # x[:, 0, :], 233 (taken before the last block's tail)
-        if first is not None:                                               # fine-tuning: blocks[first:] + ln_post + proj on the tape
-            from ..autograd import run_tower_tail
-            what = f"encode_image (visual tower, blocks {first}..{len(blocks) - 1} + heads trainable)"
-            if first == len(blocks):                                        # only the heads train: the stack keeps its class-row shortcut
-                x, _ = _run_blocks(x, blocks, B, L, self.heads, causal=False, select=pick_cls, first_token=True, h0=h0)
-                return run_tower_tail(x, None, blocks, first, B, L, self.heads, False, None, None, False, self.ln_post, self.proj, self._cache, what)
-            if first > 0:
-                x, _ = _run_blocks(x, blocks[:first], B, L, self.heads, causal=False, h0=h0)
-                h0 = None
-            rows = torch.arange(B, device=x.device) * L
-            return run_tower_tail(x, h0, blocks, first, B, L, self.heads, False, pick_cls, rows, True, self.ln_post, self.proj, self._cache, what)
-        x, d = _run_blocks(x, blocks, B, L, self.heads, causal=False, select=pick_cls, first_token=True, h0=h0)   # 229-231
-        if d is None:                                                       # ln_post(x[:, 0, :]), 233
-            cls = ops.layernorm(x, self.ln_post.weight, self.ln_post.bias)
-        else:
-            cls = ops.add_layernorm(x, d, self.ln_post.weight, self.ln_post.bias, update_x=False)
-        return ops.gemm(cls, projT)                                         # x @ proj, 235-236
+            x = ops.layernorm(vit_stem(self._cache, *stem_in, P), self.ln_pre.weight, self.ln_pre.bias)      # clip/model.py:227
+        B, L = img.shape[0], G * G + 1
+        return run_tower(tw, x, B, L, plan, tw.pick(B, L, x.device), h0=h0)                  # 229-236
 
 
 def _bn(ch):
@@ -446,7 +341,11 @@ class CLIP(nn.Module):
         self.text_projection = nn.Parameter(torch.empty(transformer_width, embed_dim), requires_grad=False)
         self.logit_scale = nn.Parameter(torch.ones([]) * np.log(1 / 0.07), requires_grad=False)
         self._cache = _Cached()
-        self._text_stem_opt_in = False                                      # unfreeze(stem=...): token_embedding / positional_embedding may train
+        prefix = [("token_embedding.weight", self.token_embedding.weight), ("positional_embedding", self.positional_embedding)]
+        head = [("ln_final.weight", self.ln_final.weight), ("ln_final.bias", self.ln_final.bias), ("text_projection", self.text_projection)]
+        self.text_tower = Tower("encode_text", "text tower", "embeddings", blocks=self.transformer.resblocks, heads=transformer_heads, causal=True,
+                                ln=self.ln_final, proj=self.text_projection, cache=self._cache, projT_key="tprojT", prefix=prefix, head=head,
+                                pick=eot_row_pick)
         self.text_chunk = 1024
 
     @property
@@ -469,26 +368,27 @@ class CLIP(nn.Module):
     def encode_text(self, text):
         """text [n, context_length] int64 -> [n, embed_dim] fp16 (clip/model.py:341-354).  Unlike the
         reference's per-class calls (utils.py:264-266, n = #templates) any n is efficient here."""
-        first, stem = self._text_tape_plan() if torch.is_grad_enabled() else (None, False)
-        with torch.set_grad_enabled(first is not None):
-            outs = [self._encode_text_chunk(text[i:i + self.text_chunk], first, stem) for i in range(0, text.shape[0], self.text_chunk)]
+        plan = self.text_tower.tape_plan() if torch.is_grad_enabled() else (None, False)
+        with torch.set_grad_enabled(plan[0] is not None):
+            outs = [self._encode_text_chunk(text[i:i + self.text_chunk], plan) for i in range(0, text.shape[0], self.text_chunk)]
             return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
 
-    def _text_prefix_params(self):
-        return [("token_embedding.weight", self.token_embedding.weight), ("positional_embedding", self.positional_embedding)]
+    @property
+    def _text_stem_opt_in(self):
+        """unfreeze(stem=...) has opted the text prefix in: token_embedding / positional_embedding may train."""
+        return self.text_tower.stem_opt_in
 
-    def _text_head_params(self):
-        return [("ln_final.weight", self.ln_final.weight), ("ln_final.bias", self.ln_final.bias), ("text_projection", self.text_projection)]
+    @_text_stem_opt_in.setter
+    def _text_stem_opt_in(self, value):
+        self.text_tower.stem_opt_in = bool(value)
 
     def _text_tape_from(self):
         """As VisionTransformer._tape_from for the text tower (ln_final / text_projection are its heads)."""
-        from ..autograd import tower_plan
-        return tower_plan("text tower", self.transformer.resblocks, self._text_prefix_params(), self._text_head_params())
+        return self.text_tower.tape_from()
 
     def _text_tape_plan(self):
         """As VisionTransformer._tape_plan for the text tower."""
-        from ..autograd import stem_plan
-        return stem_plan("text tower", self.transformer.resblocks, self._text_prefix_params(), self._text_head_params(), self._text_stem_opt_in)
+        return self.text_tower.tape_plan()
 
     def unfreeze(self, visual_blocks=0, text_blocks=0, heads=True, stem=False):
         """Make a tail of the transformer towers trainable: the last `visual_blocks` / `text_blocks` residual blocks and, with `heads`, ln_post / proj
@@ -511,17 +411,17 @@ class CLIP(nn.Module):
             nv = len(self.visual.transformer.resblocks)
             if not 0 <= visual_blocks <= nv:
                 raise PclipError(f"unfreeze: visual_blocks={visual_blocks} outside 0..{nv}")
-            vis = [p for _, p in self.visual._prefix_params()] if stem_visual else []
+            vis = [p for _, p in self.visual.tower.prefix] if stem_visual else []
             vis += [p for blk in list(self.visual.transformer.resblocks)[nv - visual_blocks:] for p in blk.parameters()]
             if heads:
-                vis += [self.visual.ln_post.weight, self.visual.ln_post.bias, self.visual.proj]
+                vis += [p for _, p in self.visual.tower.head]
         nt = len(self.transformer.resblocks)
         if not 0 <= text_blocks <= nt:
             raise PclipError(f"unfreeze: text_blocks={text_blocks} outside 0..{nt}")
-        txt = [p for _, p in self._text_prefix_params()] if stem_text else []
+        txt = [p for _, p in self.text_tower.prefix] if stem_text else []
         txt += [p for blk in list(self.transformer.resblocks)[nt - text_blocks:] for p in blk.parameters()]
         if heads:
-            txt += [self.ln_final.weight, self.ln_final.bias, self.text_projection]
+            txt += [p for _, p in self.text_tower.head]
         if stem_visual:
             self.visual._stem_opt_in = True
         if stem_text:
@@ -531,47 +431,17 @@ class CLIP(nn.Module):
             p.requires_grad_(True)
         return params
 
-    def _encode_text_chunk(self, text, first=None, stem=False):
+    def _encode_text_chunk(self, text, plan=(None, False)):
         B, L = text.shape
-        W = self.transformer.width
-        if stem:                                                                 # whole-tower fine-tuning: the embedding and every block on the tape
-            from ..autograd import TextEmbedFn, run_tower_tail
-            blocks = self.transformer.resblocks
+        tw = self.text_tower
+        if plan[1]:                                                              # whole-tower fine-tuning: the embedding and every block on the tape
+            from ..autograd import TextEmbedFn
             x = TextEmbedFn.apply(text, self.token_embedding.weight, self.positional_embedding, self._cache)
-            pos = torch.arange(L, device=x.device).expand(B, L)                  # the FIRST maximum, gather_eot's tie rule
-            eot = torch.where(text == text.max(dim=-1, keepdim=True).values, pos, pos.new_full((), L)).min(dim=-1).values
-            rows = torch.arange(B, device=x.device) * L + eot
-            what = f"encode_text (text tower, embeddings + blocks 0..{len(blocks) - 1} + heads on the tape)"
-            return run_tower_tail(x, None, blocks, 0, B, L, self.transformer_heads, True, lambda t: ops.gather_eot(t, text, B, L, W), rows, False,
-                                  self.ln_final, self.text_projection, self._cache, what)
-        emb16 = self._cache.get("tok", self.token_embedding.weight, lambda t: t.half().contiguous())
-        pos16 = self._cache.get("pos", self.positional_embedding, lambda t: t.half().contiguous())
-        projT = self._cache.get("tprojT", self.text_projection, lambda t: t.t().contiguous())
-        x = ops.text_embed(text, emb16, pos16)                                   # 342-344
-        pick_eot = lambda t: ops.gather_eot(t, text, B, L, W)                    # x[arange, text.argmax(-1)], 350
-        if first is not None:                                                    # fine-tuning: blocks[first:] + ln_final + text_projection on the tape
-            from ..autograd import run_tower_tail
-            blocks = self.transformer.resblocks
-            what = f"encode_text (text tower, blocks {first}..{len(blocks) - 1} + heads trainable)"
-            with torch.no_grad():
-                if first == len(blocks):
-                    x, _ = _run_blocks(x, blocks, B, L, self.transformer_heads, causal=True, select=pick_eot)
-                elif first > 0:
-                    x, _ = _run_blocks(x, blocks[:first], B, L, self.transformer_heads, causal=True)
-            if first == len(blocks):
-                return run_tower_tail(x, None, blocks, first, B, L, self.transformer_heads, True, None, None, False, self.ln_final,
-                                      self.text_projection, self._cache, what)
-            pos = torch.arange(L, device=x.device).expand(B, L)                  # the FIRST maximum, gather_eot's tie rule
-            eot = torch.where(text == text.max(dim=-1, keepdim=True).values, pos, pos.new_full((), L)).min(dim=-1).values
-            rows = torch.arange(B, device=x.device) * L + eot
-            return run_tower_tail(x, None, blocks, first, B, L, self.transformer_heads, True, pick_eot, rows, False, self.ln_final,
-                                  self.text_projection, self._cache, what)
-        x, d = _run_blocks(x, self.transformer.resblocks, B, L, self.transformer_heads, causal=True, select=pick_eot)   # 345-347
-        if d is None:
-            eot = ops.layernorm(x, self.ln_final.weight, self.ln_final.bias)     # 348 (row-wise: commutes with the gather)
         else:
-            eot = ops.add_layernorm(x, d, self.ln_final.weight, self.ln_final.bias, update_x=False)
-        return ops.gemm(eot, projT)                                              # @ text_projection, 352
+            emb16 = self._cache.get("tok", self.token_embedding.weight, lambda t: t.half().contiguous())
+            pos16 = self._cache.get("pos", self.positional_embedding, lambda t: t.half().contiguous())
+            x = ops.text_embed(text, emb16, pos16)                               # 342-344
+        return run_tower(tw, x, B, L, plan, tw.pick(B, L, x.device, text))       # 345-352
 
     def forward(self, image, text):
         """(logits_per_image [n_img, n_txt], logits_per_text = its transpose view), fp16 (clip/model.py:356-370): both feature matrices L2-normalised in fp16,

@@ -19,6 +19,7 @@ from . import autograd as pag
 from . import ops
 from . import utils
 from ._lib import PclipError
+from .tower import eot_positions, run_tower
 
 PLACEHOLDER = "X"        # one BPE token; its embedding is never read (the context rows take its positions)
 
@@ -27,13 +28,6 @@ def placeholder_prompts(classnames, n_ctx: int):
     """Upstream's prompt texts: n_ctx placeholder words, the class name (underscores as spaces) and a full stop."""
     prefix = " ".join([PLACEHOLDER] * n_ctx)
     return [prefix + " " + name.replace("_", " ") + "." for name in classnames]
-
-
-def eot_positions(tokens: torch.Tensor) -> torch.Tensor:
-    """Position of the FIRST maximum of every token row (int64 [N]): the row `ops.gather_eot` picks — the EOT token has the highest id."""
-    L = tokens.shape[1]
-    pos = torch.arange(L, device=tokens.device).expand(tokens.shape[0], L)
-    return torch.where(tokens == tokens.max(dim=-1, keepdim=True).values, pos, pos.new_full((), L)).min(dim=-1).values
 
 
 def effective_length(tokens: torch.Tensor) -> int:
@@ -119,9 +113,9 @@ class PromptLearner(torch.nn.Module):
             raise PclipError(f"PromptLearner: ctx must be torch.float32, got {self.ctx.dtype}")
         taped = False
         if torch.is_grad_enabled():
-            m._text_tape_from()                                            # refuses a trainable embedding in the frozen prefix
-            taped = self.ctx.requires_grad or any(p.requires_grad for p in self._tower_params())
-        L, W = self.run_length, m.transformer.width
+            tail = m._text_tape_from()                                     # refuses a trainable embedding in the frozen prefix
+            taped = self.ctx.requires_grad or tail is not None             # the context, or something of the tower's blocks / heads, trains
+        L = self.run_length
         emb16 = m._cache.get("tok", m.token_embedding.weight, lambda t: t.half().contiguous())
         pos16 = m._cache.get("pos", m.positional_embedding, lambda t: t.half().contiguous())
         with torch.set_grad_enabled(taped):
@@ -129,34 +123,19 @@ class PromptLearner(torch.nn.Module):
             for i in range(0, self.n_cls, m.text_chunk):
                 tokens = self.tokenized_prompts[i:i + m.text_chunk]
                 ctx = self.ctx[i:i + m.text_chunk] if self.class_specific else self.ctx
-                outs.append(self._chunk(ctx, tokens, emb16, pos16, L, W, taped))
+                outs.append(self._chunk(ctx, tokens, emb16, pos16, L, taped))
             return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
 
-    def _tower_params(self):
-        m = self.clip_model
-        yield from m.transformer.parameters()
-        yield from (m.ln_final.weight, m.ln_final.bias, m.text_projection)
-
-    def _chunk(self, ctx, tokens, emb16, pos16, L, W, taped):
-        from .clip.model import _run_blocks
-        m = self.clip_model
+    def _chunk(self, ctx, tokens, emb16, pos16, L, taped):
+        tw = self.clip_model.text_tower
         B = tokens.shape[0]
-        blocks = m.transformer.resblocks
         head = tokens[:, :L].contiguous()                                    # the EOT lies inside: the first maximum of the cut row is the full row's
-        pick_eot = lambda t: ops.gather_eot(t, head, B, L, W)
         if taped:
             x = pag.PromptEmbedFn.apply(ctx, tokens, emb16, pos16, self.n_ctx, L)
-            rows = torch.arange(B, device=x.device) * L + eot_positions(head)
             what = f"PromptLearner (n_ctx={self.n_ctx}, {L} tokens per prompt, text tower taped from block 0)"
-            return pag.run_tower_tail(x, None, blocks, 0, B, L, m.transformer_heads, True, pick_eot, rows, False, m.ln_final, m.text_projection,
-                                      m._cache, what)
+            return run_tower(tw, x, B, L, (0, False), tw.pick(B, L, x.device, head), what=what)
         x = ops.prompt_embed(ctx.detach(), tokens, emb16, pos16, L)
-        x, d = _run_blocks(x, blocks, B, L, m.transformer_heads, causal=True, select=pick_eot)
-        if d is None:
-            eot = ops.layernorm(x, m.ln_final.weight, m.ln_final.bias)
-        else:
-            eot = ops.add_layernorm(x, d, m.ln_final.weight, m.ln_final.bias, update_x=False)
-        return ops.gemm(eot, m._cache.get("tprojT", m.text_projection, lambda t: t.t().contiguous()))
+        return run_tower(tw, x, B, L, (None, False), tw.pick(B, L, x.device, head))
 
 
 class CoOp(torch.nn.Module):

@@ -24,6 +24,7 @@ from . import autograd as pag
 from . import ops
 from . import utils
 from ._lib import PclipError, VPT_MAX_L
+from .tower import run_tower, vit_stem
 
 
 class VisualPromptLearner(torch.nn.Module):
@@ -62,11 +63,6 @@ class VisualPromptLearner(torch.nn.Module):
         """Tokens per image the tower runs at: L0 + n_ctx."""
         return self.l0 + self.n_ctx
 
-    def _tower_params(self):
-        vis = self.clip_model.visual
-        yield from vis.transformer.parameters()
-        yield from (vis.ln_post.weight, vis.ln_post.bias, vis.proj)
-
     def forward(self, images, ctx=None):
         vis = self.clip_model.visual
         ctx = self.ctx if ctx is None else ctx
@@ -84,35 +80,26 @@ class VisualPromptLearner(torch.nn.Module):
                              "stem is not supported (the prompt rows are spliced behind a frozen stem)")
         taped = False
         if torch.is_grad_enabled():
-            vis._tape_from()                                                   # refuses a trainable parameter in the frozen prefix
-            taped = ctx.requires_grad or any(p.requires_grad for p in self._tower_params())
+            tail = vis._tape_from()                                            # refuses a trainable parameter in the frozen prefix
+            taped = ctx.requires_grad or tail is not None                      # the prompts, or something of the tower's blocks / heads, train
         with torch.set_grad_enabled(taped):
             outs = [self._chunk(ctx, images[i:i + vis.chunk]) for i in range(0, images.shape[0], vis.chunk)]
             return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
 
     def _chunk(self, ctx, img):
-        from .clip.model import _pad_patch_weight
         vis = self.clip_model.visual
-        B, Pz, W = img.shape[0], vis.patch_size, vis.width
-        G2, L0, L = (vis.input_resolution // Pz) ** 2, self.l0, self.run_length
+        B, L0, L = img.shape[0], self.l0, self.run_length
         if img.dtype not in (torch.float32, torch.float16):
             raise PclipError(f"unsupported image dtype {img.dtype}")
         what = f"VisualPromptLearner (n_ctx={self.n_ctx}, depth={self.depth}, {L} tokens per image, visual tower on the tape from block 0)"
         if ops.splitk_active(B) or ops.splitk_active(B * L):
             raise PclipError(f"{what}: a pass inside ops.low_latency() is not supported (the split-K linears have no backward and the prompted tower "
                              f"runs the taped kernel sequence); leave the context (B={B}, L={L})")
-        wconv = vis._cache.get("conv1", vis.conv1.weight, _pad_patch_weight)
-        cls16 = vis._cache.get("cls", vis.class_embedding, lambda t: t.half())
-        pos16 = vis._cache.get("pos", vis.positional_embedding, lambda t: t.half().contiguous())
-        with torch.no_grad():                                                  # the frozen stem: a constant
-            patch = ops.gemm(ops.im2col_patches(img.contiguous(), Pz), wconv if wconv.dtype == torch.float16 else wconv.half())
-            t = ops.vit_assemble_tokens(patch, cls16, pos16, B, G2, W)         # clip/model.py:225-226
+        with torch.no_grad():                                                  # the frozen stem: a constant (clip/model.py:222-226)
+            t = vit_stem(vis._cache, img.contiguous(), vis.conv1.weight, vis.class_embedding, vis.positional_embedding, vis.patch_size)
         x = pag.VptEmbedFn.apply(ctx[0], t, vis.ln_pre.weight, vis.ln_pre.bias, B, L0)
         deep = ctx[1:] if self.depth > 1 else None
-        blocks = vis.transformer.resblocks
-        rows = torch.arange(B, device=x.device) * L
-        pick_cls = lambda v: v.view(B, L, W)[:, 0, :].contiguous()
-        return pag.run_tower_tail(x, None, blocks, 0, B, L, vis.heads, False, pick_cls, rows, True, vis.ln_post, vis.proj, vis._cache, what, deep=deep)
+        return run_tower(vis.tower, x, B, L, (0, False), vis.tower.pick(B, L, x.device), what=what, deep=deep)
 
 
 class VPT(torch.nn.Module):
