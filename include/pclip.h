@@ -690,6 +690,35 @@ int pclip_vpt_replace_f16(void* x, const float* ctx, int B, int L0, int P, int W
  * written. */
 int pclip_vpt_grad_f32(void* g, int B, int L0, int P, int W, int clear, float* dctx, float* part, int nslice, pclip_stream_t stream);
 
+/* ---- MaPLe: prompt rows at an offset and the text -> vision coupling function (csrc/pclip_maple.hip lists the rounding points and every order) ---- */
+
+/* The two VPT passes above with the P rows at off .. off + P - 1 of sequences of L rows: L, off and P independent, 0 <= off, off + P <= L,
+ * L <= PCLIP_VPT_MAX_L, W % 8 == 0, B >= 0, B * L * W within an int, operands 16-byte aligned, no atomics.  At off = L - P they give the bits of
+ * pclip_vpt_replace_f16 / pclip_vpt_grad_f32. */
+
+/* In place on the stream x [B * L, W] fp16: rows off .. off + P - 1 of every sequence become r16(ctx), ctx fp32 [P, W]; the other rows are not touched. */
+int pclip_rows_replace_f16(void* x, const float* ctx, int B, int L, int off, int P, int W, pclip_stream_t stream);
+
+/* dctx [P, W] fp32 = sum over the B sequences of f32(g[b, off + j, :]) in pclip_vpt_grad_f32's order (slices of PCLIP_VPT_SLICE consecutive sequences,
+ * ascending inside a slice, then ascending slice order; every sum starts from its first term); nslice = ceil(B / PCLIP_VPT_SLICE), part
+ * [nslice][P * W] may be NULL when that is 1.  clear != 0: the lane that loaded a vector stores exact zeros over it, after its load.  Rows outside
+ * [off, off + P) are neither read nor written. */
+int pclip_rows_grad_f32(void* g, int B, int L, int off, int P, int W, int clear, float* dctx, float* part, int nslice, pclip_stream_t stream);
+
+/* The coupling function, fp32, all depths in one launch: Y[d] = X[d] Wc[d]^T + bc[d], X [depth, P, Wt], Wc [depth, Wv, Wt], bc [depth, Wv],
+ * Y [depth, P, Wv].  Envelope: depth >= 1, 1 <= P <= PCLIP_COUPLE_MAX_P, Wt % 64 == 0, Wv % 8 == 0, depth * Wv * Wt within an int, operands 16-byte
+ * aligned.  Products and additions are rounded separately (no fused multiply-add) in the one order the source file documents. */
+#define PCLIP_COUPLE_MAX_P 16
+#define PCLIP_COUPLE_SLICE 32
+int pclip_couple_fwd_f32(const float* X, const float* Wc, const float* bc, int depth, int P, int Wt, int Wv, float* Y, pclip_stream_t stream);
+
+/* Gradients of the coupling function from dY [depth, P, Wv]: dWc[d] = dY[d]^T X[d], dbc[d] = sum_p dY[d][p], dX[d] = dY[d] Wc[d]; each output is
+ * optional (NULL: not computed; X may be NULL without dWc, Wc without dX).  dX sums the rows of Wc[d] in slices of PCLIP_COUPLE_SLICE rows:
+ * nslice = ceil(Wv / PCLIP_COUPLE_SLICE), part [depth][nslice][P * Wt] fp32 (may be NULL when nslice == 1 or dX is NULL).  At most two launches
+ * and one merge launch. */
+int pclip_couple_bwd_f32(const float* dY, const float* X, const float* Wc, int depth, int P, int Wt, int Wv, float* dWc, float* dbc, float* dX,
+                         float* part, int nslice, pclip_stream_t stream);
+
 /* ---- backward of the embedding stages in front of block 0 (whole-tower fine-tuning; csrc/pclip_embed_bwd.hip lists every rounding) ---------- */
 
 /* Envelope of both entry points: B >= 1, 1 <= L <= 4096, W % 64 == 0, W <= 2048 (and V >= 1); operands 16-byte aligned.  fp32 accumulation, no atomics:

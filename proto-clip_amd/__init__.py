@@ -9,3 +9,5 @@ from . import _lib  # noqa: F401  (ctypes binding; the shared library is loaded 
 from ._lib import PclipError  # noqa: F401
 from . import tip_adapter  # noqa: F401,E402  (the Tip-Adapter / Tip-Adapter-F baselines: tip_logits, tip_classify, search_hp, TipAdapterF, run_tip_adapter[_F])
 from . import vpt  # noqa: F401,E402  (visual prompt tuning through the frozen vision tower: VisualPromptLearner, VPT, run_vpt)
+from . import maple  # noqa: F401,E402  (multi-modal prompt learning, deep text prompts coupled to VPT: MultiModalPromptLearner, MaPLe, run_maple)
+from .maple import MaPLe, MultiModalPromptLearner, run_maple  # noqa: F401,E402

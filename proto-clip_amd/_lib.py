@@ -28,6 +28,7 @@ ROUTE_RAN = {0: "cfg0", 1: "cfg1", 2: "cfg2", 3: "cfg3", 4: "cfg4", 10: "four_wa
 EMBED_BWD_CHUNK = 128                                      # PCLIP_EMBED_BWD_CHUNK: sorted rows per chunk of pclip_text_embed_backward's segmented reduction
 PROMPT_CTX_SLICE = 16                                      # PCLIP_PROMPT_CTX_SLICE: classes per slice of pclip_prompt_ctx_grad_f32's first stage
 VPT_SLICE, VPT_MAX_L = 16, 288                             # PCLIP_VPT_SLICE: images per slice of pclip_vpt_grad_f32's first stage; PCLIP_VPT_MAX_L: L0 + P at most
+COUPLE_MAX_P, COUPLE_SLICE = 16, 32                        # PCLIP_COUPLE_MAX_P: rows per depth of the coupling function; PCLIP_COUPLE_SLICE: rows of Wc per slice of dX
 
 
 class PclipError(RuntimeError):
@@ -138,6 +139,10 @@ _SIGS = {
     "pclip_vpt_append_f16": [_P, _P, c_int, c_int, c_int, c_int, _P, _P],
     "pclip_vpt_replace_f16": [_P, _P, c_int, c_int, c_int, c_int, _P],
     "pclip_vpt_grad_f32": [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P],
+    "pclip_rows_replace_f16": [_P, _P, c_int, c_int, c_int, c_int, c_int, _P],
+    "pclip_rows_grad_f32": [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P],
+    "pclip_couple_fwd_f32": [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P],
+    "pclip_couple_bwd_f32": [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P],
     "pclip_text_embed_backward": [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P],
     "pclip_vit_embed_backward_f16": [_P, c_int, c_int, c_int, _P, _P, _P],
     "pclip_adamw_f16": [_P, _P, _P, _P, c_size_t, c_double, c_double, c_double, c_double, c_double, c_int, _P],

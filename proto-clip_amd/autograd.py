@@ -319,11 +319,15 @@ class TowerTailFn(torch.autograd.Function):
     deep (visual prompt tuning; None otherwise): fp32 [n_deep, P, W], a tensor on the tape.  Before taped block i's ln_1, 1 <= i <= n_deep, the last P rows
     of every sequence are REPLACED by r16(deep[i - 1]) (ops.vpt_replace_); the backward sums those rows of the stream gradient that leaves block i's ln_1
     backward into ddeep[i - 1] and clears them in the same pass (ops.vpt_grad, clear): a replaced row passes no gradient to the block below.  Called
-    with nothing that requires a gradient (under torch.no_grad()) the forward issues the same kernels and keeps nothing for a backward."""
+    with nothing that requires a gradient (under torch.no_grad()) the forward issues the same kernels and keeps nothing for a backward.
+
+    deep_off (an optional ninth entry of `meta`; absent or None: the last P rows, as above): the pack's rows sit at deep_off .. deep_off + P - 1 of every
+    sequence instead — the learned context rows of a causal text tower (MaPLe) — through ops.rows_replace_ / ops.rows_grad, forward and backward."""
 
     @staticmethod
     def forward(ctx, x, h0, deep, meta, *params):
-        B, L, heads, causal, select, sel_rows, first_token, cache = meta
+        B, L, heads, causal, select, sel_rows, first_token, cache = meta[:8]
+        deep_off = meta[8] if len(meta) > 8 else None
         nb = (len(params) - 3) // 12
         ctx.meta, ctx.nb = meta, nb
         n_deep = 0 if deep is None else deep.shape[0]
@@ -340,7 +344,10 @@ class TowerTailFn(torch.autograd.Function):
             x, _ = residual_block(x, h, params[12 * i:12 * i + 12], B, L, heads, causal, select if last else None, first_token, rec=rec)
             if not last:
                 if i < n_deep:                                                 # block i + 1 reads its own prompt rows: replaced before its ln_1
-                    ops.vpt_replace_(x, deep[i], B, L - deep.shape[1])
+                    if deep_off is None:
+                        ops.vpt_replace_(x, deep[i], B, L - deep.shape[1])
+                    else:
+                        ops.rows_replace_(x, deep[i], B, L, deep_off)
                 h = ops.layernorm(x, params[12 * (i + 1)], params[12 * (i + 1) + 1])
             if taping:
                 tape.append(rec)
@@ -355,7 +362,8 @@ class TowerTailFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        B, L, heads, causal, select, sel_rows, first_token, cache = ctx.meta
+        B, L, heads, causal, select, sel_rows, first_token, cache = ctx.meta[:8]
+        deep_off = ctx.meta[8] if len(ctx.meta) > 8 else None
         params = ctx.saved_tensors
         nb = ctx.nb
         grads = [None] * len(params)
@@ -419,7 +427,7 @@ class TowerTailFn(torch.autograd.Function):
             gx, grads[o + 0], grads[o + 1] = ops.layernorm_backward_f32(rec["x_in"], ln1w, dh1, residual=gx)
             if 1 <= i <= n_deep:                                               # the replaced rows: their gradient is deep[i - 1]'s and goes no further
                 P = ctx.deep_shape[1]
-                d = ops.vpt_grad(gx, B, L - P, P, clear=True)
+                d = ops.vpt_grad(gx, B, L - P, P, clear=True) if deep_off is None else ops.rows_grad(gx, B, L, deep_off, P, clear=True)
                 if ddeep is not None:
                     ddeep[i - 1] = d
         dx = None
@@ -432,10 +440,11 @@ class TowerTailFn(torch.autograd.Function):
         return (dx, None, ddeep, None) + tuple(out)
 
 
-def run_tower_tail(tw, x, h0, first, B, L, pick, what, deep=None):
+def run_tower_tail(tw, x, h0, first, B, L, pick, what, deep=None, deep_off=None):
     """The taped tail of tower `tw` (a tower.Tower): blocks[first:] + final LayerNorm + projection on the residual stream x [B*L, W] (h0: ln_1 of
     blocks[first] when the caller already has it).  pick = (select, rows) from `tw.pick`, or (None, None) when x already holds the picked rows.
-    deep: TowerTailFn's pack of deep visual prompts, fp32 [n_deep, P, W] with n_deep < len(blocks) - first and P < L."""
+    deep: TowerTailFn's pack of deep visual prompts, fp32 [n_deep, P, W] with n_deep < len(blocks) - first and P < L; deep_off: None (the pack's rows are
+    the last P of a sequence) or the first of the P rows, deep_off + P <= L."""
     blocks, (select, rows) = tw.blocks, pick
     if ops.splitk_active(B) or ops.splitk_active(B * L):
         raise PclipError(f"{what}: a differentiable pass inside ops.low_latency() is not supported (the split-K linears have no backward); "
@@ -452,7 +461,16 @@ def run_tower_tail(tw, x, h0, first, B, L, pick, what, deep=None):
             raise PclipError(f"{what}: deep prompts {deep.dtype} {tuple(deep.shape)} are not float32 [n_deep, P, {x.shape[1]}] with 1 <= P < L={L}")
         if not 1 <= deep.shape[0] < len(blocks) - first:
             raise PclipError(f"{what}: {deep.shape[0]} deep prompt layers, but only blocks {first + 1}..{len(blocks) - 1} can take one")
+    if deep_off is not None:
+        if deep is None:
+            raise PclipError(f"{what}: deep_off={deep_off} without a pack of deep prompt rows")
+        deep_off = int(deep_off)
+        if deep_off < 0 or deep_off + deep.shape[1] > L:
+            raise PclipError(f"{what}: deep prompt rows deep_off .. deep_off + P - 1 = {deep_off} .. {deep_off + deep.shape[1] - 1} do not lie inside a "
+                             f"sequence of L={L} tokens")
     meta = (B, L, tw.heads, tw.causal, select, None if select is None else rows(), tw.first_token, tw.cache)
+    if deep_off is not None:
+        meta = meta + (deep_off,)
     return TowerTailFn.apply(x, h0, deep, meta, *params)
 
 
@@ -544,6 +562,27 @@ class PromptEmbedFn(torch.autograd.Function):
         if dx.dtype != torch.float16:
             dx = ops.cast_f16(dx.float())
         return ops.prompt_ctx_grad(dx, N, L_out, n_ctx, per_class), None, None, None, None, None
+
+
+# ---- MaPLe's coupling function: the visual prompt rows of every depth as a linear function of that depth's text rows ----------------------------------
+
+class CoupleFn(torch.autograd.Function):
+    """(x [depth, P, Wt], weight [depth, Wv, Wt], bias [depth, Wv], all fp32) -> y [depth, P, Wv] fp32 = x[d] @ weight[d].T + bias[d]: every depth in one
+    launch (pclip_couple_fwd_f32).  backward: pclip_couple_bwd_f32 issues only the gradients `needs_input_grad` asks for — dx = dy[d] @ weight[d],
+    dweight = dy[d].T @ x[d], dbias = dy[d].sum(0) — each in the one summation order csrc/pclip_maple.hip documents."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        ctx.save_for_backward(x, weight)
+        return ops.couple(x, weight, bias)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if dy.dtype != torch.float32:
+            raise PclipError(f"CoupleFn: the gradient of the coupled rows must be float32, got {dy.dtype}")
+        return ops.couple_backward(dy.contiguous(), x, weight, want_x=need[0], want_weight=need[1], want_bias=need[2])
 
 
 # ---- visual prompt tuning (VPT): the stream that enters block 0 as a function of the first layer's fp32 prompt rows ------------------------------------

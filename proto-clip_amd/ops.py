@@ -1233,6 +1233,90 @@ def vpt_grad(g, B: int, L0: int, P: int, clear: bool = False) -> torch.Tensor:
     return dctx
 
 
+def _rows_window(who: str, t, B: int, L: int, off: int, P: int):
+    """The stream operand of the rows-at-an-offset passes: contiguous fp16 [B * L, W] with the window off .. off + P - 1 inside a sequence."""
+    if t.dtype != torch.float16 or not t.is_contiguous() or t.dim() != 2 or t.shape[0] != B * L:
+        raise _lib.PclipError(f"{who}: {t.dtype} {tuple(t.shape)} is not a contiguous float16 [B * L, W] with B={B}, L={L}")
+    if off < 0 or P < 1 or off + P > L:
+        raise _lib.PclipError(f"{who}: rows off .. off + P - 1 = {off} .. {off + P - 1} do not lie inside a sequence of L={L} rows")
+
+
+def rows_replace_(x, ctx, B: int, L: int, off: int) -> torch.Tensor:
+    """In place on the stream x [B * L, W] fp16: rows off .. off + P - 1 of every sequence become the fp32 rows ctx [P, W] rounded once to fp16
+    (pclip_rows_replace_f16); every other row keeps its bits.  Returns x.  off = L - P is `vpt_replace_`."""
+    require_cuda(x, ctx)
+    W = x.shape[-1]
+    ctx = _vpt_ctx("rows_replace_", ctx, W)
+    P = ctx.shape[0]
+    B, L, off = int(B), int(L), int(off)
+    _rows_window("rows_replace_: x", x, B, L, off, P)
+    check(_lib.load().pclip_rows_replace_f16(ptr(x), ptr(ctx), B, L, off, P, W, stream()), "pclip_rows_replace_f16")
+    return x
+
+
+def rows_grad(g, B: int, L: int, off: int, P: int, clear: bool = False) -> torch.Tensor:
+    """fp32 [P, W]: rows off .. off + P - 1 of every sequence of the gradient stream g [B * L, W] fp16 summed over the B sequences in
+    pclip_vpt_grad_f32's fixed order (pclip_rows_grad_f32).  clear: the pass also writes exact zeros over those rows of g, IN PLACE; rows outside
+    the window are neither read nor written.  off = L - P is `vpt_grad`."""
+    require_cuda(g)
+    B, L, off, P = int(B), int(L), int(off), int(P)
+    _rows_window("rows_grad: g", g, B, L, off, P)
+    W = g.shape[1]
+    dctx = torch.empty(P, W, dtype=torch.float32, device=g.device) if B > 0 else torch.zeros(P, W, dtype=torch.float32, device=g.device)
+    nslice = (B + _lib.VPT_SLICE - 1) // _lib.VPT_SLICE
+    part = torch.empty(nslice, P * W, dtype=torch.float32, device=g.device) if nslice > 1 else None      # the kernel's workspace
+    check(_lib.load().pclip_rows_grad_f32(ptr(g), B, L, off, P, W, int(bool(clear)), ptr(dctx), ptr(part), nslice, stream()), "pclip_rows_grad_f32")
+    return dctx
+
+
+def _couple_f32(who: str, name: str, t, shape):
+    """An fp32 operand of the coupling function: dtype and shape checked, contiguous."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise _lib.PclipError(f"{who}: {name} must be float32, got {getattr(t, 'dtype', type(t))}")
+    if tuple(t.shape) != tuple(shape):
+        raise _lib.PclipError(f"{who}: {name} {tuple(t.shape)} is not {list(shape)}")
+    return t.contiguous()
+
+
+def _couple_dims(who: str, rows, weight):
+    if rows.dim() != 3 or weight.dim() != 3:
+        raise _lib.PclipError(f"{who}: rows {tuple(rows.shape)} / weight {tuple(weight.shape)} are not [depth, P, W] / [depth, Wv, Wt]")
+    return rows.shape[0], rows.shape[1], weight.shape[2], weight.shape[1]
+
+
+def couple(x, weight, bias) -> torch.Tensor:
+    """The coupling function of every depth in one launch: y [depth, P, Wv] fp32 = x[d] @ weight[d].T + bias[d] for x [depth, P, Wt], weight
+    [depth, Wv, Wt], bias [depth, Wv], all fp32 (pclip_couple_fwd_f32: 1 <= P <= 16, Wt % 64 == 0, Wv % 8 == 0; one fixed summation order)."""
+    require_cuda(x, weight, bias)
+    depth, P, Wt, Wv = _couple_dims("couple", x, weight)
+    x = _couple_f32("couple", "x", x, (depth, P, Wt))
+    weight = _couple_f32("couple", "weight", weight, (depth, Wv, Wt))
+    bias = _couple_f32("couple", "bias", bias, (depth, Wv))
+    y = torch.empty(depth, P, Wv, dtype=torch.float32, device=x.device)
+    check(_lib.load().pclip_couple_fwd_f32(ptr(x), ptr(weight), ptr(bias), depth, P, Wt, Wv, ptr(y), stream()), "pclip_couple_fwd_f32")
+    return y
+
+
+def couple_backward(dy, x, weight, want_x: bool = True, want_weight: bool = True, want_bias: bool = True):
+    """(dx, dweight, dbias) of `couple` from dy [depth, P, Wv] fp32 — dx = dy[d] @ weight[d], dweight = dy[d].T @ x[d], dbias = dy[d].sum(0) — each
+    None when not wanted: nothing is launched or allocated for it (pclip_couple_bwd_f32: at most two launches and one merge)."""
+    require_cuda(dy, x, weight)
+    depth, P, Wt, Wv = _couple_dims("couple_backward", x, weight)
+    dy = _couple_f32("couple_backward", "dy", dy, (depth, P, Wv))
+    x = _couple_f32("couple_backward", "x", x, (depth, P, Wt))
+    weight = _couple_f32("couple_backward", "weight", weight, (depth, Wv, Wt))
+    dev = dy.device
+    dx = torch.empty(depth, P, Wt, dtype=torch.float32, device=dev) if want_x else None
+    dw = torch.empty(depth, Wv, Wt, dtype=torch.float32, device=dev) if want_weight else None
+    db = torch.empty(depth, Wv, dtype=torch.float32, device=dev) if want_bias else None
+    nslice = (Wv + _lib.COUPLE_SLICE - 1) // _lib.COUPLE_SLICE
+    part = torch.empty(depth, nslice, P * Wt, dtype=torch.float32, device=dev) if want_x and nslice > 1 else None      # the kernel's workspace
+    if want_x or want_weight or want_bias:
+        check(_lib.load().pclip_couple_bwd_f32(ptr(dy), ptr(x), ptr(weight), depth, P, Wt, Wv, ptr(dw), ptr(db), ptr(dx), ptr(part), nslice, stream()),
+              "pclip_couple_bwd_f32")
+    return dx, dw, db
+
+
 def gather_eot(x, tokens, B: int, L: int, W: int) -> torch.Tensor:
     tokens = tokens.to(torch.int64).contiguous()
     out = torch.empty(B, W, dtype=torch.float16, device=x.device)

@@ -156,12 +156,12 @@ class Tower:
         return f"{self.entry} ({self.name}, blocks {first}..{n - 1} + heads trainable)"
 
 
-def run_tower(tw, x, B, L, plan, pick, what=None, h0=None, deep=None):
+def run_tower(tw, x, B, L, plan, pick, what=None, h0=None, deep=None, deep_off=None):
     """Features [B, E] of tower `tw` from the residual stream x [B*L, W] that enters block 0.  plan = (first, stem) as `Tower.tape_plan` gives it:
     blocks[:first] run frozen, blocks[first:] + final LayerNorm + projection on the tape (autograd.run_tower_tail; only the heads when
     first == len(blocks): the frozen walk then keeps its class-row shortcut); first None: nothing is taped — the frozen walk, ln(picked row)
     (row-wise: commutes with the pick) and the projection GEMM.  pick = (select, rows) from `tw.pick`; h0: ln_1(x) of block 0 when the stem
-    produced it (dropped when a frozen prefix runs first); what: the pass in the words of a refusal (default `tw.what`); deep: TowerTailFn's."""
+    produced it (dropped when a frozen prefix runs first); what: the pass in the words of a refusal (default `tw.what`); deep, deep_off: TowerTailFn's."""
     first, stem = plan
     select, _ = pick
     if first is None:
@@ -181,7 +181,7 @@ def run_tower(tw, x, B, L, plan, pick, what=None, h0=None, deep=None):
         with torch.no_grad():
             x, _ = _run_blocks(x, tw.blocks[:first], B, L, tw.heads, tw.causal, h0=h0)
         h0 = None
-    return run_tower_tail(tw, x, h0, first, B, L, pick, what, deep=deep)
+    return run_tower_tail(tw, x, h0, first, B, L, pick, what, deep=deep, deep_off=deep_off)
 
 
 def _pad_patch_weight(w):

@@ -15,8 +15,8 @@ no parameter gradient; `clip_model.unfreeze(visual_blocks=k)` composes with it: 
 
 Envelope: transformer towers of head dimension 64, fp32 `ctx`, L0 + P <= 288 tokens (ViT-B/16: P <= 91, ViT-B/32: P <= 238, ViT-L/14: P <= 31; the 336-px
 tower has 577 tokens of its own and is refused).  Not here: prompts directly behind the class token (Jia et al.'s order), a positional embedding on the
-prompts, VPT beside a trainable stem (`unfreeze(stem=...)`), MaPLe's coupling function as a module (an explicit `ctx` tensor on the tape is all it
-needs from this one)."""
+prompts, VPT beside a trainable stem (`unfreeze(stem=...)`).  MaPLe's coupling function lives in `maple.py`; an explicit `ctx` tensor on the tape is all
+it needs from this module."""
 import numpy as np
 import torch
 
