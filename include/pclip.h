@@ -647,6 +647,16 @@ int pclip_colsum_f16(const void* x, int ldx, int R, int C, float* part, int nsli
 int pclip_layernorm_backward_g32_f16(const void* x, int ldx, const float* gamma, const void* dy, int lddy, const void* residual, int ldr,
                                      int R, int D, float eps, void* dx, int lddx, float* part, int nblk, pclip_stream_t stream);
 
+/* ---- learned prompt rows (CoOp, VPT, MaPLe): THE SLICE-SUM RULE, stated here once (csrc/pclip_rows.h implements it once) ---------------------------
+ * pclip_prompt_ctx_grad_f32, pclip_vpt_grad_f32 and pclip_rows_grad_f32 are one walk: rows off .. off + P - 1 of every sequence of an fp16 stream
+ * [B * L, W] (CoOp: off = 1 over the classes; VPT: off = L0 = L - P; MaPLe: any off), summed over the B sequences in fp32 in ONE fixed order —
+ * the sequences are cut into slices of 16 consecutive sequences (PCLIP_PROMPT_CTX_SLICE = PCLIP_VPT_SLICE; the last slice may be short); inside a
+ * slice, ascending sequence order into one fp32 accumulator per column -> part [nslice][P * W]; then the slices in ascending order into one
+ * accumulator -> dctx [P, W]; every sum starts from its first term (no zero is added) and every `+` is one rounded fp32 addition; f32(fp16) is exact
+ * and nothing is rounded to fp16.  nslice must be ceil(B / 16); part may be NULL when that is 1 (dctx is then the first stage's output).  No atomics:
+ * two calls give the same bits.  clear != 0 (where an entry has it): the same pass writes exact zeros over the rows of g it has read — the lane that
+ * loaded a vector stores the zeros over it, after its load; rows outside the window are neither read nor written. */
+
 /* ---- learned prompt context (CoOp: context rows trained through the frozen text tower; csrc/pclip_prompt.hip) ---------------- */
 
 /* The embedded prompts of clip/model.py:342-343 with learned rows in place of the token embeddings at positions 1 .. n_ctx:
@@ -658,15 +668,14 @@ int pclip_prompt_embed_f16(const int64_t* tokens, int L_tok, const void* tok_emb
                            int n_ctx, int N, int L_out, int W, int vocab, void* x, pclip_stream_t stream);
 
 /* Gradient of that assembly wrt ctx from dx [N * L_out, W] fp16 (the cast of ctx to fp16 is passed through).  class_specific:
- * dctx [N, n_ctx, W] = f32(dx[n, 1 + j]), exact; part and nslice are ignored.  Shared: dctx [n_ctx, W] = sum over the classes in fp32 in ONE
- * fixed order — slices of PCLIP_PROMPT_CTX_SLICE consecutive classes summed in class order into part [nslice][n_ctx * W], the slices then summed
- * in slice order, every sum starting from its first term; nslice must be ceil(N / PCLIP_PROMPT_CTX_SLICE), and part may be NULL when that is 1.
- * No atomics: two calls give the same bits.  Context rows at 1 + j >= L_out get a zero gradient. */
+ * dctx [N, n_ctx, W] = f32(dx[n, 1 + j]), exact (the walk with slices of one class); part and nslice are ignored.  Shared: dctx [n_ctx, W] = the
+ * sum over the N classes by the slice-sum rule above at off = 1, nslice = ceil(N / PCLIP_PROMPT_CTX_SLICE).  dx is not written.  Context rows at
+ * 1 + j >= L_out have no row in dx: they are not read and get a zero gradient. */
 #define PCLIP_PROMPT_CTX_SLICE 16
 int pclip_prompt_ctx_grad_f32(const void* dx, int N, int L_out, int n_ctx, int W, int class_specific, float* dctx, float* part, int nslice,
                               pclip_stream_t stream);
 
-/* ---- visual prompt tuning (VPT: token rows trained through the frozen vision tower; csrc/pclip_vpt.hip lists the rounding points) ---------- */
+/* ---- visual prompt tuning (VPT: token rows trained through the frozen vision tower; csrc/pclip_rows.h lists the rounding points) ---------- */
 
 /* A sequence of the vision tower with P learned rows BEHIND its L0 stem rows (class token, patches): L = L0 + P rows, L <= PCLIP_VPT_MAX_L (the
  * attention kernels' resident-K/V envelope).  ctx is fp32 [P, W]; a prompt element enters the fp16 stream rounded once, round to nearest even, with
@@ -682,15 +691,11 @@ int pclip_vpt_append_f16(const void* t, const float* ctx, int B, int L0, int P, 
 /* In place on the stream x [B * L, W] fp16: rows L0 .. L - 1 of every sequence become r16(ctx); the other rows are not touched. */
 int pclip_vpt_replace_f16(void* x, const float* ctx, int B, int L0, int P, int W, pclip_stream_t stream);
 
-/* dctx [P, W] fp32 = sum over the B sequences of f32(g[b, L0 + j, :]), g [B * L, W] fp16 (L0 == 0: a compact [B * P, W]), in ONE fixed order: slices
- * of PCLIP_VPT_SLICE consecutive images; inside a slice, ascending image order into one fp32 accumulator per column -> part [nslice][P * W]; then the
- * slices in ascending order into one accumulator; every sum starts from its first term.  nslice must be ceil(B / PCLIP_VPT_SLICE); part may be NULL
- * when that is 1 (dctx is then the first stage's output).  This is pclip_prompt_ctx_grad_f32's rule.  clear != 0: the same pass writes exact zeros
- * over the prompt rows of g it has read (the lane that loaded an element stores the zero, after its load); rows l < L0 are neither read nor
- * written. */
+/* dctx [P, W] fp32 = sum over the B sequences of f32(g[b, L0 + j, :]), g [B * L, W] fp16 (L0 == 0: a compact [B * P, W]), by the slice-sum rule
+ * above at off = L0, nslice = ceil(B / PCLIP_VPT_SLICE), with its `clear`; rows l < L0 are neither read nor written. */
 int pclip_vpt_grad_f32(void* g, int B, int L0, int P, int W, int clear, float* dctx, float* part, int nslice, pclip_stream_t stream);
 
-/* ---- MaPLe: prompt rows at an offset and the text -> vision coupling function (csrc/pclip_maple.hip lists the rounding points and every order) ---- */
+/* ---- MaPLe: prompt rows at an offset and the text -> vision coupling function (csrc/pclip_maple.hip lists the coupling's rounding points and orders) ---- */
 
 /* The two VPT passes above with the P rows at off .. off + P - 1 of sequences of L rows: L, off and P independent, 0 <= off, off + P <= L,
  * L <= PCLIP_VPT_MAX_L, W % 8 == 0, B >= 0, B * L * W within an int, operands 16-byte aligned, no atomics.  At off = L - P they give the bits of
@@ -699,10 +704,8 @@ int pclip_vpt_grad_f32(void* g, int B, int L0, int P, int W, int clear, float* d
 /* In place on the stream x [B * L, W] fp16: rows off .. off + P - 1 of every sequence become r16(ctx), ctx fp32 [P, W]; the other rows are not touched. */
 int pclip_rows_replace_f16(void* x, const float* ctx, int B, int L, int off, int P, int W, pclip_stream_t stream);
 
-/* dctx [P, W] fp32 = sum over the B sequences of f32(g[b, off + j, :]) in pclip_vpt_grad_f32's order (slices of PCLIP_VPT_SLICE consecutive sequences,
- * ascending inside a slice, then ascending slice order; every sum starts from its first term); nslice = ceil(B / PCLIP_VPT_SLICE), part
- * [nslice][P * W] may be NULL when that is 1.  clear != 0: the lane that loaded a vector stores exact zeros over it, after its load.  Rows outside
- * [off, off + P) are neither read nor written. */
+/* dctx [P, W] fp32 = sum over the B sequences of f32(g[b, off + j, :]) by the slice-sum rule above, nslice = ceil(B / PCLIP_VPT_SLICE), with its
+ * `clear`.  Rows outside [off, off + P) are neither read nor written. */
 int pclip_rows_grad_f32(void* g, int B, int L, int off, int P, int W, int clear, float* dctx, float* part, int nslice, pclip_stream_t stream);
 
 /* The coupling function, fp32, all depths in one launch: Y[d] = X[d] Wc[d]^T + bc[d], X [depth, P, Wt], Wc [depth, Wv, Wt], bc [depth, Wv],

@@ -316,18 +316,16 @@ class TowerTailFn(torch.autograd.Function):
     order, each in _block_params' order), then ln.weight, ln.bias, proj.  The backward issues a weight / bias gradient only for a parameter that
     requires one: a frozen tower under a trainable input pays for none.
 
-    deep (visual prompt tuning; None otherwise): fp32 [n_deep, P, W], a tensor on the tape.  Before taped block i's ln_1, 1 <= i <= n_deep, the last P rows
-    of every sequence are REPLACED by r16(deep[i - 1]) (ops.vpt_replace_); the backward sums those rows of the stream gradient that leaves block i's ln_1
-    backward into ddeep[i - 1] and clears them in the same pass (ops.vpt_grad, clear): a replaced row passes no gradient to the block below.  Called
-    with nothing that requires a gradient (under torch.no_grad()) the forward issues the same kernels and keeps nothing for a backward.
-
-    deep_off (an optional ninth entry of `meta`; absent or None: the last P rows, as above): the pack's rows sit at deep_off .. deep_off + P - 1 of every
-    sequence instead — the learned context rows of a causal text tower (MaPLe) — through ops.rows_replace_ / ops.rows_grad, forward and backward."""
+    deep (prompt learning; None otherwise): fp32 [n_deep, P, W], a tensor on the tape; deep_off, the ninth entry of `meta` (None without a pack): the first
+    of the pack's rows in a sequence — L - P for visual prompts behind the patch rows (VPT), 1 for the context rows of a causal text tower (MaPLe).  Before
+    taped block i's ln_1, 1 <= i <= n_deep, rows deep_off .. deep_off + P - 1 of every sequence are REPLACED by r16(deep[i - 1]) (ops.rows_replace_); the
+    backward sums those rows of the stream gradient that leaves block i's ln_1 backward into ddeep[i - 1] and clears them in the same pass (ops.rows_grad,
+    clear): a replaced row passes no gradient to the block below.  Called with nothing that requires a gradient (under torch.no_grad()) the forward issues
+    the same kernels and keeps nothing for a backward."""
 
     @staticmethod
     def forward(ctx, x, h0, deep, meta, *params):
-        B, L, heads, causal, select, sel_rows, first_token, cache = meta[:8]
-        deep_off = meta[8] if len(meta) > 8 else None
+        B, L, heads, causal, select, sel_rows, first_token, cache, deep_off = meta
         nb = (len(params) - 3) // 12
         ctx.meta, ctx.nb = meta, nb
         n_deep = 0 if deep is None else deep.shape[0]
@@ -344,10 +342,7 @@ class TowerTailFn(torch.autograd.Function):
             x, _ = residual_block(x, h, params[12 * i:12 * i + 12], B, L, heads, causal, select if last else None, first_token, rec=rec)
             if not last:
                 if i < n_deep:                                                 # block i + 1 reads its own prompt rows: replaced before its ln_1
-                    if deep_off is None:
-                        ops.vpt_replace_(x, deep[i], B, L - deep.shape[1])
-                    else:
-                        ops.rows_replace_(x, deep[i], B, L, deep_off)
+                    ops.rows_replace_(x, deep[i], B, L, deep_off)
                 h = ops.layernorm(x, params[12 * (i + 1)], params[12 * (i + 1) + 1])
             if taping:
                 tape.append(rec)
@@ -362,8 +357,7 @@ class TowerTailFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        B, L, heads, causal, select, sel_rows, first_token, cache = ctx.meta[:8]
-        deep_off = ctx.meta[8] if len(ctx.meta) > 8 else None
+        B, L, heads, causal, select, sel_rows, first_token, cache, deep_off = ctx.meta
         params = ctx.saved_tensors
         nb = ctx.nb
         grads = [None] * len(params)
@@ -426,8 +420,7 @@ class TowerTailFn(torch.autograd.Function):
             del dqkv
             gx, grads[o + 0], grads[o + 1] = ops.layernorm_backward_f32(rec["x_in"], ln1w, dh1, residual=gx)
             if 1 <= i <= n_deep:                                               # the replaced rows: their gradient is deep[i - 1]'s and goes no further
-                P = ctx.deep_shape[1]
-                d = ops.vpt_grad(gx, B, L - P, P, clear=True) if deep_off is None else ops.rows_grad(gx, B, L, deep_off, P, clear=True)
+                d = ops.rows_grad(gx, B, L, deep_off, ctx.deep_shape[1], clear=True)
                 if ddeep is not None:
                     ddeep[i - 1] = d
         dx = None
@@ -443,8 +436,8 @@ class TowerTailFn(torch.autograd.Function):
 def run_tower_tail(tw, x, h0, first, B, L, pick, what, deep=None, deep_off=None):
     """The taped tail of tower `tw` (a tower.Tower): blocks[first:] + final LayerNorm + projection on the residual stream x [B*L, W] (h0: ln_1 of
     blocks[first] when the caller already has it).  pick = (select, rows) from `tw.pick`, or (None, None) when x already holds the picked rows.
-    deep: TowerTailFn's pack of deep visual prompts, fp32 [n_deep, P, W] with n_deep < len(blocks) - first and P < L; deep_off: None (the pack's rows are
-    the last P of a sequence) or the first of the P rows, deep_off + P <= L."""
+    deep: TowerTailFn's pack of deep prompt rows, fp32 [n_deep, P, W] with n_deep < len(blocks) - first and P < L; deep_off: the first of the P rows in a
+    sequence, deep_off + P <= L (None: the last P rows, L - P)."""
     blocks, (select, rows) = tw.blocks, pick
     if ops.splitk_active(B) or ops.splitk_active(B * L):
         raise PclipError(f"{what}: a differentiable pass inside ops.low_latency() is not supported (the split-K linears have no backward); "
@@ -468,9 +461,9 @@ def run_tower_tail(tw, x, h0, first, B, L, pick, what, deep=None, deep_off=None)
         if deep_off < 0 or deep_off + deep.shape[1] > L:
             raise PclipError(f"{what}: deep prompt rows deep_off .. deep_off + P - 1 = {deep_off} .. {deep_off + deep.shape[1] - 1} do not lie inside a "
                              f"sequence of L={L} tokens")
-    meta = (B, L, tw.heads, tw.causal, select, None if select is None else rows(), tw.first_token, tw.cache)
-    if deep_off is not None:
-        meta = meta + (deep_off,)
+    if deep is not None and deep_off is None:
+        deep_off = L - deep.shape[1]
+    meta = (B, L, tw.heads, tw.causal, select, None if select is None else rows(), tw.first_token, tw.cache, deep_off)
     return TowerTailFn.apply(x, h0, deep, meta, *params)
 
 

@@ -12,13 +12,13 @@ composes with it: the last k blocks and the heads then train beside the context.
 
 Envelope: the class token at the "end" (context directly after SOT) only, fp32 `ctx`, head dimension 64, prompts of at most 77 tokens.  Not here:
 CoCoOp's meta-net, the "middle" / "front" positions."""
-import numpy as np
 import torch
 
 from . import autograd as pag
 from . import ops
 from . import utils
 from ._lib import PclipError
+from .prompt_train import accuracy, train_prompts
 from .tower import eot_positions, run_tower
 
 PLACEHOLDER = "X"        # one BPE token; its embedding is never read (the context rows take its positions)
@@ -167,10 +167,6 @@ class CoOp(torch.nn.Module):
         return utils.clip_zero_shot(features, self.text_rows(), scale=float(self.logit_scale()), topk=topk, layout="nd")
 
 
-def _acc(pred, labels):
-    return 100.0 * float((pred == labels.to(pred.device).long()).sum().item()) / labels.shape[0]
-
-
 def run_coop(cfg, train_features, train_labels, test_features, test_labels, classnames, clip_model, tokenize=None, tokenized_prompts=None):
     """Train a context on cached features ([Q, D] fp16 and labels, as `pre_load_features` / `build_cache_model` hold them) with CoOp's recipe: SGD on `ctx`,
     learning rate 0.002, momentum 0.9, cosine schedule, batches of 32, cfg['coop_epochs'] epochs, cfg['n_ctx'] context rows (optional keys: 'ctx_init',
@@ -182,34 +178,11 @@ def run_coop(cfg, train_features, train_labels, test_features, test_labels, clas
     learner = PromptLearner(classnames, clip_model, n_ctx=cfg.get("n_ctx", 16), ctx_init=cfg.get("ctx_init"), class_specific=cfg.get("class_specific", False),
                             tokenize=tokenize, tokenized_prompts=tokenized_prompts, seed=seed)
     model = CoOp(clip_model, learner)
-    epochs, batch = int(cfg["coop_epochs"]), int(cfg.get("coop_batch", 32))
-    Q = train_features.shape[0]
-    steps = (Q + batch - 1) // batch
-    optimizer = torch.optim.SGD(learner.parameters(), lr=cfg.get("coop_lr", 0.002), momentum=0.9)
-    scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, max(1, epochs * steps))
-    scaler = torch.amp.GradScaler("cuda", init_scale=float(cfg.get("coop_loss_scale", 1024.0)))
-    train_labels = train_labels.to(train_features.device).long()
-    res = {"epochs": []}
-    res["start_test_acc"] = _acc(model.classify(test_features), test_labels)
-    print("\n**** CoOp's test accuracy before training: {:.2f}. ****\n".format(res["start_test_acc"]))
-    g = torch.Generator().manual_seed(seed)
-    for epoch in range(epochs):
-        print("Train Epoch: {:} / {:}".format(epoch, epochs))
-        order = torch.randperm(Q, generator=g).to(train_features.device)
-        losses = []
-        for s in range(steps):
-            idx = order[s * batch:(s + 1) * batch]
-            loss = model.loss(train_features[idx].contiguous(), train_labels[idx])
-            optimizer.zero_grad()
-            scaler.scale(loss).backward()
-            scaler.step(optimizer)
-            scaler.update()
-            scheduler.step()
-            losses.append(float(loss.detach()))
-        acc = _acc(model.classify(test_features), test_labels)
-        print("LR: {:.6f}, Loss: {:.4f}".format(scheduler.get_last_lr()[0], float(np.mean(losses))))
-        print("**** CoOp's test accuracy: {:.2f}. ****\n".format(acc))
-        res["epochs"].append({"loss": float(np.mean(losses)), "test_acc": acc})
+    labels = train_labels.to(train_features.device).long()
+    res, _ = train_prompts("CoOp", learner.parameters(), lambda idx: model.loss(train_features[idx].contiguous(), labels[idx]),
+                           train_features.shape[0], train_features.device, epochs=int(cfg["coop_epochs"]), batch=int(cfg.get("coop_batch", 32)),
+                           lr=cfg.get("coop_lr", 0.002), momentum=0.9, loss_scale=cfg.get("coop_loss_scale", 1024.0), seed=seed,
+                           evaluate=lambda: accuracy(model.classify(test_features), test_labels))
     res["test_acc"] = res["epochs"][-1]["test_acc"] if res["epochs"] else res["start_test_acc"]
     model.results = res
     return model

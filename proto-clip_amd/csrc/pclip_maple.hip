@@ -3,19 +3,9 @@
 // its gradients.  No atomics, no hand-over between workgroups: every sum has one fixed order and two calls give the same bits.
 //
 // ---- prompt rows at an offset ------------------------------------------------------------------------------------------------------------------------
-// Shapes: B sequences of L rows, the stream is [B * L, W] fp16; the P prompt rows are rows off .. off + P - 1 of every sequence; L, off and P are
-// independent (0 <= off, off + P <= L <= PCLIP_VPT_MAX_L).  Flat passes of 16-byte (8-half) vectors, W % 8 == 0.  At off = L - P both entries are
-// pclip_vpt_replace_f16 / pclip_vpt_grad_f32 (pclip_vpt.hip) bit for bit: the same loads, the same additions in the same order.
-//
-// Rounding points / summation order
-//   replace:  a prompt element is rounded ONCE, fp32 -> fp16, round to nearest even (r16); nothing is added to it.  Every other row is not touched.
-//   gradient: f32(fp16) is exact; every `+` below is one rounded fp32 addition; nothing is rounded to fp16.
-//     the sequences are cut into slices of PCLIP_VPT_SLICE = 16 consecutive sequences (the last one may be short); n0 = 16 s;
-//     part[s][j][d] = (..((f32(g[n0, off + j, d]) + f32(g[n0 + 1, off + j, d])) + f32(g[n0 + 2, off + j, d])) + ..)   ascending sequence order, one accumulator
-//     dctx[j][d]    = (..((part[0][j][d] + part[1][j][d]) + part[2][j][d]) + ..)                                      ascending slice order, one accumulator
-//     each sum starts from its first term (no zero is added).  One slice: part is dctx itself.
-//   clear = 1: the same pass stores exact zeros (+0) over the rows of g it has read — the lane that loaded a vector stores the zeros over it, after its
-//   load.  Rows outside [off, off + P) are neither read nor written.
+// pclip_rows_replace_f16 / pclip_rows_grad_f32: the replace and the slice-sum walk of pclip_rows.h with L, off and P independent
+// (0 <= off, off + P <= L <= PCLIP_VPT_MAX_L); rounding points, summation order and `clear` are stated there.  The row kernels hold no multiplication,
+// so they are indifferent to this file's contraction setting.
 //
 // ---- the coupling function, fp32, all depths in one launch -----------------------------------------------------------------------------------------------
 // Y[d] = X[d] Wc[d]^T + bc[d]:  X [depth, P, Wt] (text rows), Wc [depth, Wv, Wt], bc [depth, Wv], Y [depth, P, Wv] (visual rows).
@@ -37,83 +27,11 @@
 //     dX[d][p][t]      = (..((part[d][0][p][t] + part[d][1][p][t]) + part[d][2][p][t]) + ..)                ascending slice order, starting from slice 0
 //     One slice (Wv <= 32): part is dX itself and there is no merge launch.  (1 product + at most 32 additions + nslice - 1 merges)
 // Launches: forward 1; backward at most 2 (dWc with dbc; dX partials) + 1 merge, for any depth.
-#include "pclip_common.h"
+#include "pclip_rows.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-inline int flat_grid(size_t n) { size_t g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g)); }
-
-__device__ __forceinline__ half8_t r16_row8(const float* __restrict__ c) {
-    const float4_t c0 = reinterpret_cast<const float4_t*>(c)[0], c1 = reinterpret_cast<const float4_t*>(c)[1];
-    half8_t a;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { a[j] = (half_t)c0[j]; a[4 + j] = (half_t)c1[j]; }
-    return a;
-}
-
-// x[b, off + j, :] = r16(ctx[j, :]); the other rows are not touched
-__global__ __launch_bounds__(256) void rows_replace_kernel(half_t* __restrict__ x, const float* __restrict__ ctx, int B, int L, int off, int P, int W) {
-    const int WV = W / 8;
-    const size_t nvec = (size_t)B * P * WV;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (size_t)gridDim.x * 256) {
-        const int d = (int)(i % WV) * 8;
-        const int j = (int)((i / WV) % P);
-        const size_t b = i / ((size_t)WV * P);
-        st_half8(x + (b * L + off + j) * W + d, r16_row8(ctx + (size_t)j * W + d));
-    }
-}
-
-// first stage: one thread per (slice, prompt row, 8 columns) walks its slice's sequences in ascending order
-__global__ __launch_bounds__(256) void rows_grad_part_kernel(half_t* __restrict__ g, int B, int L, int off, int P, int W, int clear, int nslice,
-                                                             float* __restrict__ part) {
-    const int WV = W / 8;
-    const size_t nvec = (size_t)nslice * P * WV;
-    half8_t zero;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) zero[k] = (half_t)0.f;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (size_t)gridDim.x * 256) {
-        const int d = (int)(i % WV) * 8;
-        const int j = (int)((i / WV) % P);
-        const int s = (int)(i / ((size_t)WV * P));
-        const int n0 = s * PCLIP_VPT_SLICE, n1 = n0 + PCLIP_VPT_SLICE < B ? n0 + PCLIP_VPT_SLICE : B;
-        half_t* src = g + ((size_t)n0 * L + off + j) * W + d;
-        half8_t v = ld_half8(src);
-        if (clear) st_half8(src, zero);
-        float acc[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) acc[k] = (float)v[k];
-        for (int n = n0 + 1; n < n1; ++n) {
-            src += (size_t)L * W;
-            v = ld_half8(src);
-            if (clear) st_half8(src, zero);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) acc[k] += (float)v[k];
-        }
-        float4_t* dst = reinterpret_cast<float4_t*>(part + ((size_t)s * P + j) * W + d);
-        float4_t o0, o1;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { o0[k] = acc[k]; o1[k] = acc[4 + k]; }
-        dst[0] = o0;
-        dst[1] = o1;
-    }
-}
-
-// out[i] = (..(part[0][i] + part[1][i]) + ..) + part[nslice - 1][i], four elements per thread (M % 4 == 0)
-__global__ __launch_bounds__(256) void rows_grad_sum_kernel(const float* __restrict__ part, int nslice, size_t M, float* __restrict__ out) {
-    const size_t nvec = M / 4;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (size_t)gridDim.x * 256) {
-        float4_t acc = reinterpret_cast<const float4_t*>(part)[i];
-#pragma unroll 8
-        for (int s = 1; s < nslice; ++s) {
-            const float4_t v = reinterpret_cast<const float4_t*>(part + (size_t)s * M)[i];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) acc[k] += v[k];
-        }
-        reinterpret_cast<float4_t*>(out)[i] = acc;
-    }
-}
-
 // the envelope both row entries share; 0 = fine
 int rows_envelope(const char* who, int B, int L, int off, int P, int W) {
     PCLIP_REQUIRE(W > 0 && W % 8 == 0, "%s: W=%d must be a positive multiple of 8 (16-byte vectors)", who, W);
@@ -280,8 +198,7 @@ extern "C" int pclip_rows_replace_f16(void* x, const float* ctx, int B, int L, i
     if (int rc = rows_envelope("pclip_rows_replace_f16", B, L, off, P, W)) return rc;
     PCLIP_REQUIRE((((uintptr_t)x | (uintptr_t)ctx) & 15) == 0, "pclip_rows_replace_f16: operands must be 16-byte aligned");
     if (B == 0) return PCLIP_OK;
-    rows_replace_kernel<<<flat_grid((size_t)B * P * (W / 8)), 256, 0, (hipStream_t)stream>>>((half_t*)x, ctx, B, L, off, P, W);
-    return pclip_check_launch("rows_replace");
+    return rows_replace("rows_replace", x, ctx, B, L, off, P, W, stream);
 }
 
 extern "C" int pclip_rows_grad_f32(void* g, int B, int L, int off, int P, int W, int clear, float* dctx, float* part, int nslice, pclip_stream_t stream) {
@@ -292,11 +209,7 @@ extern "C" int pclip_rows_grad_f32(void* g, int B, int L, int off, int P, int W,
     const int want = (B + PCLIP_VPT_SLICE - 1) / PCLIP_VPT_SLICE;
     PCLIP_REQUIRE(nslice == want, "pclip_rows_grad_f32: nslice=%d, expected ceil(B / %d) = %d", nslice, PCLIP_VPT_SLICE, want);
     PCLIP_REQUIRE(nslice == 1 || part, "pclip_rows_grad_f32: %d sequence slices need the part buffer", nslice);
-    hipStream_t s = (hipStream_t)stream;
-    rows_grad_part_kernel<<<flat_grid((size_t)nslice * P * (W / 8)), 256, 0, s>>>((half_t*)g, B, L, off, P, W, clear ? 1 : 0, nslice,
-                                                                                  nslice == 1 ? dctx : part);
-    if (nslice > 1) rows_grad_sum_kernel<<<flat_grid((size_t)P * W / 4), 256, 0, s>>>(part, nslice, (size_t)P * W, dctx);
-    return pclip_check_launch("rows_grad");
+    return rows_grad<PCLIP_VPT_SLICE>("rows_grad", g, B, L, off, P, P, W, clear, nslice == 1 ? dctx : part, nslice, dctx, stream);
 }
 
 extern "C" int pclip_couple_fwd_f32(const float* X, const float* Wc, const float* bc, int depth, int P, int Wt, int Wv, float* Y, pclip_stream_t stream) {

@@ -4,33 +4,12 @@
 //
 // Shapes: a sequence has L = L0 + P rows, L0 stem rows (class + patches) followed by P prompt rows; B sequences; the stream is [B * L, W] fp16.
 //
-// Rounding points
-//   append / replace: a prompt element is rounded ONCE, fp32 -> fp16, round to nearest even (r16); nothing is added to it (no positional embedding on a
-//                     prompt row).  Stem rows are copied bit for bit (append) or not touched (replace).
-//   gradient:         f32(fp16) is exact; every `+` below is one rounded fp32 addition; nothing is rounded to fp16.  The rounding of the prompt to fp16
-//                     is passed straight through (as autograd passes a cast).
-//
-// Summation order of the gradient, dctx[j][d] over the B sequences (`images`):
-//   the images are cut into slices of PCLIP_VPT_SLICE = 16 consecutive images (the last one may be short); n0 = 16 s;
-//   part[s][j][d] = (..((f32(g[n0, L0 + j, d]) + f32(g[n0 + 1, L0 + j, d])) + f32(g[n0 + 2, L0 + j, d])) + ..)     ascending image order, one accumulator
-//   dctx[j][d]    = (..((part[0][j][d] + part[1][j][d]) + part[2][j][d]) + ..)                                      ascending slice order, one accumulator
-//   each sum starts from its first term (no zero is added).  One slice: part is dctx itself.
-// This is the rule pclip_prompt_ctx_grad_f32 (pclip_prompt.hip) uses for classes.
-// clear = 1: the same pass stores exact zeros (+0) over the prompt rows of g it has read — the lane that loaded a vector stores the zeros over it, after
-// its load, so no element is cleared before it is read.  Rows l < L0 are neither read nor written.
-#include "pclip_common.h"
+// Rounding points, the summation order of the gradient and `clear`: pclip_rows.h, whose replace and slice-sum walk these entries are at off = L0,
+// L = L0 + P.  append: a prompt element is rounded once (r16), nothing is added to it (no positional embedding on a prompt row); stem rows are copied bit
+// for bit.
+#include "pclip_rows.h"
 
 namespace {
-inline int flat_grid(size_t n) { size_t g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g)); }
-
-__device__ __forceinline__ half8_t r16_row8(const float* __restrict__ c) {
-    const float4_t c0 = reinterpret_cast<const float4_t*>(c)[0], c1 = reinterpret_cast<const float4_t*>(c)[1];
-    half8_t a;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { a[j] = (half_t)c0[j]; a[4 + j] = (half_t)c1[j]; }
-    return a;
-}
-
 // out[b, l, :] = t[b, l, :] for l < L0, r16(ctx[l - L0, :]) for L0 <= l < L0 + P
 __global__ __launch_bounds__(256) void vpt_append_kernel(const half_t* __restrict__ t, const float* __restrict__ ctx, int B, int L0, int P, int W,
                                                          half_t* __restrict__ out) {
@@ -43,67 +22,6 @@ __global__ __launch_bounds__(256) void vpt_append_kernel(const half_t* __restric
         const size_t b = row / L;
         const half8_t v = l < L0 ? ld_half8(t + (b * L0 + l) * W + d) : r16_row8(ctx + (size_t)(l - L0) * W + d);
         st_half8(out + row * W + d, v);
-    }
-}
-
-// x[b, L0 + j, :] = r16(ctx[j, :]); the other rows are not touched
-__global__ __launch_bounds__(256) void vpt_replace_kernel(half_t* __restrict__ x, const float* __restrict__ ctx, int B, int L0, int P, int W) {
-    const int WV = W / 8, L = L0 + P;
-    const size_t nvec = (size_t)B * P * WV;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (size_t)gridDim.x * 256) {
-        const int d = (int)(i % WV) * 8;
-        const int j = (int)((i / WV) % P);
-        const size_t b = i / ((size_t)WV * P);
-        st_half8(x + (b * L + L0 + j) * W + d, r16_row8(ctx + (size_t)j * W + d));
-    }
-}
-
-// first stage: one thread per (slice, prompt row, 8 columns) walks its slice's images in ascending order
-__global__ __launch_bounds__(256) void vpt_grad_part_kernel(half_t* __restrict__ g, int B, int L0, int P, int W, int clear, int nslice,
-                                                            float* __restrict__ part) {
-    const int WV = W / 8, L = L0 + P;
-    const size_t nvec = (size_t)nslice * P * WV;
-    half8_t zero;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) zero[k] = (half_t)0.f;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (size_t)gridDim.x * 256) {
-        const int d = (int)(i % WV) * 8;
-        const int j = (int)((i / WV) % P);
-        const int s = (int)(i / ((size_t)WV * P));
-        const int n0 = s * PCLIP_VPT_SLICE, n1 = n0 + PCLIP_VPT_SLICE < B ? n0 + PCLIP_VPT_SLICE : B;
-        half_t* src = g + ((size_t)n0 * L + L0 + j) * W + d;
-        half8_t v = ld_half8(src);
-        if (clear) st_half8(src, zero);
-        float acc[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) acc[k] = (float)v[k];
-        for (int n = n0 + 1; n < n1; ++n) {
-            src += (size_t)L * W;
-            v = ld_half8(src);
-            if (clear) st_half8(src, zero);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) acc[k] += (float)v[k];
-        }
-        float4_t* dst = reinterpret_cast<float4_t*>(part + ((size_t)s * P + j) * W + d);
-        float4_t o0, o1;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { o0[k] = acc[k]; o1[k] = acc[4 + k]; }
-        dst[0] = o0;
-        dst[1] = o1;
-    }
-}
-
-// out[i] = (..(part[0][i] + part[1][i]) + ..) + part[nslice - 1][i], four elements per thread (M % 4 == 0)
-__global__ __launch_bounds__(256) void vpt_grad_sum_kernel(const float* __restrict__ part, int nslice, size_t M, float* __restrict__ out) {
-    const size_t nvec = M / 4;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (size_t)gridDim.x * 256) {
-        float4_t acc = reinterpret_cast<const float4_t*>(part)[i];
-        for (int s = 1; s < nslice; ++s) {
-            const float4_t v = reinterpret_cast<const float4_t*>(part + (size_t)s * M)[i];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) acc[k] += v[k];
-        }
-        reinterpret_cast<float4_t*>(out)[i] = acc;
     }
 }
 
@@ -133,8 +51,7 @@ extern "C" int pclip_vpt_replace_f16(void* x, const float* ctx, int B, int L0, i
     if (int rc = vpt_envelope("pclip_vpt_replace_f16", B, L0, P, W)) return rc;
     PCLIP_REQUIRE((((uintptr_t)x | (uintptr_t)ctx) & 15) == 0, "pclip_vpt_replace_f16: operands must be 16-byte aligned");
     if (B == 0) return PCLIP_OK;
-    vpt_replace_kernel<<<flat_grid((size_t)B * P * (W / 8)), 256, 0, (hipStream_t)stream>>>((half_t*)x, ctx, B, L0, P, W);
-    return pclip_check_launch("vpt_replace");
+    return rows_replace("vpt_replace", x, ctx, B, L0 + P, L0, P, W, stream);
 }
 
 extern "C" int pclip_vpt_grad_f32(void* g, int B, int L0, int P, int W, int clear, float* dctx, float* part, int nslice, pclip_stream_t stream) {
@@ -145,8 +62,5 @@ extern "C" int pclip_vpt_grad_f32(void* g, int B, int L0, int P, int W, int clea
     const int want = (B + PCLIP_VPT_SLICE - 1) / PCLIP_VPT_SLICE;
     PCLIP_REQUIRE(nslice == want, "pclip_vpt_grad_f32: nslice=%d, expected ceil(B / %d) = %d", nslice, PCLIP_VPT_SLICE, want);
     PCLIP_REQUIRE(nslice == 1 || part, "pclip_vpt_grad_f32: %d image slices need the part buffer", nslice);
-    hipStream_t s = (hipStream_t)stream;
-    vpt_grad_part_kernel<<<flat_grid((size_t)nslice * P * (W / 8)), 256, 0, s>>>((half_t*)g, B, L0, P, W, clear ? 1 : 0, nslice, nslice == 1 ? dctx : part);
-    if (nslice > 1) vpt_grad_sum_kernel<<<flat_grid((size_t)P * W / 4), 256, 0, s>>>(part, nslice, (size_t)P * W, dctx);
-    return pclip_check_launch("vpt_grad");
+    return rows_grad<PCLIP_VPT_SLICE>("vpt_grad", g, B, L0 + P, L0, P, P, W, clear, nslice == 1 ? dctx : part, nslice, dctx, stream);
 }

@@ -14,7 +14,6 @@ text_blocks=m)` composes with it.  depth = 1 is CoOp's context with a coupled sh
 Envelope: transformer towers of head dimension 64, fp32 parameters, 1 <= n_ctx <= 16 (the coupling kernel's rows per depth), 1 <= depth <= min(vision
 layers, text layers), L0 + n_ctx <= 288 vision tokens, text width a multiple of 64, context shared by the classes.  Not here: CoCoOp's meta-net (an
 image-conditioned context), PromptSRC's regularisers, a per-class (class-specific) context."""
-import numpy as np
 import torch
 
 from . import autograd as pag
@@ -22,6 +21,7 @@ from . import ops
 from . import utils
 from ._lib import COUPLE_MAX_P, VPT_MAX_L, PclipError
 from .coop import PromptLearner
+from .prompt_train import accuracy, train_prompts
 from .tower import run_tower
 from .vpt import VisualPromptLearner
 
@@ -181,10 +181,6 @@ class MaPLe(torch.nn.Module):
             return utils.clip_zero_shot(feats, self.text_rows(), scale=float(self.logit_scale()), topk=topk, layout="nd")
 
 
-def _acc(pred, labels):
-    return 100.0 * float((pred == labels.to(pred.device).long()).sum().item()) / labels.shape[0]
-
-
 def run_maple(cfg, train_images, train_labels, classnames, clip_model, test_images=None, test_labels=None, learner=None, tokenize=None,
               tokenized_prompts=None):
     """Train multi-modal prompts on pre-processed image tensors ([Q, 3, R, R]) and labels with the recipe of MaPLe's code base: SGD on the three tensors,
@@ -202,38 +198,10 @@ def run_maple(cfg, train_images, train_labels, classnames, clip_model, test_imag
     elif learner.clip_model is not clip_model:
         raise PclipError("run_maple: the learner belongs to another CLIP model")
     model = MaPLe(clip_model, learner)
-    epochs, batch = int(cfg["maple_epochs"]), int(cfg.get("maple_batch", 4))
-    Q = train_images.shape[0]
-    steps = (Q + batch - 1) // batch
-    optimizer = torch.optim.SGD(learner.parameters(), lr=cfg.get("maple_lr", 0.0035), momentum=cfg.get("maple_momentum", 0.9))
-    scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, max(1, epochs * steps))
-    scaler = torch.amp.GradScaler("cuda", init_scale=float(cfg.get("maple_loss_scale", 1024.0)))
-    train_labels = train_labels.to(train_images.device).long()
-    res = {"epochs": []}
-    if test_images is not None:
-        res["start_test_acc"] = _acc(model.classify(test_images), test_labels)
-        print("\n**** MaPLe's test accuracy before training: {:.2f}. ****\n".format(res["start_test_acc"]))
-    g = torch.Generator().manual_seed(seed)
-    epoch_losses = []
-    for epoch in range(epochs):
-        print("Train Epoch: {:} / {:}".format(epoch, epochs))
-        order = torch.randperm(Q, generator=g).to(train_images.device)
-        losses = []
-        for s in range(steps):
-            idx = order[s * batch:(s + 1) * batch]
-            loss = model.loss(train_images[idx].contiguous(), train_labels[idx])
-            optimizer.zero_grad()
-            scaler.scale(loss).backward()
-            scaler.step(optimizer)
-            scaler.update()
-            scheduler.step()
-            losses.append(float(loss.detach()))
-        epoch_losses.append(float(np.mean(losses)))
-        print("LR: {:.6f}, Loss: {:.4f}".format(scheduler.get_last_lr()[0], epoch_losses[-1]))
-        rec = {"loss": epoch_losses[-1]}
-        if test_images is not None:
-            rec["test_acc"] = _acc(model.classify(test_images), test_labels)
-            print("**** MaPLe's test accuracy: {:.2f}. ****\n".format(rec["test_acc"]))
-        res["epochs"].append(rec)
-    learner.results = res
+    labels = train_labels.to(train_images.device).long()
+    evaluate = None if test_images is None else lambda: accuracy(model.classify(test_images), test_labels)
+    learner.results, epoch_losses = train_prompts(
+        "MaPLe", learner.parameters(), lambda idx: model.loss(train_images[idx].contiguous(), labels[idx]), train_images.shape[0], train_images.device,
+        epochs=int(cfg["maple_epochs"]), batch=int(cfg.get("maple_batch", 4)), lr=cfg.get("maple_lr", 0.0035), momentum=cfg.get("maple_momentum", 0.9),
+        loss_scale=cfg.get("maple_loss_scale", 1024.0), seed=seed, evaluate=evaluate)
     return learner, epoch_losses

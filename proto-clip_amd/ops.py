@@ -1161,8 +1161,8 @@ def prompt_embed(ctx, tokens, tok_emb, pos_emb, L_out: int = None) -> torch.Tens
 
 
 def prompt_ctx_grad(dx, N: int, L_out: int, n_ctx: int, class_specific: bool = False) -> torch.Tensor:
-    """Gradient of `prompt_embed` wrt the context from dx [N * L_out, W] fp16: fp32 [n_ctx, W] (summed over the classes in one fixed order) or, class
-    specific, [N, n_ctx, W] (pclip_prompt_ctx_grad_f32)."""
+    """Gradient of `prompt_embed` wrt the context from dx [N * L_out, W] fp16: fp32 [n_ctx, W] (summed over the classes by the slice-sum rule, `rows_grad`
+    at off = 1) or, class specific, [N, n_ctx, W] (pclip_prompt_ctx_grad_f32).  A context row at 1 + j >= L_out is not read: its gradient is 0."""
     require_cuda(dx)
     dx = _f16c(dx)
     W = dx.shape[1]
@@ -1207,7 +1207,7 @@ def vpt_append(t, ctx, B: int, L0: int) -> torch.Tensor:
 
 def vpt_replace_(x, ctx, B: int, L0: int) -> torch.Tensor:
     """In place on the stream x [B * (L0 + P), W] fp16: the last P rows of every sequence become the fp32 rows ctx [P, W] rounded once to fp16
-    (pclip_vpt_replace_f16).  Returns x."""
+    (pclip_vpt_replace_f16): `rows_replace_` at L = L0 + P, off = L0.  Returns x."""
     require_cuda(x, ctx)
     W = x.shape[-1]
     ctx = _vpt_ctx("vpt_replace_", ctx, W)
@@ -1220,8 +1220,8 @@ def vpt_replace_(x, ctx, B: int, L0: int) -> torch.Tensor:
 
 def vpt_grad(g, B: int, L0: int, P: int, clear: bool = False) -> torch.Tensor:
     """fp32 [P, W]: the prompt rows (L0 .. L0 + P - 1 of every sequence) of the gradient stream g [B * (L0 + P), W] fp16 summed over the B sequences
-    in pclip_vpt_grad_f32's fixed order (slices of 16 images, then the slices).  L0 == 0: g is a compact [B * P, W].  clear: the pass also writes
-    exact zeros over those rows of g, IN PLACE — the rows of a replaced deep prompt pass no gradient to the block below."""
+    by the slice-sum rule (`rows_grad` at L = L0 + P, off = L0; pclip_vpt_grad_f32).  L0 == 0: g is a compact [B * P, W].  clear: the pass also writes
+    exact zeros over those rows of g, IN PLACE."""
     require_cuda(g)
     if g.dtype != torch.float16 or not g.is_contiguous() or g.dim() != 2 or g.shape[0] != B * (L0 + P):
         raise _lib.PclipError(f"vpt_grad: g {g.dtype} {tuple(g.shape)} is not a contiguous float16 [B * (L0 + P), W] with B={B}, L0={L0}, P={P}")
@@ -1243,7 +1243,8 @@ def _rows_window(who: str, t, B: int, L: int, off: int, P: int):
 
 def rows_replace_(x, ctx, B: int, L: int, off: int) -> torch.Tensor:
     """In place on the stream x [B * L, W] fp16: rows off .. off + P - 1 of every sequence become the fp32 rows ctx [P, W] rounded once to fp16
-    (pclip_rows_replace_f16); every other row keeps its bits.  Returns x.  off = L - P is `vpt_replace_`."""
+    (pclip_rows_replace_f16); every other row keeps its bits.  Returns x.  The deep-prompt pack of the taped tower (autograd.TowerTailFn) goes through
+    this entry for either tower; off = L - P is `vpt_replace_`."""
     require_cuda(x, ctx)
     W = x.shape[-1]
     ctx = _vpt_ctx("rows_replace_", ctx, W)
@@ -1255,9 +1256,10 @@ def rows_replace_(x, ctx, B: int, L: int, off: int) -> torch.Tensor:
 
 
 def rows_grad(g, B: int, L: int, off: int, P: int, clear: bool = False) -> torch.Tensor:
-    """fp32 [P, W]: rows off .. off + P - 1 of every sequence of the gradient stream g [B * L, W] fp16 summed over the B sequences in
-    pclip_vpt_grad_f32's fixed order (pclip_rows_grad_f32).  clear: the pass also writes exact zeros over those rows of g, IN PLACE; rows outside
-    the window are neither read nor written.  off = L - P is `vpt_grad`."""
+    """fp32 [P, W]: rows off .. off + P - 1 of every sequence of the gradient stream g [B * L, W] fp16 summed over the B sequences by the slice-sum rule
+    (pclip_rows_grad_f32; include/pclip.h states the rule: slices of 16 sequences in ascending order, then the slices in ascending order, fp32).  clear: the
+    pass also writes exact zeros over those rows of g, IN PLACE — the rows of a replaced deep prompt pass no gradient to the block below; rows outside the
+    window are neither read nor written.  off = L - P is `vpt_grad`."""
     require_cuda(g)
     B, L, off, P = int(B), int(L), int(off), int(P)
     _rows_window("rows_grad: g", g, B, L, off, P)

@@ -161,7 +161,8 @@ def run_tower(tw, x, B, L, plan, pick, what=None, h0=None, deep=None, deep_off=N
     blocks[:first] run frozen, blocks[first:] + final LayerNorm + projection on the tape (autograd.run_tower_tail; only the heads when
     first == len(blocks): the frozen walk then keeps its class-row shortcut); first None: nothing is taped — the frozen walk, ln(picked row)
     (row-wise: commutes with the pick) and the projection GEMM.  pick = (select, rows) from `tw.pick`; h0: ln_1(x) of block 0 when the stem
-    produced it (dropped when a frozen prefix runs first); what: the pass in the words of a refusal (default `tw.what`); deep, deep_off: TowerTailFn's."""
+    produced it (dropped when a frozen prefix runs first); what: the pass in the words of a refusal (default `tw.what`); deep, deep_off: TowerTailFn's pack of
+    deep prompt rows and the first of its rows in a sequence (None: the last rows, which run_tower_tail resolves to L - P)."""
     first, stem = plan
     select, _ = pick
     if first is None:

@@ -17,13 +17,13 @@ Envelope: transformer towers of head dimension 64, fp32 `ctx`, L0 + P <= 288 tok
 tower has 577 tokens of its own and is refused).  Not here: prompts directly behind the class token (Jia et al.'s order), a positional embedding on the
 prompts, VPT beside a trainable stem (`unfreeze(stem=...)`).  MaPLe's coupling function lives in `maple.py`; an explicit `ctx` tensor on the tape is all
 it needs from this module."""
-import numpy as np
 import torch
 
 from . import autograd as pag
 from . import ops
 from . import utils
 from ._lib import PclipError, VPT_MAX_L
+from .prompt_train import accuracy, train_prompts
 from .tower import run_tower, vit_stem
 
 
@@ -132,10 +132,6 @@ class VPT(torch.nn.Module):
             return utils.clip_zero_shot(feats, rows, scale=float(self.logit_scale()), topk=topk, layout="nd")
 
 
-def _acc(pred, labels):
-    return 100.0 * float((pred == labels.to(pred.device).long()).sum().item()) / labels.shape[0]
-
-
 def run_vpt(cfg, train_images, train_labels, clip_weights, clip_model, test_images=None, test_labels=None, learner=None):
     """Train visual prompts on pre-processed image tensors ([Q, 3, R, R]) and labels against fixed class weights, with the optimiser and schedule choices
     of `coop.run_coop`: SGD on `ctx`, learning rate 0.002, momentum 0.9, cosine schedule, batches of 32, cfg['vpt_epochs'] epochs, cfg['n_ctx'] prompt
@@ -150,38 +146,10 @@ def run_vpt(cfg, train_images, train_labels, clip_weights, clip_model, test_imag
     elif learner.clip_model is not clip_model:
         raise PclipError("run_vpt: the learner belongs to another CLIP model")
     model = VPT(clip_model, learner)
-    epochs, batch = int(cfg["vpt_epochs"]), int(cfg.get("vpt_batch", 32))
-    Q = train_images.shape[0]
-    steps = (Q + batch - 1) // batch
-    optimizer = torch.optim.SGD(learner.parameters(), lr=cfg.get("vpt_lr", 0.002), momentum=cfg.get("vpt_momentum", 0.9))
-    scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, max(1, epochs * steps))
-    scaler = torch.amp.GradScaler("cuda", init_scale=float(cfg.get("vpt_loss_scale", 1024.0)))
-    train_labels = train_labels.to(train_images.device).long()
-    res = {"epochs": []}
-    if test_images is not None:
-        res["start_test_acc"] = _acc(model.classify(test_images, clip_weights), test_labels)
-        print("\n**** VPT's test accuracy before training: {:.2f}. ****\n".format(res["start_test_acc"]))
-    g = torch.Generator().manual_seed(seed)
-    epoch_losses = []
-    for epoch in range(epochs):
-        print("Train Epoch: {:} / {:}".format(epoch, epochs))
-        order = torch.randperm(Q, generator=g).to(train_images.device)
-        losses = []
-        for s in range(steps):
-            idx = order[s * batch:(s + 1) * batch]
-            loss = model.loss(train_images[idx].contiguous(), clip_weights, train_labels[idx])
-            optimizer.zero_grad()
-            scaler.scale(loss).backward()
-            scaler.step(optimizer)
-            scaler.update()
-            scheduler.step()
-            losses.append(float(loss.detach()))
-        epoch_losses.append(float(np.mean(losses)))
-        print("LR: {:.6f}, Loss: {:.4f}".format(scheduler.get_last_lr()[0], epoch_losses[-1]))
-        rec = {"loss": epoch_losses[-1]}
-        if test_images is not None:
-            rec["test_acc"] = _acc(model.classify(test_images, clip_weights), test_labels)
-            print("**** VPT's test accuracy: {:.2f}. ****\n".format(rec["test_acc"]))
-        res["epochs"].append(rec)
-    learner.results = res
+    labels = train_labels.to(train_images.device).long()
+    evaluate = None if test_images is None else lambda: accuracy(model.classify(test_images, clip_weights), test_labels)
+    learner.results, epoch_losses = train_prompts(
+        "VPT", learner.parameters(), lambda idx: model.loss(train_images[idx].contiguous(), clip_weights, labels[idx]), train_images.shape[0],
+        train_images.device, epochs=int(cfg["vpt_epochs"]), batch=int(cfg.get("vpt_batch", 32)), lr=cfg.get("vpt_lr", 0.002),
+        momentum=cfg.get("vpt_momentum", 0.9), loss_scale=cfg.get("vpt_loss_scale", 1024.0), seed=seed, evaluate=evaluate)
     return learner, epoch_losses

@@ -49,6 +49,12 @@ def _prompt_ctx_grad(a):
     return _z(*((a["N"], a["n_ctx"], W) if a["class_specific"] else (a["n_ctx"], W)), dtype=F32)
 
 
+def _couple_backward(a):
+    (depth, P, Wt), Wv = a["x"].shape, a["weight"].shape[1]
+    return (_z(depth, P, Wt, dtype=F32) if a["want_x"] else None, _z(depth, Wv, Wt, dtype=F32) if a["want_weight"] else None,
+            _z(depth, Wv, dtype=F32) if a["want_bias"] else None)
+
+
 def _vit_embed_backward(a):
     W = a["dt"].shape[-1]
     return (_z(a["L"], W, dtype=F32) if a["want_pos"] else None, _z(a["B"] * (a["L"] - 1), W) if a["want_patch"] else None)
@@ -76,6 +82,10 @@ STUBS = {
     "vpt_append": lambda a: _z(a["B"] * (a["L0"] + a["ctx"].shape[0]), a["ctx"].shape[-1]),
     "vpt_replace_": lambda a: a["x"],
     "vpt_grad": lambda a: _z(a["P"], a["g"].shape[1], dtype=F32),
+    "rows_replace_": lambda a: a["x"],
+    "rows_grad": lambda a: _z(a["P"], a["g"].shape[1], dtype=F32),
+    "couple": lambda a: _z(a["x"].shape[0], a["x"].shape[1], a["weight"].shape[1], dtype=F32),
+    "couple_backward": _couple_backward,
     "transpose": lambda a: _z(a["x"].shape[1], a["x"].shape[0]),
     "cast_f16": lambda a: _z(*a["x"].shape),
     "colsum_f16": lambda a: _z(a["x"].shape[1], dtype=F32),

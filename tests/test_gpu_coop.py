@@ -64,6 +64,21 @@ def test_kernels_match_the_cpu_restatement_bit_for_bit(W, class_specific):
                 assert torch.equal(again, got)
 
 
+def test_context_gradient_is_the_row_walk_at_offset_one():
+    """pclip_prompt_ctx_grad_f32 and pclip_rows_grad_f32 are one walk (csrc/pclip_rows.h): the shared context's gradient has the bits of `rows_grad` at
+    off = 1, the class-specific one is the rows themselves, and neither writes the stream.  N = 1, 16, 17, 33: one slice, a full slice, one and two slice
+    boundaries crossed; W = 72 is no multiple of 64."""
+    from proto_clip_amd import ops
+    L_out, n_ctx, W = 6, 4, 72
+    g = torch.Generator().manual_seed(72)
+    for N in (1, 16, 17, 33):
+        dx = torch.randn(N * L_out, W, generator=g).half().cuda()
+        before = dx.clone()
+        assert torch.equal(ops.prompt_ctx_grad(dx, N, L_out, n_ctx), ops.rows_grad(dx, N, L_out, 1, n_ctx)), N
+        assert torch.equal(ops.prompt_ctx_grad(dx, N, L_out, n_ctx, class_specific=True), dx.view(N, L_out, W)[:, 1:1 + n_ctx].float()), N
+        assert torch.equal(dx, before), N
+
+
 def test_fp16_exact_context_rows_give_text_embed_bits():
     from proto_clip_amd import ops
     vocab, W, N, n_ctx = 300, 128, 9, 4

@@ -1,10 +1,12 @@
 """Every way the package runs a transformer tower, as small seeded cases behind public entry points only (encode_image / encode_text, unfreeze,
-ops.low_latency, coop.PromptLearner, vpt.VisualPromptLearner): the frozen pass, the low-latency pass, heads-only training, a taped tail behind a frozen
-prefix, the whole stack taped, the stem on the tape, learned text context, visual prompts, a tower without blocks.  Each case is a forward plus
+ops.low_latency, coop.PromptLearner, vpt.VisualPromptLearner, maple.MultiModalPromptLearner): the frozen pass, the low-latency pass, heads-only training,
+a taped tail behind a frozen prefix, the whole stack taped, the stem on the tape, learned text context, visual prompts, multi-modal prompts (either
+tower), a tower without blocks.  Each case is a forward plus
 `features.sum().backward()` wherever something requires grad and returns {"features": ..., "grad.<parameter>": ...}.
 
 Two consumers: tests/golden/make_golden_tower_trace.py records the sequence of `ops` calls of every case on the CPU (test_tower_trace_cpu.py), and
-tests/test_gpu_tower_pass.py compares the bits of every returned tensor with profiles/tower_pass_refactor.txt:
+tests/test_gpu_tower_pass.py compares the bits of every returned tensor with profiles/tower_pass_refactor.txt (the MaPLe cases:
+profiles/prompt_rows_refactor.txt):
 
     python tests/tower_pass_cases.py --digests          # on the GPU: the `digest KEY VALUE` lines of that file"""
 import contextlib
@@ -105,6 +107,21 @@ def _vpt_case(depth, taped):
     return run
 
 
+def _maple_case(depth, tower, taped):
+    def run(device, on_model=lambda named: None):
+        from proto_clip_amd import maple
+        model = make_model(TINY, 12, device)
+        images = make_images(TINY, device)
+        tokens = make_tokens(TINY, device, n_ctx=N_CTX)
+        learner = maple.MultiModalPromptLearner([f"class{i}" for i in range(N_TXT)], model, n_ctx=N_CTX, depth=depth, tokenized_prompts=tokens, seed=5)
+        named = {**dict(model.named_parameters()), "ctx": learner.ctx, "couple_weight": learner.couple_weight, "couple_bias": learner.couple_bias}
+        on_model({**named, "input": images if tower == "image" else tokens})
+        with torch.set_grad_enabled(taped):
+            feats = learner.image_features(images) if tower == "image" else learner.text_features()
+        return _result(feats, named)
+    return run
+
+
 def _no_blocks_case(heads):
     def run(device, on_model=lambda named: None):
         from proto_clip_amd.clip.model import build_model, random_state_dict
@@ -141,6 +158,10 @@ def cases(gpu_only=False):
     for depth in (1, 2):
         for taped in (True, False):
             out[f"vpt.tiny.depth{depth}.{'taped' if taped else 'nograd'}"] = _vpt_case(depth, taped)
+    for depth in (1, 2):
+        for tower in ("image", "text"):
+            for taped in (True, False):
+                out[f"maple.tiny.depth{depth}.{tower}.{'taped' if taped else 'nograd'}"] = _maple_case(depth, tower, taped)
     if not gpu_only:
         out["noblocks.tiny.image.frozen"] = _no_blocks_case(False)
         out["noblocks.tiny.image.heads"] = _no_blocks_case(True)

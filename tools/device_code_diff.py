@@ -7,7 +7,11 @@ Each directory holds one `hipcc --cuda-device-only -S` listing per translation u
 (pclip_train, pclip_tower_optim and pclip_preprocess with -ffp-contract=off, as there).  Kernels are matched by name through RENAMES (applied to the mangled
 name, length prefix included: no demangler that knows _Float16 ships with every ROCm); the kernel sets must be equal.  Per kernel it prints, and fails on: a change in the count of MFMA, vector-memory, LDS, barrier, transcendental or convert instructions;
 any scratch instruction, private segment or VGPR spill (but for a kernel whose every figure equals the parent's: it is the parent's kernel); a change of the LDS size; a change of the waves-per-SIMD step; a total instruction count more than
-1 % from the parent's.  Instructions are classified by the prefixes below and nothing else."""
+1 % from the parent's.  Instructions are classified by the prefixes below and nothing else.
+
+A kernel of the new build without a partner of its own name is compared with the parent's kernel that MOVED names for it, in the same listing (several
+copies folded into one shared kernel: many old names to one new one, and one old kernel may stand for several instantiations).  Such a pair passes the
+same gate but for the total, which is printed and not gated: a shared kernel carries the arguments of all its callers."""
 import os
 import re
 import sys
@@ -15,6 +19,11 @@ import sys
 CLASSES = {"mfma": ("v_mfma",), "vmem": ("global_", "buffer_", "flat_"), "lds": ("ds_",), "barrier": ("s_barrier",),
            "trans": ("v_exp", "v_rcp", "v_rsq", "v_sqrt", "v_log"), "cvt": ("v_cvt",), "scratch": ("scratch_",)}
 RENAMES = (("ce_transpose_kernel", "transpose_kernel"), ("logits_norm_rows_kernel", "norm_rows_kernel"), ("ce_norm_rows_kernel", "norm_rows_kernel"))
+# short new name -> the short names of the parent's kernels it replaces (csrc/pclip_rows.h: the prompt-row kernels of CoOp, VPT and MaPLe)
+MOVED = {"rows_replace_kernel": ("vpt_replace_kernel",),
+         "rows_grad_part_kernel<16>": ("prompt_ctx_grad_part_kernel", "vpt_grad_part_kernel", "rows_grad_part_kernel"),
+         "rows_grad_part_kernel<1>": ("prompt_ctx_grad_part_kernel",),
+         "rows_grad_sum_kernel": ("prompt_ctx_grad_sum_kernel", "vpt_grad_sum_kernel")}
 TOTAL_TOL = 0.01
 
 
@@ -65,18 +74,22 @@ def compare(parent_dir, new_dir, out=sys.stdout):
             p = os.path.join(d, unit)
             sides.append(parse(p) if os.path.exists(p) else {})
         old, new = {renamed(name): k for name, k in sides[0].items()}, sides[1]
-        for name in sorted(set(old) | set(new)):
+        moved = {}                                       # new name -> the parent's name it is compared with
+        for name in set(new) - set(old):
+            for was in (o for o in set(old) - set(new) if short(o) in MOVED.get(short(name), ())):
+                moved[name] = was
+        for name in sorted((set(old) | set(new)) - set(moved.values())):
             why = []
-            if name not in old or name not in new:
+            if name not in new or name not in old and name not in moved:
                 why.append("only in the %s build" % ("new" if name in new else "parent"))
             else:
-                o, n = old[name], new[name]
+                o, n = old[moved.get(name, name)], new[name]
                 why += ["%s %d -> %d" % (c, o[c], n[c]) for c in ("mfma", "vmem", "lds", "barrier", "trans", "cvt", "lds_bytes", "waves") if o[c] != n[c]]
                 why += ["%s %d" % (c, n[c]) for c in ("scratch", "private", "spill") if n[c] and o != n]
-                if abs(n["total"] - o["total"]) > TOTAL_TOL * o["total"]:
+                if name not in moved and abs(n["total"] - o["total"]) > TOTAL_TOL * o["total"]:
                     why.append("total beyond %g %%" % (100 * TOTAL_TOL))
-                print("%-22s %-36s total %5d -> %5d (%+.2f %%)  mfma %4d vmem %4d lds %4d bar %2d trans %3d cvt %3d  waves %d  %s" % (
-                    unit, short(name), o["total"], n["total"], 100.0 * (n["total"] - o["total"]) / o["total"], n["mfma"], n["vmem"], n["lds"], n["barrier"],
+                print("%-22s %-60s total %5d -> %5d (%+.2f %%)  mfma %4d vmem %4d lds %4d bar %2d trans %3d cvt %3d  waves %d  %s" % (
+                    unit, short(name) + (" <- " + short(moved[name]) if name in moved else ""), o["total"], n["total"], 100.0 * (n["total"] - o["total"]) / o["total"], n["mfma"], n["vmem"], n["lds"], n["barrier"],
                     n["trans"], n["cvt"], n["waves"], "same" if o == n else "ok" if not why else ""), file=out)
             if why:
                 bad += 1
