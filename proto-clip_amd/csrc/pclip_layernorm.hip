@@ -1,5 +1,18 @@
-// LayerNorm passes of the CLIP towers and adapters (clip/model.py:155-161; model.py:86-95): wave-per-row kernels with fp32 statistics, the whole-batch prefetching form,
-// row statistics / finalisation and the weight fold of the opt-in LayerNorm fold, the fused add + LayerNorm of the split-K serving path.
+// LayerNorm passes of the CLIP towers and adapters (clip/model.py:155-161; model.py:86-95): wave-per-row kernels with fp32 statistics (fp32 or fp16 affine, the
+// Adapter_FC blend with its optional row normalise), the whole-batch prefetching form with and without an LDS copy of gamma / beta, the residual add fused into the
+// LayerNorm that consumes it.
+//
+// ROUNDING POINTS (graded per element against float64 with the tolerance derived from them: tests/row_passes_ref.py, tests/test_gpu_row_passes.py).  Every kernel here,
+// ln_row_pf (pclip_encoder_common.h) and ln_row_inplace (pclip_stem.hip) compute one chain per row; NCH = 1, 2, 4, 8 chunks of 512 columns, lane l holds columns
+// c 512 + 8 l .. + 7, a lane beyond D adds exact zeros:
+//   s     8 NCH in-lane v_add_f32, then the six butterfly levels lane ^ 32 .. ^ 1: chains of n = 8 NCH + 6 additions
+//   mean  = s / D, the IEEE division (correctly rounded);  t = v - mean: one v_sub_f32
+//   q     += t t by fma (ln_sq_acc: one rounding per term), then the butterfly: n roundings
+//   rstd  = 1 / sqrtf(q / D + eps): a division, an addition, the correctly rounded square root (v_sqrt_f32 corrected by two fma residuals), a division
+//   o     = (t rstd) g + b: two rounded multiplies and a rounded add (ln_affine_dev, contraction off);  y = r16(o): one fp16 rounding
+// MODE 1 then rounds to fp16 at a = r16(ratio y), c = r16(omr res) (each ONE rounding of the product where the compiler emits v_fma_mixlo_f16) and r16(a + c)
+// (v_pk_add_f16); with l2norm, n = r16(sqrtf(sum of the exact squares, n additions)), z = r16(y / n) by the IEEE division — n = inf gives zeros —, sq_out = the fp32 sum of
+// the squares of the stored values.  add_layernorm's xs = r16(x + delta) is the correctly rounded sum of two fp16 values.
 #include "pclip_encoder_common.h"
 #include <stdlib.h>
 #include <type_traits>

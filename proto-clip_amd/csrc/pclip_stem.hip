@@ -182,16 +182,19 @@ __global__ __launch_bounds__(256) void text_embed_kernel(const int64_t* __restri
     }
 }
 
-// out[b] = x[b, argmax_l tokens[b, l]]  (first maximum, like torch.argmax)
+// out[b] = x[b, argmax_l tokens[b, l]]  (first maximum, like torch.argmax).  Every lane starts below any id (-inf), so a lane with a position accepts its first
+// token whatever its sign: a row of negative ids selects its first maximum too, and a lane without a position (l >= L) keeps (-inf, INT_MAX) and loses every
+// comparison of wave_argmax.  The index is clamped to the row before the copy all the same.
 __global__ __launch_bounds__(64) void gather_eot_kernel(const half_t* __restrict__ x, const int64_t* __restrict__ tokens,
                                                         int L, int W, half_t* __restrict__ out) {
     const int b = blockIdx.x, lane = threadIdx.x;
-    float bv = -1.f; int bi = 0x7fffffff;
+    float bv = -INFINITY; int bi = 0x7fffffff;
     for (int l = lane; l < L; l += 64) {
         const float t = (float)tokens[(size_t)b * L + l];
         if (t > bv) { bv = t; bi = l; }
     }
     wave_argmax(bv, bi);
+    bi = bi < 0 ? 0 : (bi > L - 1 ? L - 1 : bi);
     for (int d = lane * 8; d < W; d += 512) st_half8(out + (size_t)b * W + d, ld_half8(x + ((size_t)b * L + bi) * W + d));
 }
 

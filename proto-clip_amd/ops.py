@@ -715,16 +715,18 @@ def adapter_fc(x, w1, g1, b1, w2, g2, b2, ratio: float = 0.2, l2norm_out: bool =
     return (y, sq) if want_sq else y
 
 
-def layernorm_blend(h, gamma, beta, x, ratio: float = 0.2, l2norm_out: bool = False, eps: float = 1e-5):
-    """r16(r16(ratio * LN(h)) + r16((1 - ratio) * x)) — the last stage of Adapter_FC.forward (model.py:92-95) on its own."""
+def layernorm_blend(h, gamma, beta, x, ratio: float = 0.2, l2norm_out: bool = False, eps: float = 1e-5, want_sq: bool = False, out=None):
+    """r16(r16(ratio * LN(h)) + r16((1 - ratio) * x)) — the last stage of Adapter_FC.forward (model.py:92-95) on its own, optionally followed by the
+    row normalise.  want_sq (as adapter_fc's): also the fp32 squared norms of the rows as stored, (y, sq)."""
     require_cuda(h, gamma, beta, x)
     h, x = _f16c(h), _f16c(x)
     R, D = h.shape
-    y = torch.empty_like(h)
+    y = torch.empty_like(h) if out is None else out
+    sq = torch.empty(R, dtype=torch.float32, device=h.device) if want_sq else None
     r32, omr32 = float(np.float32(ratio)), float(np.float32(1 - ratio))
     check(_lib.load().pclip_layernorm_blend_f16(ptr(h), ptr(_f16c(gamma)), ptr(_f16c(beta)), eps, ptr(x), r32, omr32, int(l2norm_out),
-                                                ptr(y), None, R, D, stream()), "pclip_layernorm_blend_f16")
-    return y
+                                                ptr(y), ptr(sq), R, D, stream()), "pclip_layernorm_blend_f16")
+    return (y, sq) if want_sq else y
 
 
 ADAPTER_WIDTHS = (8, 16, 24, 32)      # conv adapter widths the kernels are instantiated for (csrc/pclip_adapter.hip: 16, pclip_adapter_w.hip: the rest)
