@@ -722,6 +722,37 @@ int pclip_couple_fwd_f32(const float* X, const float* Wc, const float* bc, int d
 int pclip_couple_bwd_f32(const float* dY, const float* X, const float* Wc, int depth, int P, int Wt, int Wv, float* dWc, float* dbc, float* dX,
                          float* part, int nslice, pclip_stream_t stream);
 
+/* ---- CoCoOp: the image-conditioned context (csrc/pclip_cocoop.hip lists every rounding point and summation order) ------------------------------- */
+
+/* The meta-net, fp32: h[b] = relu(W1 f[b] + b1), pi[b] = W2 h[b] + b2 for f [B, E] fp16 (already normalised; a constant), W1 [Hd, E], b1 [Hd],
+ * W2 [Wt, Hd], b2 [Wt]; outputs h [B, Hd] (kept for the backward) and pi [B, Wt], the per-image shift of the context rows.  Envelope:
+ * 1 <= B <= PCLIP_COCOOP_MAX_B, E % 64 == 0, Hd % 4 == 0, 4 <= Hd <= 256, Wt % 8 == 0, operands 16-byte aligned.  Products and additions are rounded
+ * separately (no fused multiply-add) in the one order the source file documents; the biases are added last.  Two launches. */
+#define PCLIP_COCOOP_MAX_B 16
+int pclip_metanet_fwd_f32(const void* f, const float* W1, const float* b1, const float* W2, const float* b2, int B, int E, int Hd, int Wt, float* h,
+                          float* pi, pclip_stream_t stream);
+
+/* Gradients of the meta-net from dpi [B, Wt]: dW2 = dpi^T h, db2 = sum_b dpi[b], dpre = (dpi W2) masked by h > 0, dW1 = dpre^T f, db1 = sum_b dpre[b];
+ * sums over b ascend in one accumulator; f gets no gradient.  Each output is optional (NULL: not computed, nothing launched for it; h may be NULL
+ * without dW2 / dW1 / db1, f without dW1, W2 without dW1 / db1).  dpre [B, Hd] fp32 is the workspace dW1 and db1 need (may be NULL without them).
+ * The envelope of the forward.  At most three launches. */
+int pclip_metanet_bwd_f32(const float* dpi, const void* f, const float* h, const float* W2, int B, int E, int Hd, int Wt, float* dW1, float* db1,
+                          float* dW2, float* db2, float* dpre, pclip_stream_t stream);
+
+/* pclip_prompt_embed_f16 with context rows that differ per image and are shared by that image's N classes: x [B * N, L_out, W] fp16,
+ * x[b * N + n, l] = r16(f32(src) + f32(pos_emb[l])), src = r16(ctx[l - 1] + pi[b]) for 1 <= l <= n_ctx (one rounded fp32 addition, then the rounding to
+ * fp16) and tok_emb[clamp(tokens[n, l], 0, vocab - 1)] elsewhere.  ctx fp32 [n_ctx, W], pi fp32 [B, W], tokens int64 [N, L_tok] shared by the images,
+ * L_out <= L_tok.  Envelope: 1 <= B <= PCLIP_COCOOP_MAX_B, N >= 1, n_ctx >= 1, W % 8 == 0, B * N * L_out within an int, operands 16-byte aligned. */
+int pclip_prompt_embed_cond_f16(const int64_t* tokens, int L_tok, const void* tok_emb, const void* pos_emb, const float* ctx, const float* pi, int n_ctx,
+                                int B, int N, int L_out, int W, int vocab, void* x, pclip_stream_t stream);
+
+/* Gradient of that assembly from dx [B * N * L_out, W] fp16 (read only): dshift [B, n_ctx, W] = the slice-sum rule above at off = 1 applied to the N
+ * prompts of every image (nslice = ceil(N / PCLIP_PROMPT_CTX_SLICE); part [B][nslice][n_ctx * W] fp32, may be NULL when nslice == 1), dctx [n_ctx, W] =
+ * the sum of dshift over b ascending from b = 0, dpi [B, W] = the sum of dshift over j ascending over the rows that exist (1 + j < L_out; the others
+ * are not read and their dshift is +0).  The envelope of the assembly.  Two launches: the grouped partials and one finishing pass. */
+int pclip_prompt_cond_grad_f32(const void* dx, int B, int N, int L_out, int n_ctx, int W, float* dshift, float* dctx, float* dpi, float* part, int nslice,
+                               pclip_stream_t stream);
+
 /* ---- backward of the embedding stages in front of block 0 (whole-tower fine-tuning; csrc/pclip_embed_bwd.hip lists every rounding) ---------- */
 
 /* Envelope of both entry points: B >= 1, 1 <= L <= 4096, W % 64 == 0, W <= 2048 (and V >= 1); operands 16-byte aligned.  fp32 accumulation, no atomics:

@@ -11,3 +11,5 @@ from . import tip_adapter  # noqa: F401,E402  (the Tip-Adapter / Tip-Adapter-F b
 from . import vpt  # noqa: F401,E402  (visual prompt tuning through the frozen vision tower: VisualPromptLearner, VPT, run_vpt)
 from . import maple  # noqa: F401,E402  (multi-modal prompt learning, deep text prompts coupled to VPT: MultiModalPromptLearner, MaPLe, run_maple)
 from .maple import MaPLe, MultiModalPromptLearner, run_maple  # noqa: F401,E402
+from . import cocoop  # noqa: F401,E402  (the image-conditioned context: ConditionalPromptLearner, CoCoOp, run_cocoop)
+from .cocoop import CoCoOp, ConditionalPromptLearner, run_cocoop  # noqa: F401,E402

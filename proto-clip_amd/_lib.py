@@ -29,6 +29,7 @@ EMBED_BWD_CHUNK = 128                                      # PCLIP_EMBED_BWD_CHU
 PROMPT_CTX_SLICE = 16                                      # PCLIP_PROMPT_CTX_SLICE: classes per slice of pclip_prompt_ctx_grad_f32's first stage
 VPT_SLICE, VPT_MAX_L = 16, 288                             # PCLIP_VPT_SLICE: images per slice of pclip_vpt_grad_f32's first stage; PCLIP_VPT_MAX_L: L0 + P at most
 COUPLE_MAX_P, COUPLE_SLICE = 16, 32                        # PCLIP_COUPLE_MAX_P: rows per depth of the coupling function; PCLIP_COUPLE_SLICE: rows of Wc per slice of dX
+COCOOP_MAX_B = 16                                          # PCLIP_COCOOP_MAX_B: images per call of the meta-net and the conditional assembly
 
 
 class PclipError(RuntimeError):
@@ -143,6 +144,10 @@ _SIGS = {
     "pclip_rows_grad_f32": [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P],
     "pclip_couple_fwd_f32": [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P],
     "pclip_couple_bwd_f32": [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P],
+    "pclip_metanet_fwd_f32": [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P],
+    "pclip_metanet_bwd_f32": [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P],
+    "pclip_prompt_embed_cond_f16": [_P, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P],
+    "pclip_prompt_cond_grad_f32": [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P],
     "pclip_text_embed_backward": [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P],
     "pclip_vit_embed_backward_f16": [_P, c_int, c_int, c_int, _P, _P, _P],
     "pclip_adamw_f16": [_P, _P, _P, _P, c_size_t, c_double, c_double, c_double, c_double, c_double, c_int, _P],

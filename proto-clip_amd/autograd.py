@@ -578,6 +578,49 @@ class CoupleFn(torch.autograd.Function):
         return ops.couple_backward(dy.contiguous(), x, weight, want_x=need[0], want_weight=need[1], want_bias=need[2])
 
 
+# ---- CoCoOp: the per-image shift of the context rows and the prompts assembled with it ------------------------------------------------------------------
+
+class MetaNetFn(torch.autograd.Function):
+    """(f [B, E] fp16, w1 [Hd, E], b1 [Hd], w2 [Wt, Hd], b2 [Wt], the four fp32) -> pi [B, Wt] fp32 = relu(f @ w1.T + b1) @ w2.T + b2
+    (pclip_metanet_fwd_f32).  backward: pclip_metanet_bwd_f32 issues only the gradients `needs_input_grad` asks for, each in the one summation order
+    csrc/pclip_cocoop.hip documents; f (cached, normalised image features) is a constant and gets none."""
+
+    @staticmethod
+    def forward(ctx, f, w1, b1, w2, b2):
+        h, pi = ops.metanet(f, w1, b1, w2, b2)
+        ctx.save_for_backward(f, h, w1, w2)
+        return pi
+
+    @staticmethod
+    def backward(ctx, dpi):
+        f, h, w1, w2 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if dpi.dtype != torch.float32:
+            raise PclipError(f"MetaNetFn: the gradient of the shift must be float32, got {dpi.dtype}")
+        return (None,) + ops.metanet_backward(dpi.contiguous(), f, h, w1, w2, want_w1=need[1], want_b1=need[2], want_w2=need[3], want_b2=need[4])
+
+
+class CondPromptEmbedFn(torch.autograd.Function):
+    """(ctx [n_ctx, W] fp32, pi [B, W] fp32, tokens [N, L_tok], emb16, pos16, L_out) -> x [B * N * L_out, W] fp16, the residual stream that enters block 0
+    of the text tower for B images x N classes: the rows r16(ctx[j] + pi[b]) at positions 1 .. n_ctx of image b's prompts, the token embeddings elsewhere,
+    plus the positional embedding (pclip_prompt_embed_cond_f16).  backward: (dctx, dpi) in fp32 (pclip_prompt_cond_grad_f32: fixed orders over classes,
+    images and rows, no atomics); nothing else gets a gradient."""
+
+    @staticmethod
+    def forward(ctx, ctx_rows, pi, tokens, emb16, pos16, L_out):
+        ctx.shape = (pi.shape[0], tokens.shape[0], int(L_out), ctx_rows.shape[0])
+        return ops.prompt_embed_cond(ctx_rows, pi, tokens, emb16, pos16, L_out)
+
+    @staticmethod
+    def backward(ctx, dx):
+        B, N, L_out, n_ctx = ctx.shape
+        dx = dx.contiguous()
+        if dx.dtype != torch.float16:
+            dx = ops.cast_f16(dx.float())
+        dctx, dpi, _ = ops.prompt_cond_grad(dx, B, N, L_out, n_ctx)
+        return dctx, dpi, None, None, None, None
+
+
 # ---- visual prompt tuning (VPT): the stream that enters block 0 as a function of the first layer's fp32 prompt rows ------------------------------------
 
 class VptEmbedFn(torch.autograd.Function):

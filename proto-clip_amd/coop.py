@@ -11,7 +11,7 @@ A frozen tower pays for no parameter gradient (TowerTailFn skips what `needs_inp
 composes with it: the last k blocks and the heads then train beside the context.
 
 Envelope: the class token at the "end" (context directly after SOT) only, fp32 `ctx`, head dimension 64, prompts of at most 77 tokens.  Not here:
-CoCoOp's meta-net, the "middle" / "front" positions."""
+the "middle" / "front" positions.  CoCoOp's meta-net (an image-conditioned context) is `cocoop.py`."""
 import torch
 
 from . import autograd as pag

@@ -12,8 +12,8 @@ A replaced row passes no gradient to the block below.  The towers are frozen and
 text_blocks=m)` composes with it.  depth = 1 is CoOp's context with a coupled shallow VPT.
 
 Envelope: transformer towers of head dimension 64, fp32 parameters, 1 <= n_ctx <= 16 (the coupling kernel's rows per depth), 1 <= depth <= min(vision
-layers, text layers), L0 + n_ctx <= 288 vision tokens, text width a multiple of 64, context shared by the classes.  Not here: CoCoOp's meta-net (an
-image-conditioned context), PromptSRC's regularisers, a per-class (class-specific) context."""
+layers, text layers), L0 + n_ctx <= 288 vision tokens, text width a multiple of 64, context shared by the classes.  Not here: PromptSRC's regularisers, a
+per-class (class-specific) context.  CoCoOp's meta-net (an image-conditioned context) is `cocoop.py`."""
 import torch
 
 from . import autograd as pag

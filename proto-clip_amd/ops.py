@@ -1321,6 +1321,115 @@ def couple_backward(dy, x, weight, want_x: bool = True, want_weight: bool = True
     return dx, dw, db
 
 
+def _metanet_dims(who: str, f, w1, w2):
+    """(B, E, Hd, Wt) of a meta-net call, with the envelope of pclip_metanet_fwd_f32 checked on the host (the shapes alone: before any device is asked
+    for)."""
+    if f.dim() != 2 or w1.dim() != 2 or w2.dim() != 2:
+        raise _lib.PclipError(f"{who}: features {tuple(f.shape)} / W1 {tuple(w1.shape)} / W2 {tuple(w2.shape)} are not [B, E] / [Hd, E] / [Wt, Hd]")
+    B, E = f.shape
+    Hd, Wt = w1.shape[0], w2.shape[0]
+    if w1.shape[1] != E or w2.shape[1] != Hd:
+        raise _lib.PclipError(f"{who}: W1 {tuple(w1.shape)} / W2 {tuple(w2.shape)} do not chain with features of E={E} (W1 [Hd, E], W2 [Wt, Hd])")
+    if E < 64 or E % 64 != 0:
+        raise _lib.PclipError(f"{who}: E={E} must be a positive multiple of 64 (a quarter wave reads 64 columns per step)")
+    if not 4 <= Hd <= 256 or Hd % 4 != 0:
+        raise _lib.PclipError(f"{who}: Hd={Hd} must be a multiple of 4 in 4 .. 256")
+    if Wt < 8 or Wt % 8 != 0:
+        raise _lib.PclipError(f"{who}: Wt={Wt} must be a positive multiple of 8")
+    if not 1 <= B <= _lib.COCOOP_MAX_B:
+        raise _lib.PclipError(f"{who}: B={B} images outside 1 .. {_lib.COCOOP_MAX_B} (chunk the images; cocoop.ConditionalPromptLearner does)")
+    return B, E, Hd, Wt
+
+
+def metanet(f, w1, b1, w2, b2):
+    """CoCoOp's meta-net: (h [B, Hd], pi [B, Wt]) fp32 = (relu(f @ w1.T + b1), h @ w2.T + b2) for f [B, E] fp16 (normalised features, a constant) and
+    fp32 w1 [Hd, E], b1 [Hd], w2 [Wt, Hd], b2 [Wt] (pclip_metanet_fwd_f32: 1 <= B <= 16, E % 64 == 0, Hd % 4 == 0 in 4 .. 256, Wt % 8 == 0; two
+    launches, one fixed summation order).  h is what `metanet_backward` reads."""
+    B, E, Hd, Wt = _metanet_dims("metanet", f, w1, w2)
+    require_cuda(f, w1, b1, w2, b2)
+    f = _f16c(f)
+    w1, b1 = _couple_f32("metanet", "w1", w1, (Hd, E)), _couple_f32("metanet", "b1", b1, (Hd,))
+    w2, b2 = _couple_f32("metanet", "w2", w2, (Wt, Hd)), _couple_f32("metanet", "b2", b2, (Wt,))
+    h = torch.empty(B, Hd, dtype=torch.float32, device=f.device)
+    pi = torch.empty(B, Wt, dtype=torch.float32, device=f.device)
+    check(_lib.load().pclip_metanet_fwd_f32(ptr(f), ptr(w1), ptr(b1), ptr(w2), ptr(b2), B, E, Hd, Wt, ptr(h), ptr(pi), stream()), "pclip_metanet_fwd_f32")
+    return h, pi
+
+
+def metanet_backward(dpi, f, h, w1, w2, want_w1: bool = True, want_b1: bool = True, want_w2: bool = True, want_b2: bool = True):
+    """(dw1, db1, dw2, db2) of `metanet` from dpi [B, Wt] fp32 — dw2 = dpi.T @ h, db2 = dpi.sum(0), dpre = (dpi @ w2) * (h > 0), dw1 = dpre.T @ f,
+    db1 = dpre.sum(0) — each None when not wanted: nothing is launched or allocated for it (pclip_metanet_bwd_f32: at most three launches).  f is a
+    constant and gets no gradient."""
+    B, E, Hd, Wt = _metanet_dims("metanet_backward", f, w1, w2)
+    require_cuda(dpi, f, h, w1, w2)
+    f = _f16c(f)
+    dpi = _couple_f32("metanet_backward", "dpi", dpi, (B, Wt))
+    h = _couple_f32("metanet_backward", "h", h, (B, Hd))
+    w2 = _couple_f32("metanet_backward", "w2", w2, (Wt, Hd))
+    dev = dpi.device
+    new = lambda want, *shape: torch.empty(*shape, dtype=torch.float32, device=dev) if want else None      # noqa: E731
+    dw1, db1, dw2, db2 = new(want_w1, Hd, E), new(want_b1, Hd), new(want_w2, Wt, Hd), new(want_b2, Wt)
+    dpre = new(want_w1 or want_b1, B, Hd)                                        # the kernel's workspace
+    if want_w1 or want_b1 or want_w2 or want_b2:
+        check(_lib.load().pclip_metanet_bwd_f32(ptr(dpi), ptr(f), ptr(h), ptr(w2), B, E, Hd, Wt, ptr(dw1), ptr(db1), ptr(dw2), ptr(db2), ptr(dpre),
+                                                stream()), "pclip_metanet_bwd_f32")
+    return dw1, db1, dw2, db2
+
+
+def _cond_ctx(who: str, ctx, pi, W: int):
+    """(n_ctx, B) of a conditional assembly: the shared fp32 context [n_ctx, W] and the per-image shifts [B, W]."""
+    for name, t in (("ctx", ctx), ("pi", pi)):
+        if t.dtype != torch.float32:
+            raise _lib.PclipError(f"{who}: {name} must be float32, got {t.dtype}")
+    if ctx.dim() != 2 or ctx.shape[1] != W or ctx.shape[0] < 1 or pi.dim() != 2 or pi.shape[1] != W:
+        raise _lib.PclipError(f"{who}: ctx {tuple(ctx.shape)} / pi {tuple(pi.shape)} are not [n_ctx, {W}] / [B, {W}]")
+    B = pi.shape[0]
+    if not 1 <= B <= _lib.COCOOP_MAX_B:
+        raise _lib.PclipError(f"{who}: B={B} images outside 1 .. {_lib.COCOOP_MAX_B} (chunk the images; cocoop.ConditionalPromptLearner does)")
+    return ctx.shape[0], B
+
+
+def prompt_embed_cond(ctx, pi, tokens, tok_emb, pos_emb, L_out: int = None) -> torch.Tensor:
+    """Embedded prompts [B * N * L_out, W] fp16 of B images x N classes: `prompt_embed` with the context rows r16(ctx[j] + pi[b]) — ctx fp32 [n_ctx, W]
+    shared, pi fp32 [B, W] per image — in the prompts b * N .. b * N + N - 1 (pclip_prompt_embed_cond_f16).  tokens [N, L_tok] are shared by the images."""
+    N, L_tok = tokens.shape
+    vocab, W = tok_emb.shape
+    L_out = L_tok if L_out is None else int(L_out)
+    n_ctx, B = _cond_ctx("prompt_embed_cond", ctx, pi, W)
+    if not 1 <= L_out <= L_tok or pos_emb.shape[0] < L_out or pos_emb.shape[1] != W or N < 1:
+        raise _lib.PclipError(f"prompt_embed_cond: L_out={L_out} with tokens {tuple(tokens.shape)} and positional rows {tuple(pos_emb.shape)}")
+    require_cuda(ctx, pi, tokens, tok_emb, pos_emb)
+    tokens = tokens.to(torch.int64).contiguous()
+    ctx, pi, tok_emb, pos_emb = ctx.contiguous(), pi.contiguous(), _f16c(tok_emb), _f16c(pos_emb)
+    x = torch.empty(B * N * L_out, W, dtype=torch.float16, device=tok_emb.device)
+    check(_lib.load().pclip_prompt_embed_cond_f16(ptr(tokens), L_tok, ptr(tok_emb), ptr(pos_emb), ptr(ctx), ptr(pi), n_ctx, B, N, L_out, W, vocab, ptr(x),
+                                                  stream()), "pclip_prompt_embed_cond_f16")
+    return x
+
+
+def prompt_cond_grad(dx, B: int, N: int, L_out: int, n_ctx: int):
+    """(dctx [n_ctx, W], dpi [B, W], dshift [B, n_ctx, W]) fp32, the gradient of `prompt_embed_cond` from dx [B * N * L_out, W] fp16: dshift[b] is
+    `prompt_ctx_grad` of image b's N prompts (the slice-sum rule), dctx its sum over the images in ascending order, dpi[b] its sum over the context rows
+    in ascending order (pclip_prompt_cond_grad_f32: two launches).  A context row at 1 + j >= L_out is not read: its dshift is 0."""
+    B, N, L_out, n_ctx = int(B), int(N), int(L_out), int(n_ctx)
+    if not 1 <= B <= _lib.COCOOP_MAX_B:
+        raise _lib.PclipError(f"prompt_cond_grad: B={B} images outside 1 .. {_lib.COCOOP_MAX_B}")
+    if dx.dim() != 2 or dx.shape[0] != B * N * L_out or N < 1 or L_out < 1 or n_ctx < 1:
+        raise _lib.PclipError(f"prompt_cond_grad: dx {tuple(dx.shape)} has not B * N * L_out = {B} * {N} * {L_out} rows (n_ctx={n_ctx})")
+    require_cuda(dx)
+    dx = _f16c(dx)
+    W = dx.shape[1]
+    dev = dx.device
+    dshift = torch.empty(B, n_ctx, W, dtype=torch.float32, device=dev)
+    dctx = torch.empty(n_ctx, W, dtype=torch.float32, device=dev)
+    dpi = torch.empty(B, W, dtype=torch.float32, device=dev)
+    nslice = (N + _lib.PROMPT_CTX_SLICE - 1) // _lib.PROMPT_CTX_SLICE
+    part = torch.empty(B, nslice, n_ctx * W, dtype=torch.float32, device=dev) if nslice > 1 else None      # the kernel's workspace
+    check(_lib.load().pclip_prompt_cond_grad_f32(ptr(dx), B, N, L_out, n_ctx, W, ptr(dshift), ptr(dctx), ptr(dpi), ptr(part), nslice, stream()),
+          "pclip_prompt_cond_grad_f32")
+    return dctx, dpi, dshift
+
+
 def gather_eot(x, tokens, B: int, L: int, W: int) -> torch.Tensor:
     tokens = tokens.to(torch.int64).contiguous()
     out = torch.empty(B, W, dtype=torch.float16, device=x.device)

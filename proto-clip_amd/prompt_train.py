@@ -1,4 +1,4 @@
-"""The training loop of the prompt learners (`coop.run_coop`, `vpt.run_vpt`, `maple.run_maple`), stated once: SGD with momentum on a few fp32 tensors,
+"""The training loop of the prompt learners (`coop.run_coop`, `vpt.run_vpt`, `maple.run_maple`, `cocoop.run_cocoop`), stated once: SGD with momentum on a few fp32 tensors,
 a cosine schedule over every step, torch's GradScaler in front of the fp16 gradient stream of the towers, one seeded permutation of the samples per epoch."""
 import numpy as np
 import torch
