@@ -1486,6 +1486,15 @@ def cast_f32(x: torch.Tensor) -> torch.Tensor:
     return y
 
 
+def _f32_rows(who: str, name: str, t: torch.Tensor, shape=None):
+    """Refuse an operand that is not a device fp32 tensor with unit stride along its last axis (and of `shape`, when given): the entries take a pointer and a
+    row stride only."""
+    require_cuda(t)
+    if t.dtype != torch.float32 or (shape is not None and tuple(t.shape) != tuple(shape)) or (t.dim() > 0 and t.stride(-1) != 1 and t.shape[-1] > 1):
+        want = "fp32" + (f" {list(shape)}" if shape is not None else "")
+        raise _lib.PclipError(f"{who}: `{name}` must be a {want} tensor with unit column stride (got {t.dtype} {list(t.shape)}, strides {list(t.stride())})")
+
+
 def gemm_f32(a: torch.Tensor, b: torch.Tensor, trans_a: bool = False, trans_b: bool = False, alpha: float = 1.0,
              out: torch.Tensor = None, beta: float = 0.0) -> torch.Tensor:
     """out = alpha * op(a) @ op(b) + beta * out in fp32 on the fp32 MFMA; a, b are 2-D row-major (unit column stride, any
@@ -1503,6 +1512,8 @@ def gemm_f32(a: torch.Tensor, b: torch.Tensor, trans_a: bool = False, trans_b: b
     if out is None:
         out = torch.empty(M, N, dtype=torch.float32, device=a.device)
         beta = 0.0
+    else:
+        _f32_rows("gemm_f32", "out", out, (M, N))
     ws = _workspace(32 * M * N * 4, a.device) if K >= 1024 and ((M + 63) // 64) * ((N + 63) // 64) <= 128 else None
     check(_lib.load().pclip_gemm_f32(ptr(a), int(a.dtype == torch.float16), rsa, csa, ptr(b), int(b.dtype == torch.float16),
                                      rsb, csb, ptr(out), out.stride(0), M, N, K, alpha, beta, ptr(ws),
@@ -1519,6 +1530,10 @@ def colsum_f32(x: torch.Tensor, rows: int = None, cols: int = None, scale: float
     acc = out is not None
     if out is None:
         out = torch.empty(C, dtype=torch.float32, device=x.device)
+    else:
+        require_cuda(out)
+        if out.dtype != torch.float32 or out.numel() != C or not out.is_contiguous():
+            raise _lib.PclipError(f"colsum_f32: `out` must be a contiguous fp32 tensor of {C} elements (got {out.dtype} {list(out.shape)}, strides {list(out.stride())})")
     ws = _workspace(64 * C * 4, x.device) if R > 128 else None
     check(_lib.load().pclip_colsum_f32(ptr(x), x.stride(0), R, C, scale, ptr(out), int(acc), ptr(ws), ws.numel() if ws is not None else 0,
                                        stream()), "pclip_colsum_f32")
@@ -1528,7 +1543,12 @@ def colsum_f32(x: torch.Tensor, rows: int = None, cols: int = None, scale: float
 def addscaled_rows_(c: torch.Tensor, x: torch.Tensor, rowscale: torch.Tensor, s: float) -> torch.Tensor:
     """c[r, :] += s * rowscale[r] * x[r, :] in place (fp32)."""
     require_cuda(c, x, rowscale)
+    if c.dim() != 2:
+        raise _lib.PclipError(f"addscaled_rows_: `c` must be a 2-D fp32 tensor (got {list(c.shape)})")
     R, D = c.shape
+    _f32_rows("addscaled_rows_", "c", c)
+    _f32_rows("addscaled_rows_", "x", x, (R, D))
+    _f32_rows("addscaled_rows_", "rowscale", rowscale, (R,))
     check(_lib.load().pclip_addscaled_rows_f32(ptr(c), c.stride(0), ptr(x), x.stride(0), ptr(rowscale), s, R, D, stream()),
           "pclip_addscaled_rows_f32")
     return c
@@ -1536,7 +1556,8 @@ def addscaled_rows_(c: torch.Tensor, x: torch.Tensor, rowscale: torch.Tensor, s:
 
 def nll_grad(d2i, d2t, labels, N: int, alpha: float, beta: float, q_total: int = None):
     """From the distance rows of sqdist_f32: gradients (gi, gt) of mean NLL(log P) wrt them, rowsum(gi + gt), the per-query
-    -log p[y], max probability and argmax (utils.py:84-93)."""
+    -log p[y], max probability and argmax — the lowest index among equal maxima — (utils.py:84-93).  gi / gt are padded like the distance rows; the kernel leaves
+    their columns >= N untouched."""
     require_cuda(d2i, d2t, labels)
     Q, ldd = d2i.shape
     gi, gt = torch.empty_like(d2i), torch.empty_like(d2t)
@@ -1549,8 +1570,8 @@ def nll_grad(d2i, d2t, labels, N: int, alpha: float, beta: float, q_total: int =
 
 
 def fuse_probs_backward(d2i, d2t, dp, N: int, alpha: float, beta: float):
-    """Backward of `fuse_probs` for an arbitrary upstream dp [Q, N] fp32: (gi, gt) wrt the two distance rows (padded like them,
-    columns >= N unspecified) and rowsum(gi + gt) — the autograd-transparent utils.P."""
+    """Backward of `fuse_probs` for an arbitrary upstream dp [Q, N] fp32: (gi, gt) wrt the two distance rows (padded like them;
+    the kernel leaves columns >= N untouched, here they hold whatever the fresh buffers held) and rowsum(gi + gt) — the autograd-transparent utils.P."""
     require_cuda(d2i, d2t, dp)
     Q, ldd = d2i.shape
     if dp.dtype != torch.float32 or dp.shape != (Q, N) or dp.stride(1) != 1:
@@ -1569,7 +1590,8 @@ def nll_mean_backward(p: torch.Tensor, labels: torch.Tensor, g: torch.Tensor) ->
     Q, N = p.shape
     dp = torch.empty(Q, N, dtype=torch.float32, device=p.device)
     g = g.reshape(1).float().contiguous()
-    check(_lib.load().pclip_nll_mean_backward(ptr(p), p.stride(0), ptr(labels.to(torch.int32)), Q, N, ptr(g), ptr(dp), N, stream()),
+    lab = labels.to(torch.int32)                                    # held in a name: the converted copy must outlive the launch
+    check(_lib.load().pclip_nll_mean_backward(ptr(p), p.stride(0), ptr(lab), Q, N, ptr(g), ptr(dp), N, stream()),
           "pclip_nll_mean_backward")
     return dp
 

@@ -83,7 +83,11 @@ def test_nll_grad_and_cdist_backward(ops, Q, N, D, alpha, beta):
     d2i, d2t, _ = ops.sqdist_f32(zq.detach().cuda(), zi.detach().cuda(), zt.detach().cuda())
     gi, gt, rs, nll, pmax, am = ops.nll_grad(d2i, d2t, lab.cuda(), N, alpha, beta)
     assert abs(nll.mean().item() - loss.item()) <= 1e-5 * max(1.0, abs(loss.item()))
-    assert torch.equal(am.cpu().long(), p.max(1)[1]) or (am.cpu().long() != p.max(1)[1]).sum() <= 1
+    # argmax is the lowest index of the maximum (tests/test_gpu_train_f32.py pins that on exact ties); against the fp32 oracle at most one row may differ, and
+    # only where the oracle's own two candidates are within fp32 noise of each other
+    amc, top = am.cpu().long(), p.detach().max(1)
+    assert (amc != top[1]).sum() <= 1
+    assert bool((p.detach().gather(1, amc.view(-1, 1)).squeeze(1) >= top[0] * (1 - 1e-5)).all())
     assert torch.allclose(pmax.cpu(), p.max(1)[0].detach(), rtol=1e-5, atol=1e-7)
     zqc, zic, ztc = zq.detach().cuda(), zi.detach().cuda(), zt.detach().cuda()
     gq = ops.gemm_f32(gi[:, :N], zic, alpha=-2.0)
