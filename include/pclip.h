@@ -696,7 +696,7 @@ int pclip_vpt_replace_f16(void* x, const float* ctx, int B, int L0, int P, int W
  * above at off = L0, nslice = ceil(B / PCLIP_VPT_SLICE), with its `clear`; rows l < L0 are neither read nor written. */
 int pclip_vpt_grad_f32(void* g, int B, int L0, int P, int W, int clear, float* dctx, float* part, int nslice, pclip_stream_t stream);
 
-/* ---- MaPLe: prompt rows at an offset and the text -> vision coupling function (csrc/pclip_maple.hip lists the coupling's rounding points and orders) ---- */
+/* ---- MaPLe: prompt rows at an offset and the text -> vision coupling function (csrc/pclip_small_linear.h and csrc/pclip_maple.hip list the coupling's rounding points and orders) ---- */
 
 /* The two VPT passes above with the P rows at off .. off + P - 1 of sequences of L rows: L, off and P independent, 0 <= off, off + P <= L,
  * L <= PCLIP_VPT_MAX_L, W % 8 == 0, B >= 0, B * L * W within an int, operands 16-byte aligned, no atomics.  At off = L - P they give the bits of
@@ -723,7 +723,7 @@ int pclip_couple_fwd_f32(const float* X, const float* Wc, const float* bc, int d
 int pclip_couple_bwd_f32(const float* dY, const float* X, const float* Wc, int depth, int P, int Wt, int Wv, float* dWc, float* dbc, float* dX,
                          float* part, int nslice, pclip_stream_t stream);
 
-/* ---- CoCoOp: the image-conditioned context (csrc/pclip_cocoop.hip lists every rounding point and summation order) ------------------------------- */
+/* ---- CoCoOp: the image-conditioned context (csrc/pclip_cocoop.hip and csrc/pclip_small_linear.h list every rounding point and summation order) -- */
 
 /* The meta-net, fp32: h[b] = relu(W1 f[b] + b1), pi[b] = W2 h[b] + b2 for f [B, E] fp16 (already normalised; a constant), W1 [Hd, E], b1 [Hd],
  * W2 [Wt, Hd], b2 [Wt]; outputs h [B, Hd] (kept for the backward) and pi [B, Wt], the per-image shift of the context rows.  Envelope:

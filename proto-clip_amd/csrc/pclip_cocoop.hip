@@ -9,20 +9,13 @@
 // Rounding points / summation order.  f32(fp16) is exact; everything after it is fp32.  A product is rounded on its own (one fp32 multiplication) and then
 // added (one rounded fp32 addition): this file is compiled without floating-point contraction, there is no fused multiply-add in it.  Every accumulator
 // starts at +0.
-//   layer 1, pre[b][u]: 16 lanes share the row W1[u][:]; lane l (0 .. 15) owns columns e = 64 k + 4 l + j, j = 0 .. 3, k = 0 .. E / 64 - 1, and walks them
-//     in ascending k, then ascending j, into one accumulator:
-//       a_l = (..(((0 + f[b][4l] W1[u][4l]) + f[b][4l + 1] W1[u][4l + 1]) + .. + f[b][4l + 3] W1[u][4l + 3]) + f[b][64 + 4l] W1[u][64 + 4l]) + ..)
-//     the 16 lane sums are combined by a butterfly at distances 8, 4, 2, 1:  a_l <- a_l + a_(l xor 8);  .. ;  a_l <- a_l + a_(l xor 1)   (fp32 addition
-//     commutes, so all 16 lanes hold the same bits);  pre = a + b1[u], the bias added LAST;  h = +0 where pre <= 0, else pre (a NaN stays a NaN).
-//     Rounded operations on the path of one term: 1 product, at most E / 16 chain additions, 4 butterfly additions, 1 bias addition.
+//   layer 1 (h), dW2 with db2 and dW1 with db1: the small linear layer of pclip_small_linear.h at depth 1 with the B images as its rows — the forward with
+//     X = f (fp16), K = E, R = Hd and the ReLU;  dW2, db2 from dY = dpi, X = h (K = Hd, R = Wt);  dW1, db1 from dY = dpre, X = f (K = E, R = Hd).  The walks
+//     are stated there.
 //   layer 2, pi[b][t] = (..((0 + h[b][0] W2[t][0]) + h[b][1] W2[t][1]) + ..) + b2[t]      ascending u, one accumulator, the bias added LAST
 //     (1 product + Hd additions + 1 bias addition).
-//   dW2[t][u] = (..((0 + dpi[0][t] h[0][u]) + dpi[1][t] h[1][u]) + ..)                    ascending b, one accumulator  (1 product + B additions)
-//   db2[t]    = (..((0 + dpi[0][t]) + dpi[1][t]) + ..)                                    ascending b, one accumulator  (B additions)
 //   dh[b][u]  = (..((0 + dpi[b][0] W2[0][u]) + dpi[b][1] W2[1][u]) + ..)                  ascending t, one accumulator  (1 product + Wt additions)
 //   dpre[b][u] = dh[b][u] where h[b][u] > 0, else +0  (a hidden unit that is exactly 0 passes no gradient); f is a constant and gets no gradient.
-//   dW1[u][e] = (..((0 + dpre[0][u] f[0][e]) + dpre[1][u] f[1][e]) + ..)                  ascending b, one accumulator  (1 product + B additions)
-//   db1[u]    = (..((0 + dpre[0][u]) + dpre[1][u]) + ..)                                  ascending b, one accumulator  (B additions)
 // Launches: forward 2 (layer 1; layer 2); backward at most 3 (dW2 with db2; dpre; dW1 with db1) — nothing is launched for what is not asked for.
 //
 // ---- the conditional assembly -----------------------------------------------------------------------------------------------------------------------------------
@@ -35,7 +28,8 @@
 // ---- the conditional context gradient ----------------------------------------------------------------------------------------------------------------------------
 // From dx [B N L_out, W] fp16; f32(fp16) is exact, every `+` is one rounded fp32 addition, the roundings of the context to fp16 are passed straight through.
 //   dshift[b][j][d]: THE SLICE-SUM RULE of pclip_rows.h (SLICE = PCLIP_PROMPT_CTX_SLICE = 16, off = 1, avail = min(n_ctx, L_out - 1)) applied to the N
-//     prompts of image b:  part[b][s][j][d] = (..(f32(dx[b N + 16 s, 1 + j, d]) + f32(dx[b N + 16 s + 1, 1 + j, d])) + ..)   ascending class order
+//     prompts of image b, its first stage launched with one group per image:
+//                          part[b][s][j][d] = (..(f32(dx[b N + 16 s, 1 + j, d]) + f32(dx[b N + 16 s + 1, 1 + j, d])) + ..)   ascending class order
 //                          dshift[b][j][d]  = (..(part[b][0][j][d] + part[b][1][j][d]) + ..)                                  ascending slice order
 //     each sum starts from its first term; one slice (N <= 16): part is dshift itself.  A row j >= avail has no row in dx: it is not read, its dshift is +0.
 //   dctx[j][d] = (..(dshift[0][j][d] + dshift[1][j][d]) + ..)        ascending b, starting from b = 0
@@ -46,53 +40,12 @@
 
 #pragma clang fp contract(off)
 
+#include "pclip_small_linear.h"
+
 namespace {
 constexpr int MAXB = PCLIP_COCOOP_MAX_B;
 
 // ---- meta-net ------------------------------------------------------------------------------------------------------------------------------------------------
-
-// layer 1: a quarter wave (16 lanes) per row u of W1: four rows per wave, 16 rows per 256-thread block; grid ceil(Hd / 16)
-__global__ __launch_bounds__(256) void metanet_l1_kernel(const half_t* __restrict__ f, const float* __restrict__ W1, const float* __restrict__ b1, int B, int E,
-                                                         int Hd, float* __restrict__ h) {
-    const int l = threadIdx.x & 15;
-    const int u = blockIdx.x * 16 + (threadIdx.x >> 4);
-    const int ur = u < Hd ? u : Hd - 1;                                      // a row past the end reads the last row and stores nothing
-    const float* w = W1 + (size_t)ur * E + 4 * l;
-    const half_t* x = f + 4 * l;
-    float acc[MAXB];
-#pragma unroll
-    for (int b = 0; b < MAXB; ++b) acc[b] = 0.f;
-    for (int k = 0; k < E; k += 64) {
-        const float4_t w4 = *reinterpret_cast<const float4_t*>(w + k);
-#pragma unroll
-        for (int b = 0; b < MAXB; ++b) {
-            if (b < B) {
-                const half4_t x4 = *reinterpret_cast<const half4_t*>(x + (size_t)b * E + k);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float prod = (float)x4[j] * w4[j];
-                    acc[b] = acc[b] + prod;
-                }
-            }
-        }
-    }
-    float mine = 0.f;
-#pragma unroll
-    for (int b = 0; b < MAXB; ++b) {
-        if (b < B) {
-            float s = acc[b];
-            s = s + __shfl_xor(s, 8, 16);
-            s = s + __shfl_xor(s, 4, 16);
-            s = s + __shfl_xor(s, 2, 16);
-            s = s + __shfl_xor(s, 1, 16);
-            if (l == b) mine = s;
-        }
-    }
-    if (l < B && u < Hd) {
-        const float pre = mine + b1[u];
-        h[(size_t)l * Hd + u] = pre <= 0.f ? 0.f : pre;
-    }
-}
 
 // layer 2: one thread per row t of W2 walks its Hd columns in ascending order for every image; grid ceil(Wt / 64)
 __global__ __launch_bounds__(64) void metanet_l2_kernel(const float* __restrict__ h, const float* __restrict__ W2, const float* __restrict__ b2, int B, int Hd,
@@ -121,48 +74,6 @@ __global__ __launch_bounds__(64) void metanet_l2_kernel(const float* __restrict_
 #pragma unroll
     for (int b = 0; b < MAXB; ++b)
         if (b < B) pi[(size_t)b * Wt + t] = acc[b] + bias;
-}
-
-__device__ __forceinline__ float4_t ld_f32x4(const float* p) { return *reinterpret_cast<const float4_t*>(p); }
-__device__ __forceinline__ float4_t ld_f32x4(const half_t* p) {
-    const half4_t v = *reinterpret_cast<const half4_t*>(p);
-    return float4_t{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-}
-
-// dW [R, C] = dY^T X and db [R] = column sums of dY, over the B rows in ascending order: dY [B, R] fp32, X [B, C] fp32 or fp16; one thread per (r, 4 columns),
-// flat over R * C / 4; the thread of a row's first vector also sums the row's bias gradient.  (dW2, db2: dY = dpi, X = h;  dW1, db1: dY = dpre, X = f.)
-template <typename XT>
-__global__ __launch_bounds__(256) void metanet_dw_kernel(const float* __restrict__ dY, const XT* __restrict__ X, int B, int R, int C, float* __restrict__ dW,
-                                                         float* __restrict__ db) {
-    const int C4 = C / 4;
-    const size_t nvec = (size_t)R * C4;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C4);
-        const int r = (int)(i / C4);
-        float4_t acc = {0.f, 0.f, 0.f, 0.f};
-        float s = 0.f;
-        for (int b = 0; b < B; ++b) {
-            const float g = dY[(size_t)b * R + r];
-            const float4_t x4 = ld_f32x4(X + (size_t)b * C + 4 * c);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float prod = g * x4[j];
-                acc[j] = acc[j] + prod;
-            }
-            s = s + g;
-        }
-        reinterpret_cast<float4_t*>(dW)[i] = acc;
-        if (db && c == 0) db[r] = s;
-    }
-}
-
-// db alone (dW not asked for): one thread per r
-__global__ __launch_bounds__(256) void metanet_db_kernel(const float* __restrict__ dY, int B, int R, float* __restrict__ db) {
-    for (size_t r = (size_t)blockIdx.x * 256 + threadIdx.x; r < (size_t)R; r += (size_t)gridDim.x * 256) {
-        float s = 0.f;
-        for (int b = 0; b < B; ++b) s = s + dY[(size_t)b * R + r];
-        db[r] = s;
-    }
 }
 
 // dpre [B, Hd]: one thread per (b, 4 hidden units) walks the Wt rows of W2 in ascending order, then masks by h > 0; flat over B * Hd / 4
@@ -242,42 +153,6 @@ __global__ __launch_bounds__(256) void prompt_embed_cond_kernel(const int64_t* _
 
 // ---- conditional context gradient --------------------------------------------------------------------------------------------------------------------------------
 
-// first stage: one thread per (image, slice, context row, 8 columns) walks its slice's classes in ascending order; part [B][nslice][P][W]
-__global__ __launch_bounds__(256) void cond_grad_part_kernel(const half_t* __restrict__ g, int B, int N, int L, int P, int avail, int W, int nslice,
-                                                             float* __restrict__ part) {
-    const int WV = W / 8;
-    const size_t nvec = (size_t)B * nslice * P * WV;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (size_t)gridDim.x * 256) {
-        const int d = (int)(i % WV) * 8;
-        const int j = (int)((i / WV) % P);
-        const size_t bs = i / ((size_t)WV * P);
-        const int s = (int)(bs % nslice);
-        const size_t b = bs / nslice;
-        const int n0 = s * PCLIP_PROMPT_CTX_SLICE, n1 = n0 + PCLIP_PROMPT_CTX_SLICE < N ? n0 + PCLIP_PROMPT_CTX_SLICE : N;
-        float acc[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) acc[k] = 0.f;
-        if (j < avail) {
-            const half_t* src = g + ((b * N + n0) * L + 1 + j) * W + d;
-            half8_t v = ld_half8(src);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) acc[k] = (float)v[k];
-            for (int n = n0 + 1; n < n1; ++n) {
-                src += (size_t)L * W;
-                v = ld_half8(src);
-#pragma unroll
-                for (int k = 0; k < 8; ++k) acc[k] += (float)v[k];
-            }
-        }
-        float4_t* dst = reinterpret_cast<float4_t*>(part + (bs * P + j) * W + d);
-        float4_t o0, o1;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { o0[k] = acc[k]; o1[k] = acc[4 + k]; }
-        dst[0] = o0;
-        dst[1] = o1;
-    }
-}
-
 // the merge of one (b, j, 4 columns): (..(part[b][0][j] + part[b][1][j]) + ..), starting from slice 0
 __device__ __forceinline__ float4_t cond_merge(const float* __restrict__ part, size_t b, int j, int c, int P, int W, int nslice) {
     const float* src = part + ((b * nslice) * P + j) * W + 4 * c;
@@ -344,7 +219,7 @@ extern "C" int pclip_metanet_fwd_f32(const void* f, const float* W1, const float
     PCLIP_REQUIRE((((uintptr_t)f | (uintptr_t)W1 | (uintptr_t)b1 | (uintptr_t)W2 | (uintptr_t)b2 | (uintptr_t)h | (uintptr_t)pi) & 15) == 0,
                   "pclip_metanet_fwd_f32: operands must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    metanet_l1_kernel<<<(Hd + 15) / 16, 256, 0, s>>>((const half_t*)f, W1, b1, B, E, Hd, h);
+    rowdot16_kernel<half_t, true, false><<<(Hd + 15) / 16, 256, 0, s>>>((const half_t*)f, W1, b1, B, E, Hd, h);
     metanet_l2_kernel<<<(Wt + 63) / 64, 64, 0, s>>>(h, W2, b2, B, Hd, Wt, pi);
     return pclip_check_launch("metanet_fwd");
 }
@@ -360,15 +235,15 @@ extern "C" int pclip_metanet_bwd_f32(const float* dpi, const void* f, const floa
                     (uintptr_t)dpre) & 15) == 0, "pclip_metanet_bwd_f32: operands must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     if (dW2)
-        metanet_dw_kernel<float><<<flat_grid((size_t)Wt * (Hd / 4)), 256, 0, s>>>(dpi, h, B, Wt, Hd, dW2, db2);
+        small_linear_dw_kernel<float><<<flat_grid((size_t)Wt * (Hd / 4)), 256, 0, s>>>(dpi, h, B, Wt, Hd, dW2, db2);
     else if (db2)
-        metanet_db_kernel<<<flat_grid((size_t)Wt), 256, 0, s>>>(dpi, B, Wt, db2);
+        small_linear_db_kernel<><<<flat_grid((size_t)Wt), 256, 0, s>>>(dpi, B, Wt, db2);
     if (dW1 || db1) {
         metanet_dpre_kernel<<<(B * (Hd / 4) + 63) / 64, 64, 0, s>>>(dpi, W2, h, B, Hd, Wt, dpre);
         if (dW1)
-            metanet_dw_kernel<half_t><<<flat_grid((size_t)Hd * (E / 4)), 256, 0, s>>>(dpre, (const half_t*)f, B, Hd, E, dW1, db1);
+            small_linear_dw_kernel<half_t><<<flat_grid((size_t)Hd * (E / 4)), 256, 0, s>>>(dpre, (const half_t*)f, B, Hd, E, dW1, db1);
         else
-            metanet_db_kernel<<<flat_grid((size_t)Hd), 256, 0, s>>>(dpre, B, Hd, db1);
+            small_linear_db_kernel<><<<flat_grid((size_t)Hd), 256, 0, s>>>(dpre, B, Hd, db1);
     }
     return pclip_check_launch("metanet_bwd");
 }
@@ -397,7 +272,9 @@ extern "C" int pclip_prompt_cond_grad_f32(const void* dx, int B, int N, int L_ou
     const int avail = n_ctx < L_out - 1 ? n_ctx : L_out - 1;
     float* first = nslice == 1 ? dshift : part;
     hipStream_t s = (hipStream_t)stream;
-    cond_grad_part_kernel<<<flat_grid((size_t)B * nslice * n_ctx * (W / 8)), 256, 0, s>>>((const half_t*)dx, B, N, L_out, n_ctx, avail, W, nslice, first);
+    // one group per image; clear = 0: dx is only read
+    rows_grad_part_kernel<PCLIP_PROMPT_CTX_SLICE, true><<<dim3(flat_grid((size_t)nslice * n_ctx * (W / 8)), B), 256, 0, s>>>(
+        (half_t*)const_cast<void*>(dx), N, L_out, 1, n_ctx, avail, W, 0, nslice, first, (size_t)N * L_out * W, (size_t)nslice * n_ctx * W);
     cond_grad_finish_kernel<<<flat_grid((size_t)(B + n_ctx) * (W / 4)), 256, 0, s>>>(first, B, n_ctx, avail, W, nslice, dshift, dctx, dpi);
     return pclip_check_launch("prompt_cond_grad");
 }

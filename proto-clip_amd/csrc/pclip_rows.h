@@ -1,11 +1,12 @@
-// Learned prompt rows inside an fp16 stream, defined once for CoOp (pclip_prompt.hip), VPT (pclip_vpt.hip) and MaPLe (pclip_maple.hip): writing the
-// rows (replace) and the gradient of the rows summed over the sequences (the slice-sum walk).  Flat memory-bound passes of 16-byte (8-half) vectors,
-// W % 8 == 0; no atomics, no hand-over between workgroups: every sum has one fixed order and two calls give the same bits.
+// Learned prompt rows inside an fp16 stream, defined once for CoOp (pclip_prompt.hip), VPT (pclip_vpt.hip), MaPLe (pclip_maple.hip) and CoCoOp
+// (pclip_cocoop.hip): writing the rows (replace) and the gradient of the rows summed over the sequences (the slice-sum walk).  Flat memory-bound passes of
+// 16-byte (8-half) vectors, W % 8 == 0; no atomics, no hand-over between workgroups: every sum has one fixed order and two calls give the same bits.
 //
 // Shapes: B sequences of L rows, the stream is [B * L, W] fp16; the P prompt rows are rows off .. off + P - 1 of every sequence.
 //   CoOp   off = 1 (the context directly behind SOT), B = the classes
 //   VPT    off = L0 = L - P (behind the stem rows); the compact call of the embedding's backward is L = P, off = 0
 //   MaPLe  any off with off + P <= L
+//   CoCoOp off = 1, B = the classes of ONE image; the images are groups (below)
 //
 // Rounding points
 //   replace:  a prompt element is rounded ONCE, fp32 -> fp16, round to nearest even (r16); nothing is added to it.  Every other row is not touched.
@@ -23,6 +24,13 @@
 //   and their gradient is +0.
 //   clear = 1: the same pass stores exact zeros (+0) over the rows of g it has read — the lane that loaded a vector stores the zeros over it, after its
 //   load, so no element is cleared before it is read.  Rows outside [off, off + avail) are neither read nor written.
+//
+// Groups: the GROUPED instantiation of either gradient kernel, launched with gridDim.y = G, runs G independent walks of the same shape, one per
+// blockIdx.y; group q reads and writes at its own base, the pointers advanced by q times a per-group stride (elements) the caller passes.  Nothing is
+// added across groups and no index is divided by G.  The first stage's groups are CoCoOp's images (stream stride N * L * W, part stride nslice * P * W);
+// the merge's groups are the depths of MaPLe's coupling gradient dX (part stride nslice * M, out stride M).  Every other caller takes the ungrouped
+// instantiation, which does not read the strides (gridDim.y == 1): the twenty scalar instructions of the two 64-bit base offsets are measurable in passes
+// whose time is their launch.
 #pragma once
 #include "pclip_common.h"
 
@@ -50,10 +58,14 @@ __global__ __launch_bounds__(256) void rows_replace_kernel(half_t* __restrict__ 
     }
 }
 
-// first stage: one thread per (slice, prompt row, 8 columns) walks its slice's sequences in ascending order; part [nslice][P][W]
-template <int SLICE>
+// first stage: one thread per (slice, prompt row, 8 columns) walks its slice's sequences in ascending order; part [nslice][P][W]; grid (flat, groups)
+template <int SLICE, bool GROUPED = false>
 __global__ __launch_bounds__(256) void rows_grad_part_kernel(half_t* __restrict__ g, int B, int L, int off, int P, int avail, int W, int clear, int nslice,
-                                                             float* __restrict__ part) {
+                                                             float* __restrict__ part, size_t g_stride, size_t part_stride) {
+    if (GROUPED) {
+        g += blockIdx.y * g_stride;
+        part += blockIdx.y * part_stride;
+    }
     const int WV = W / 8;
     const size_t nvec = (size_t)nslice * P * WV;
     half8_t zero;
@@ -90,8 +102,14 @@ __global__ __launch_bounds__(256) void rows_grad_part_kernel(half_t* __restrict_
     }
 }
 
-// the merge: out[i] = (..(part[0][i] + part[1][i]) + ..) + part[nslice - 1][i], four elements per thread (M % 4 == 0)
-__global__ __launch_bounds__(256) void rows_grad_sum_kernel(const float* __restrict__ part, int nslice, size_t M, float* __restrict__ out) {
+// the merge: out[i] = (..(part[0][i] + part[1][i]) + ..) + part[nslice - 1][i], four elements per thread (M % 4 == 0); grid (flat, groups)
+template <bool GROUPED = false>
+__global__ __launch_bounds__(256) void rows_grad_sum_kernel(const float* __restrict__ part, int nslice, size_t M, float* __restrict__ out, size_t part_stride,
+                                                            size_t out_stride) {
+    if (GROUPED) {
+        part += blockIdx.y * part_stride;
+        out += blockIdx.y * out_stride;
+    }
     const size_t nvec = M / 4;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (size_t)gridDim.x * 256) {
         float4_t acc = reinterpret_cast<const float4_t*>(part)[i];
@@ -118,8 +136,8 @@ template <int SLICE>
 inline int rows_grad(const char* name, void* g, int B, int L, int off, int P, int avail, int W, int clear, float* first, int nslice, float* merged,
                      pclip_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
-    rows_grad_part_kernel<SLICE><<<flat_grid((size_t)nslice * P * (W / 8)), 256, 0, s>>>((half_t*)g, B, L, off, P, avail, W, clear ? 1 : 0, nslice, first);
-    if (merged && nslice > 1) rows_grad_sum_kernel<<<flat_grid((size_t)P * W / 4), 256, 0, s>>>(first, nslice, (size_t)P * W, merged);
+    rows_grad_part_kernel<SLICE><<<flat_grid((size_t)nslice * P * (W / 8)), 256, 0, s>>>((half_t*)g, B, L, off, P, avail, W, clear ? 1 : 0, nslice, first, 0, 0);
+    if (merged && nslice > 1) rows_grad_sum_kernel<><<<flat_grid((size_t)P * W / 4), 256, 0, s>>>(first, nslice, (size_t)P * W, merged, 0, 0);
     return pclip_check_launch(name);
 }
 }  // namespace

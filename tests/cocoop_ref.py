@@ -1,7 +1,8 @@
-"""References for CoCoOp's kernels (csrc/pclip_cocoop.hip), on the CPU, derived from the header comment of that file:
+"""References for CoCoOp's kernels (csrc/pclip_cocoop.hip), on the CPU, derived from the header comments of that file and of csrc/pclip_small_linear.h:
 
   * a numpy-float32 emulation of the meta-net's forward and backward in exactly the documented order — every product rounded on its own, every `+` one
-    rounded fp32 addition, every accumulator starting at +0, the biases added last — with the float64 statements and the tolerances derived from that order
+    rounded fp32 addition, every accumulator starting at +0, the biases added last; layer 1 and the weight / bias gradients are the shared walks of
+    tests/maple_ref.py (emulate_rowdot16, emulate_dw_db) at depth 1 — with the float64 statements and the tolerances derived from that order
     by the project's rule: (rounded operations on the path of one term) x u x sum |terms|, u = 2^-24, plus what an input's own tolerance contributes where
     a stage reads the previous stage's result;
   * the conditional assembly (tests/coop_ref.py's restatement with the rows r16(ctx[j] + pi[b])) with its float64 statement and the tolerance of its
@@ -16,6 +17,7 @@ import numpy as np
 import torch
 
 import coop_ref
+import maple_ref
 import vpt_ref
 
 U32 = vpt_ref.U32
@@ -35,44 +37,26 @@ def _t(a):
     return torch.from_numpy(np.ascontiguousarray(a))
 
 
-def _madd(acc, a, b, fused):
-    """acc + a * b: the product rounded on its own and then added — or, fused, one rounding of the exact sum (the product of two fp32 numbers is exact
-    in float64; the float64 addition's own rounding is 29 bits below fp32's)."""
-    if fused:
-        return (acc.astype(np.float64) + a.astype(np.float64) * b.astype(np.float64)).astype(np.float32)
-    return (acc + (a * b).astype(np.float32)).astype(np.float32)
+_madd = maple_ref.madd
 
 
 # ---- the meta-net -------------------------------------------------------------------------------------------------------------------------------------------
 
 def emulate_metanet_fwd(f16, W1, b1, W2, b2, variant=None):
-    """(h [B, Hd], pi [B, Wt]) fp32 by the documented walks.  Layer 1: lane l of 16 owns columns 64 k + 4 l + j, ascending k then j into one accumulator
-    from +0; butterfly at distances 8, 4, 2, 1; the bias last; h = +0 where pre <= 0.  Layer 2: ascending u into one accumulator from +0, the bias last.
-    variant "bias_first": both accumulators start at the bias instead (lane 0's in layer 1); "fma": every multiply-add is fused."""
+    """(h [B, Hd], pi [B, Wt]) fp32 by the documented walks.  Layer 1: maple_ref.emulate_rowdot16 at depth 1, then h = +0 where pre <= 0.  Layer 2:
+    ascending u into one accumulator from +0, the bias last.  variant "bias_first": both accumulators start at the bias instead (lane 0's in layer 1);
+    "fma": every multiply-add is fused."""
     f, W1, b1, W2, b2 = _f32(f16.float()), _f32(W1), _f32(b1), _f32(W2), _f32(b2)
     fused = variant == "fma"
-    B, E = f.shape
-    Hd, Wt = W1.shape[0], W2.shape[0]
-    xs = f.reshape(B, 1, E // 64, 16, 4)
-    ws = W1.reshape(1, Hd, E // 64, 16, 4)
-    acc = np.zeros((B, Hd, 16), np.float32)
-    if variant == "bias_first":
-        acc[:, :, 0] = b1[None, :]
-    for k in range(E // 64):
-        for j in range(4):
-            acc = _madd(acc, np.broadcast_to(xs[:, :, k, :, j], acc.shape), np.broadcast_to(ws[:, :, k, :, j], acc.shape), fused)
-    lanes = np.arange(16)
-    for m in (8, 4, 2, 1):
-        acc = (acc + acc[..., lanes ^ m]).astype(np.float32)
-    pre = acc[..., 0]
-    if variant != "bias_first":
-        pre = (pre + b1[None, :]).astype(np.float32)
+    B, Wt = f.shape[0], W2.shape[0]
+    Hd = W1.shape[0]
+    pre = maple_ref.emulate_rowdot16(f[None], W1[None], b1[None], "first" if variant == "bias_first" else "last", fused)[0]
     h = np.where(pre <= 0, np.float32(0), pre).astype(np.float32)
     out = np.zeros((B, Wt), np.float32)
     if variant == "bias_first":
         out = out + b2[None, :]
     for u in range(Hd):
-        out = _madd(out, np.broadcast_to(h[:, u, None], out.shape), np.broadcast_to(W2[None, :, u], out.shape), fused)
+        out = _madd(out, h[:, u, None], W2[None, :, u], fused)
     if variant != "bias_first":
         out = (out + b2[None, :]).astype(np.float32)
     return _t(h), _t(out)
@@ -95,27 +79,24 @@ def tol_metanet_fwd(f16, W1, b1, W2, b2):
     return tol_h, (Hd + 2) * U32 * (h @ w2.t() + b2.double().abs()) + tol_h @ w2.t()
 
 
+def emulate_metanet_dpre(dpi, h, W2, fused=False):
+    """dpre [B, Hd] fp32 (numpy): dh sums over t in ascending order in one accumulator from +0; dpre = dh where h > 0, else +0."""
+    dpi, h, W2 = _f32(dpi), _f32(h), _f32(W2)
+    dh = np.zeros(h.shape, np.float32)
+    for t in range(dpi.shape[1]):
+        dh = _madd(dh, dpi[:, t, None], W2[None, t, :], fused)
+    return np.where(h > 0, dh, np.float32(0)).astype(np.float32)
+
+
 def emulate_metanet_bwd(dpi, f16, h, W2, variant=None):
-    """(dW1, db1, dW2, db2) fp32 by the documented walks: sums over b and over t ascend in one accumulator from +0; dpre = dh where h > 0, else +0.
-    variant "descending_b": the images are added from the last to the first; "fma": every multiply-add is fused."""
+    """(dW1, db1, dW2, db2) fp32 by the documented walks: dW2 with db2 from (dpi, h) and dW1 with db1 from (dpre, f) by maple_ref.emulate_dw_db at depth
+    1, dpre by emulate_metanet_dpre.  variant "descending_b": the images are added from the last to the first; "fma": every multiply-add is fused."""
     dpi, f, h, W2 = _f32(dpi), _f32(f16.float()), _f32(h), _f32(W2)
-    fused = variant == "fma"
-    B, Wt = dpi.shape
-    Hd, E = h.shape[1], f.shape[1]
-    order = range(B - 1, -1, -1) if variant == "descending_b" else range(B)
-    dW2, db2 = np.zeros((Wt, Hd), np.float32), np.zeros(Wt, np.float32)
-    for b in order:
-        dW2 = _madd(dW2, np.broadcast_to(dpi[b, :, None], dW2.shape), np.broadcast_to(h[b, None, :], dW2.shape), fused)
-        db2 = (db2 + dpi[b]).astype(np.float32)
-    dh = np.zeros((B, Hd), np.float32)
-    for t in range(Wt):
-        dh = _madd(dh, np.broadcast_to(dpi[:, t, None], dh.shape), np.broadcast_to(W2[None, t, :], dh.shape), fused)
-    dpre = np.where(h > 0, dh, np.float32(0)).astype(np.float32)
-    dW1, db1 = np.zeros((Hd, E), np.float32), np.zeros(Hd, np.float32)
-    for b in order:
-        dW1 = _madd(dW1, np.broadcast_to(dpre[b, :, None], dW1.shape), np.broadcast_to(f[b, None, :], dW1.shape), fused)
-        db1 = (db1 + dpre[b]).astype(np.float32)
-    return _t(dW1), _t(db1), _t(dW2), _t(db2)
+    fused, descending = variant == "fma", variant == "descending_b"
+    dW2, db2 = maple_ref.emulate_dw_db(dpi[None], h[None], descending, fused)
+    dpre = emulate_metanet_dpre(dpi, h, W2, fused)
+    dW1, db1 = maple_ref.emulate_dw_db(dpre[None], f[None], descending, fused)
+    return _t(dW1[0]), _t(db1[0]), _t(dW2[0]), _t(db2[0])
 
 
 def metanet_bwd64(dpi, f16, h, W2):

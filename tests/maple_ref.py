@@ -1,4 +1,4 @@
-"""References for MaPLe's kernels (csrc/pclip_maple.hip), on the CPU, derived from the header comment of that file:
+"""References for MaPLe's kernels (csrc/pclip_maple.hip), on the CPU, derived from the header comments of that file and of csrc/pclip_small_linear.h:
 
   * the torch expression of the replace at an offset, and the emulation of the row gradient's summation ORDER (tests/vpt_ref.py's rule applied to the window
     off .. off + P - 1 of sequences of L rows) with its float64 sum and tolerance;
@@ -61,27 +61,57 @@ def _f32(t):
     return np.ascontiguousarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t, dtype=np.float32)
 
 
-def emulate_couple_fwd(X, Wc, bc, variant=None):
-    """Y [depth, P, Wv] fp32 by the documented walk: lane l of 16 owns columns 64 k + 4 l + j, ascending k then j into one accumulator from +0; butterfly
-    at distances 8, 4, 2, 1; the bias last.  variant "no_bias": the bias is dropped; "wrong_depth": depth d reads the weights of depth d - 1."""
-    X, Wc, bc = _f32(X), _f32(Wc), _f32(bc)
-    if variant == "wrong_depth":
-        Wc = np.roll(Wc, 1, axis=0)
-    D, P, Wt = X.shape
-    Wv = Wc.shape[1]
-    xs = X.reshape(D, P, 1, Wt // 64, 16, 4)
-    ws = Wc.reshape(D, 1, Wv, Wt // 64, 16, 4)
-    acc = np.zeros((D, P, Wv, 16), np.float32)
-    for k in range(Wt // 64):
+def madd(acc, a, b, fused=False):
+    """acc + a * b: the product rounded on its own and then added — or, fused, one rounding of the exact sum (the product of two fp32 numbers is exact
+    in float64; the float64 addition's own rounding is 29 bits below fp32's)."""
+    if fused:
+        return (acc.astype(np.float64) + a.astype(np.float64) * b.astype(np.float64)).astype(np.float32)
+    return (acc + (a * b).astype(np.float32)).astype(np.float32)
+
+
+# The walks of csrc/pclip_small_linear.h, in numpy float32: the one emulation of each behind the coupling function (here) and the meta-net (cocoop_ref.py).
+
+def emulate_rowdot16(X, W, b, bias="last", fused=False):
+    """pre [D, P, R] fp32 of X [D, P, K], W [D, R, K], b [D, R]: lane l of 16 owns columns 64 k + 4 l + j, ascending k then j into one accumulator from +0;
+    butterfly at distances 8, 4, 2, 1; the bias last.  bias "first": lane 0's accumulator starts at the bias instead; None: the bias is dropped.  fused:
+    every multiply-add of the chain is fused."""
+    D, P, K = X.shape
+    R = W.shape[1]
+    xs = X.reshape(D, P, 1, K // 64, 16, 4)
+    ws = W.reshape(D, 1, R, K // 64, 16, 4)
+    acc = np.zeros((D, P, R, 16), np.float32)
+    if bias == "first":
+        acc[..., 0] = b[:, None, :]
+    for k in range(K // 64):
         for j in range(4):
-            prod = (xs[:, :, :, k, :, j] * ws[:, :, :, k, :, j]).astype(np.float32)
-            acc = (acc + prod).astype(np.float32)
+            acc = madd(acc, xs[:, :, :, k, :, j], ws[:, :, :, k, :, j], fused)
     lanes = np.arange(16)
     for m in (8, 4, 2, 1):
         acc = (acc + acc[..., lanes ^ m]).astype(np.float32)
     y = acc[..., 0]
-    if variant != "no_bias":
-        y = (y + bc[:, None, :]).astype(np.float32)
+    if bias == "last":
+        y = (y + b[:, None, :]).astype(np.float32)
+    return y
+
+
+def emulate_dw_db(dY, X, descending=False, fused=False):
+    """(dW [D, R, K], db [D, R]) fp32 of dY [D, P, R], X [D, P, K]: the P rows in ascending order (descending: from the last to the first) into one
+    accumulator from +0."""
+    D, P, R = dY.shape
+    dW, db = np.zeros((D, R, X.shape[2]), np.float32), np.zeros((D, R), np.float32)
+    for p in (range(P - 1, -1, -1) if descending else range(P)):
+        dW = madd(dW, dY[:, p, :, None], X[:, p, None, :], fused)
+        db = (db + dY[:, p, :]).astype(np.float32)
+    return dW, db
+
+
+def emulate_couple_fwd(X, Wc, bc, variant=None):
+    """Y [depth, P, Wv] fp32 by the documented walk (emulate_rowdot16).  variant "no_bias": the bias is dropped; "wrong_depth": depth d reads the weights
+    of depth d - 1."""
+    X, Wc, bc = _f32(X), _f32(Wc), _f32(bc)
+    if variant == "wrong_depth":
+        Wc = np.roll(Wc, 1, axis=0)
+    y = emulate_rowdot16(X, Wc, bc, None if variant == "no_bias" else "last")
     return torch.from_numpy(np.ascontiguousarray(y))
 
 
@@ -97,19 +127,14 @@ def tol_couple_fwd(X, Wc, bc):
 
 
 def emulate_couple_bwd(dY, X, Wc, variant=None):
-    """(dX, dWc, dbc) fp32 by the documented walks.  variant "drop_last_slice": the merge of dX forgets the last slice of 32 rows; "wrong_depth": dX of
-    depth d reads the weights of depth d - 1."""
+    """(dX, dWc, dbc) fp32 by the documented walks (dWc, dbc: emulate_dw_db).  variant "drop_last_slice": the merge of dX forgets the last slice of 32
+    rows; "wrong_depth": dX of depth d reads the weights of depth d - 1."""
     dY, X, Wc = _f32(dY), _f32(X), _f32(Wc)
     if variant == "wrong_depth":
         Wc = np.roll(Wc, 1, axis=0)
     D, P, Wt = X.shape
     Wv = Wc.shape[1]
-    dW = np.zeros((D, Wv, Wt), np.float32)
-    db = np.zeros((D, Wv), np.float32)
-    for p in range(P):
-        prod = (dY[:, p, :, None] * X[:, p, None, :]).astype(np.float32)
-        dW = (dW + prod).astype(np.float32)
-        db = (db + dY[:, p, :]).astype(np.float32)
+    dW, db = emulate_dw_db(dY, X)
     parts = []
     for v0 in range(0, Wv, COUPLE_SLICE):
         acc = np.zeros((D, P, Wt), np.float32)

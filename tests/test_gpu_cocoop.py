@@ -110,6 +110,31 @@ def test_ties_to_the_shared_context_kernels():
         assert torch.equal(bits(dpi[0]), bits(acc))
 
 
+@pytest.mark.parametrize("family", ["decades", "cancel"])
+@pytest.mark.parametrize("E,Hd,Wt", [(64, 8, 64), (128, 40, 128)])
+def test_the_metanet_ties_to_the_coupling_function(E, Hd, Wt, family):
+    """The meta-net's layer 1 and its weight / bias gradients are the coupling function's walks (csrc/pclip_small_linear.h) at depth 1 with the B images as the
+    rows, B in {1, 3, 16}: h has the bits of relu(ops.couple(f, W1, b1)); dw2, db2 those of ops.couple_backward(dpi, h) and dw1, db1 those of
+    ops.couple_backward(dpre, f), dpre from the emulation.  The coupling's envelope wants its input width a multiple of 64: h goes in with zero columns
+    appended up to 64 (a column of dWc depends on that column of X alone; dbc on none)."""
+    from proto_clip_amd import ops
+    for B in (1, 3, 16):
+        f, W1, b1, W2, b2, dpi = ref.synth_metanet(B, E, Hd, Wt, 100 * B + Hd, family)
+        fd, W1d, b1d, W2d, b2d, dpid = [t.cuda() for t in (f, W1, b1, W2, b2, dpi)]
+        h, _ = ops.metanet(fd, W1d, b1d, W2d, b2d)
+        pre = ops.couple(fd.float()[None], W1d[None], b1d[None])[0]
+        assert torch.equal(bits(h), bits(torch.where(pre <= 0, torch.zeros_like(pre), pre))), B
+        dw1, db1, dw2, db2 = ops.metanet_backward(dpid, fd, h, W1d, W2d)
+        Hp = (Hd + 63) // 64 * 64
+        hp = torch.zeros(B, Hp, device="cuda")
+        hp[:, :Hd] = h
+        _, dwc, dbc = ops.couple_backward(dpid[None], hp[None], torch.zeros(1, Wt, Hp, device="cuda"), want_x=False)
+        assert torch.equal(bits(dw2), bits(dwc[0, :, :Hd])) and torch.equal(bits(db2), bits(dbc[0])), B
+        dpre = torch.from_numpy(ref.emulate_metanet_dpre(dpi, h, W2)).cuda()
+        _, dwc, dbc = ops.couple_backward(dpre[None], fd.float()[None], W1d[None], want_x=False)
+        assert torch.equal(bits(dw1), bits(dwc[0])) and torch.equal(bits(db1), bits(dbc[0])), B
+
+
 # ---- the meta-net ------------------------------------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("family", ["decades", "cancel"])

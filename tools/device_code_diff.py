@@ -21,20 +21,38 @@ CLASSES = {"mfma": ("v_mfma",), "vmem": ("global_", "buffer_", "flat_"), "lds": 
 RENAMES = (("ce_transpose_kernel", "transpose_kernel"), ("logits_norm_rows_kernel", "norm_rows_kernel"), ("ce_norm_rows_kernel", "norm_rows_kernel"))
 # short new name -> the short names of the parent's kernels it replaces (csrc/pclip_rows.h: the prompt-row kernels of CoOp, VPT and MaPLe)
 MOVED = {"rows_replace_kernel": ("vpt_replace_kernel",),
+         # (the grouped slice sums: the kernels' own earlier names too — two stride arguments more are another mangled name — with CoCoOp's first stage and
+         # the coupling's dX merge)
          "rows_grad_part_kernel<16>": ("prompt_ctx_grad_part_kernel", "vpt_grad_part_kernel", "rows_grad_part_kernel"),
          "rows_grad_part_kernel<1>": ("prompt_ctx_grad_part_kernel",),
-         "rows_grad_sum_kernel": ("prompt_ctx_grad_sum_kernel", "vpt_grad_sum_kernel")}
+         "rows_grad_sum_kernel": ("prompt_ctx_grad_sum_kernel", "vpt_grad_sum_kernel"),
+         # the slice sums with a group flag: the ungrouped instantiations against the kernels' own earlier names, the grouped ones against CoCoOp's first
+         # stage and the coupling's dX merge
+         "rows_grad_part_kernel<16, false>": ("rows_grad_part_kernel<16>",),
+         "rows_grad_part_kernel<1, false>": ("rows_grad_part_kernel<1>",),
+         "rows_grad_part_kernel<16, true>": ("cond_grad_part_kernel",),
+         "rows_grad_sum_kernel<false>": ("rows_grad_sum_kernel",),
+         "rows_grad_sum_kernel<true>": ("couple_dx_sum_kernel",),
+         # csrc/pclip_small_linear.h: the coupling function's and the meta-net's layer walks
+         "rowdot16_kernel<float, false, true>": ("couple_fwd_kernel",),
+         "rowdot16_kernel<half_t, true, false>": ("metanet_l1_kernel",),
+         "small_linear_dw_kernel<float>": ("couple_dw_kernel", "metanet_dw_kernel<float>"),
+         "small_linear_dw_kernel<half_t>": ("metanet_dw_kernel<half_t>",),
+         "small_linear_db_kernel<0>": ("couple_db_kernel", "metanet_db_kernel")}
 TOTAL_TOL = 0.01
 
 
 def short(name):
-    """kernel<1, 4, 8> from _ZN12_GLOBAL__N_1<len>kernelILi1ELi4ELi8EEEv...; other names as they are"""
+    """kernel<1, 4, 8> from _ZN12_GLOBAL__N_1<len>kernelILi1ELi4ELi8EEEv..., kernel<half_t, true> from ...kernelIDF16_Lb1EEEv...; other names as they are"""
     m = re.match(r"_ZN12_GLOBAL__N_1(\d+)", name)
     if not m:
         return name
     base, rest = name[m.end():m.end() + int(m.group(1))], name[m.end() + int(m.group(1)):]
-    targs = re.match(r"I((?:L[a-z]\d+E)+)E", rest)
-    return base + ("<%s>" % ", ".join(re.findall(r"L[a-z](\d+)E", targs.group(1))) if targs else "")
+    targs = re.match(r"I((?:f|DF16_|L[a-z]\d+E)+)E", rest)
+    if not targs:
+        return base
+    args = [{"f": "float", "DF16_": "half_t", "Lb0E": "false", "Lb1E": "true"}.get(a, a[2:-1]) for a in re.findall(r"f|DF16_|L[a-z]\d+E", targs.group(1))]
+    return "%s<%s>" % (base, ", ".join(args))
 
 
 def renamed(name):

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Interleaved A/B of the prompt-row entries (pclip_vpt_replace_f16, pclip_vpt_grad_f32, pclip_rows_replace_f16, pclip_rows_grad_f32,
-pclip_prompt_ctx_grad_f32) between two builds of libpclip (proto-clip_amd/libpclip.so against libpclip_old.so, tools/ab_lib.py's convention), through
-ctypes in one process on the same tensors, at the shapes of tools/vpt_bench.py, tools/maple_bench.py and tools/coop_bench.py.
+pclip_prompt_ctx_grad_f32, pclip_prompt_cond_grad_f32) and of the small fp32 layers (pclip_couple_fwd_f32, pclip_couple_bwd_f32, pclip_metanet_fwd_f32,
+pclip_metanet_bwd_f32) between two builds of libpclip (proto-clip_amd/libpclip.so against libpclip_old.so, tools/ab_lib.py's convention), through ctypes in
+one process on the same tensors, at the shapes of tools/vpt_bench.py, tools/maple_bench.py, tools/coop_bench.py and tools/cocoop_bench.py.
 
     python tools/prompt_rows_ab.py [--rounds 7] [--iters 20] [--out FILE]
 
@@ -21,7 +22,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from kernel_bench import timeit  # noqa: E402
 from proto_clip_amd import _lib  # noqa: E402
 
-ENTRIES = ("pclip_vpt_replace_f16", "pclip_vpt_grad_f32", "pclip_rows_replace_f16", "pclip_rows_grad_f32", "pclip_prompt_ctx_grad_f32")
+ENTRIES = ("pclip_vpt_replace_f16", "pclip_vpt_grad_f32", "pclip_rows_replace_f16", "pclip_rows_grad_f32", "pclip_prompt_ctx_grad_f32", "pclip_couple_fwd_f32",
+           "pclip_couple_bwd_f32", "pclip_metanet_fwd_f32", "pclip_metanet_bwd_f32", "pclip_prompt_cond_grad_f32")
 
 
 def load(name):
@@ -78,6 +80,53 @@ def cases():
             return dx, call
         return make
 
+    def couple(backward, depth, P, Wt, Wv):
+        def make():
+            g = torch.Generator().manual_seed(5)
+            X, Wc, bc, dY = (torch.randn(*s, generator=g).cuda() * k for s, k in (((depth, P, Wt), 0.02), ((depth, Wv, Wt), Wt ** -0.5), ((depth, Wv), 0.05),
+                                                                                  ((depth, P, Wv), 1.0)))
+            nslice = (Wv + _lib.COUPLE_SLICE - 1) // _lib.COUPLE_SLICE
+            Y, dW, db, dX, part = f32(depth, P, Wv), f32(depth, Wv, Wt), f32(depth, Wv), f32(depth, P, Wt), f32(depth, nslice, P * Wt)
+
+            def call(lib, X):
+                if backward:
+                    assert lib.pclip_couple_bwd_f32(P_(dY), P_(X), P_(Wc), depth, P, Wt, Wv, P_(dW), P_(db), P_(dX), P_(part), nslice, st()) == 0
+                    return dW, db, dX
+                assert lib.pclip_couple_fwd_f32(P_(X), P_(Wc), P_(bc), depth, P, Wt, Wv, P_(Y), st()) == 0
+                return (Y,)
+            return X, call
+        return make
+
+    def metanet(backward, B, E, Hd, Wt):
+        def make():
+            g = torch.Generator().manual_seed(6)
+            f = torch.nn.functional.normalize(torch.randn(B, E, generator=g), dim=1).half().cuda()
+            W1, b1, W2, b2, dpi = (torch.randn(*s, generator=g).cuda() * k for s, k in (((Hd, E), E ** -0.5), ((Hd,), 0.05), ((Wt, Hd), Hd ** -0.5), ((Wt,), 0.01),
+                                                                                        ((B, Wt), 1.0)))
+            h_in = torch.relu(f.float() @ W1.t() + b1).contiguous()              # what the backward reads: any hidden layer with zeros in it will do
+            h, pi, dW1, db1, dW2, db2, dpre = f32(B, Hd), f32(B, Wt), f32(Hd, E), f32(Hd), f32(Wt, Hd), f32(Wt), f32(B, Hd)
+
+            def call(lib, f):
+                if backward:
+                    assert lib.pclip_metanet_bwd_f32(P_(dpi), P_(f), P_(h_in), P_(W2), B, E, Hd, Wt, P_(dW1), P_(db1), P_(dW2), P_(db2), P_(dpre), st()) == 0
+                    return dW1, db1, dW2, db2
+                assert lib.pclip_metanet_fwd_f32(P_(f), P_(W1), P_(b1), P_(W2), P_(b2), B, E, Hd, Wt, P_(h), P_(pi), st()) == 0
+                return h, pi
+            return f, call
+        return make
+
+    def cond_grad(B, N, L, n_ctx, W):
+        def make():
+            dx = stream_rows(B * N, L, W, 7)
+            nslice = (N + 15) // 16
+            dshift, dctx, dpi, part = f32(B, n_ctx, W), f32(n_ctx, W), f32(B, W), f32(B, nslice, n_ctx * W) if nslice > 1 else None
+
+            def call(lib, dx):
+                assert lib.pclip_prompt_cond_grad_f32(P_(dx), B, N, L, n_ctx, W, P_(dshift), P_(dctx), P_(dpi), P_(part), nslice, st()) == 0
+                return dctx, dpi, dshift, dx
+            return dx, call
+        return make
+
     out = []
     for B, L0, P, W in ((256, 197, 8, 768), (1024, 50, 8, 768)):                     # tools/vpt_bench.py
         shape = f"{B} x ({L0} + {P}) x {W}"
@@ -91,6 +140,16 @@ def cases():
     out.append((f"rows_grad + clear  {shape}", grad("pclip_rows_grad_f32", B, L, off, P, W, 1)))
     for specific in (False, True):                                                    # tools/coop_bench.py: ImageNet's class names, L_eff = 30
         out.append((f"prompt_ctx_grad    1000 x 30 x 512, n_ctx 16, {'class-specific' if specific else 'shared'}", ctx_grad(1000, 30, 16, 512, specific)))
+    for depth in (9, 12):                                                             # tools/maple_bench.py: the coupling function at ViT-B/16's widths
+        for P in (2, 4):
+            shape = f"depth {depth}, P = {P}, 512 -> 768"
+            out.append((f"couple_fwd         {shape}", couple(False, depth, P, 512, 768)))
+            out.append((f"couple_bwd         {shape}", couple(True, depth, P, 512, 768)))
+    for B in (1, 4, 16):                                                              # tools/cocoop_bench.py: the meta-net and the conditional gradient
+        out.append((f"metanet_fwd        B = {B}, 512 -> 32 -> 512", metanet(False, B, 512, 32, 512)))
+        out.append((f"metanet_bwd        B = {B}, 512 -> 32 -> 512", metanet(True, B, 512, 32, 512)))
+    for B, N in ((4, 1000), (16, 37)):
+        out.append((f"prompt_cond_grad   {B} x {N} x 12 x 512, n_ctx 4", cond_grad(B, N, 12, 4, 512)))
     return out
 
 
