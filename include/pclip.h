@@ -211,6 +211,25 @@ int pclip_cosine_ce_backward_f16(const void* a, int lda, int M, const void* b, i
 #define PCLIP_CE_SYMMETRIC 0x4
 #define PCLIP_CE_LABELS_I64 0x8
 
+/* G independent labelled problems of one shape in ONE call (CoCoOp's per-image classifiers, episodes): group g is a_g = a + g * gsa as [M, D] (rows lda
+ * apart) against b_g = b + g * gsb as [T, D] (rows ldb apart), fp16, the strides counted in halves; labels [G, M] index the rows of the group's OWN b_g.
+ * Outputs (fp32, all required): lse_row [G * M], row_loss [G * M], loss [G] — loss[g] the mean of group g's M terms.
+ * A group's numbers are the bits of pclip_cosine_ce_f16 called on that group alone: the group is a grid dimension of the same walk (same tile order, same
+ * rounding points), nothing crosses groups, and the number of launches does not depend on G.  No atomics; two calls give the same bits.
+ * The envelope of pclip_cosine_ce_f16 per group, and: 1 <= G <= 65535; gsa, gsb multiples of 8 halves (0: the groups share that operand);
+ * PCLIP_CE_SYMMETRIC is refused; ws: pclip_cosine_ce_grouped_workspace(0, G, M, T, D) (PCLIP_E_WORKSPACE if smaller).  Everything else is
+ * PCLIP_E_INVALID before any launch. */
+int pclip_cosine_ce_grouped_f16(const void* a, int lda, size_t gsa, int M, const void* b, int ldb, size_t gsb, int T, int D, int G, float scale, int flags,
+                                const void* labels, float* lse_row, float* row_loss, float* loss, void* ws, size_t ws_bytes, pclip_stream_t stream);
+/* The gradients of the above, group by group those of pclip_cosine_ce_backward_f16 (labelled) with the one `weight` for every group:
+ *   direction 0: grad [G, M, D] fp32 dense = dL_g/da_g;  direction 1: grad [G, T, D] fp32 dense = dL_g/db_g, its walk chunked by the plain call's rule.
+ * dscale (nullable, [G] fp32): group g's sum G o cos.  lse_row [G * M] as the forward wrote it.  ws: pclip_cosine_ce_grouped_workspace(1, G, M, T, D). */
+int pclip_cosine_ce_grouped_backward_f16(const void* a, int lda, size_t gsa, int M, const void* b, int ldb, size_t gsb, int T, int D, int G, float scale,
+                                         int flags, const void* labels, const float* lse_row, float weight, int direction, float* grad, float* dscale,
+                                         void* ws, size_t ws_bytes, pclip_stream_t stream);
+/* G times pclip_workspace_bytes(PCLIP_OP_COSINE_CE [backward: _BACKWARD], M, T, D): at G = 1 the plain call's size.  0 for G < 1. */
+size_t pclip_cosine_ce_grouped_workspace(int backward, int G, int M, int T, int D);
+
 /* ---- the pairwise sigmoid (SigLIP) loss over cosine logits, multi-positive by ids (clip/model.py:356-370 gives the logits) ------------- */
 
 /* x[m, t] = fma(scale, cos[m, t], bias) in fp32, cos = the fp32 matrix-pipe accumulation of a'[m, :] . b'[t, :], one accumulator over k = 0, 32, ... on every

@@ -68,6 +68,10 @@ _SIGS = {
     "pclip_cosine_logits_f16": [_P, c_int, c_int, _P, c_int, c_int, c_int, c_float, c_int, _P, c_int, _P, _P, _P, c_int, _P, c_size_t, _P],
     "pclip_cosine_ce_f16": [_P, c_int, c_int, _P, c_int, c_int, c_int, c_float, c_int, _P, _P, _P, _P, _P, _P, c_size_t, _P],
     "pclip_cosine_ce_backward_f16": [_P, c_int, c_int, _P, c_int, c_int, c_int, c_float, c_int, _P, _P, _P, c_float, c_int, _P, _P, _P, c_size_t, _P],
+    "pclip_cosine_ce_grouped_f16": [_P, c_int, c_size_t, c_int, _P, c_int, c_size_t, c_int, c_int, c_int, c_float, c_int, _P, _P, _P, _P, _P, c_size_t, _P],
+    "pclip_cosine_ce_grouped_backward_f16": [_P, c_int, c_size_t, c_int, _P, c_int, c_size_t, c_int, c_int, c_int, c_float, c_int, _P, _P, c_float, c_int, _P, _P,
+                                             _P, c_size_t, _P],
+    "pclip_cosine_ce_grouped_workspace": [c_int, c_int, c_int, c_int, c_int],
     "pclip_cosine_sigmoid_f16": [_P, c_int, c_int, _P, c_int, c_int, c_int, c_float, c_float, c_int, _P, _P, _P, _P, _P, c_size_t, _P],
     "pclip_cosine_sigmoid_backward_f16": [_P, c_int, c_int, _P, c_int, c_int, c_int, c_float, c_float, c_int, _P, _P, c_float, c_int, _P, _P, _P, _P, c_size_t, _P],
     "pclip_tip_logits_f16": [_P, c_int, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_float, c_float, c_float, _P, c_int, _P, _P, _P],
@@ -157,7 +161,7 @@ _SIGS = {
     "pclip_preprocess_u8": [_P, _P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, _P, c_int, _P, _P],
     "pclip_workspace_bytes": [c_int, c_int, c_int, c_int],
 }
-_RESTYPES = {"pclip_last_error": c_char_p, "pclip_workspace_bytes": c_size_t, "pclip_gemm_splitk_workspace": c_size_t, "pclip_gemm_kernel_launches": c_long}
+_RESTYPES = {"pclip_last_error": c_char_p, "pclip_workspace_bytes": c_size_t, "pclip_gemm_splitk_workspace": c_size_t, "pclip_cosine_ce_grouped_workspace": c_size_t, "pclip_gemm_kernel_launches": c_long}
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
 

@@ -14,6 +14,7 @@ belong to (fp16 parameters get fp16 gradients, as autograd on the reference's fp
 
 Not differentiated: the INPUT of the conv adapter (the reference feeds it constants: rows of the frozen key bank, main.py:265-266,
 or encode_image outputs under no_grad, main.qt.py:199-201) — asking for it raises."""
+import numpy as np
 import torch
 
 from . import ops
@@ -229,6 +230,53 @@ def cosine_cross_entropy(a, b, scale, labels=None, symmetric=False, normalize_a=
     b16 = b if b.dtype == torch.float16 else ops.cast_f16(b.detach().float().contiguous())
     s = float(scale.detach()) if isinstance(scale, torch.Tensor) else float(scale)
     return ops.cosine_cross_entropy(a16.detach(), b16.detach(), s, labels, symmetric, normalize_a, normalize_b)[0]
+
+
+def _f16_operand(t):
+    return t if t.dtype == torch.float16 else ops.cast_f16(t.float().contiguous())
+
+
+class GroupedCosineCeFn(torch.autograd.Function):
+    """G independent labelled cross-entropies over cosine logits in one call (ops.cosine_cross_entropy_grouped): a [G, M, D] (or [G, D]), b [G, T, D],
+    labels [G, M].  Returns the [G] VECTOR of group losses — the caller chooses the reduction — each the bits of `CosineCeFn` on that group alone.
+    The backward takes g [G], runs the grouped backward with weight 1 / M and multiplies group q's gradient by g[q] in fp32 (one broadcast multiply), then
+    casts back as `CosineCeFn` does.  A 0-dim tensor `scale` receives sum_q g[q] * dscale[q]: the products rounded to fp32, then added one by one in
+    ASCENDING q in fp32 (on the host: the tensor-scale path reads the scale's value there anyway — one more sync, and no graph capture)."""
+
+    @staticmethod
+    def forward(ctx, a, b, scale, labels, normalize_a, normalize_b):
+        a16, b16 = _f16_operand(a), _f16_operand(b)
+        ctx.scale = float(scale.detach()) if isinstance(scale, torch.Tensor) else float(scale)
+        ctx.mode = (bool(normalize_a), bool(normalize_b))
+        ctx.refs = tuple((t.dtype, t.shape) if isinstance(t, torch.Tensor) else None for t in (a, b, scale))      # what each gradient is cast back to
+        loss, lse_row, _ = ops.cosine_cross_entropy_grouped(a16, b16, ctx.scale, labels, *ctx.mode)
+        ctx.save_for_backward(a16, b16, lse_row, labels)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        a16, b16, lse_row, labels = ctx.saved_tensors
+        need_a, need_b, need_s = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        ga, gb, gs = ops.cosine_cross_entropy_grouped_backward(a16, b16, ctx.scale, lse_row, labels, *ctx.mode, want_a=need_a, want_b=need_b, want_scale=need_s)
+        g = g.float()
+
+        def cast(t, ref):
+            if t is None:
+                return None
+            t = (t * g.view(-1, 1, 1)).reshape(ref[1])
+            return ops.cast_f16(t.contiguous()) if ref[0] == torch.float16 else t.to(ref[0])
+        if need_s:
+            total = np.cumsum((gs * g).cpu().numpy(), dtype=np.float32)[-1]                           # ((p0 + p1) + p2) + ..: numpy accumulates in index order
+            gs = torch.full(ctx.refs[2][1], float(total), dtype=torch.float32, device=g.device).to(ctx.refs[2][0])
+        return (cast(ga, ctx.refs[0]) if need_a else None, cast(gb, ctx.refs[1]) if need_b else None, gs if need_s else None, None, None, None)
+
+
+def cosine_cross_entropy_grouped(a, b, scale, labels, normalize_a=False, normalize_b=False):
+    """The [G] losses of `GroupedCosineCeFn` with a tape where one is wanted, the bare forward under torch.no_grad() or for constants."""
+    if wants_grad(a, b, scale if isinstance(scale, torch.Tensor) else None):
+        return GroupedCosineCeFn.apply(a, b, scale, labels, normalize_a, normalize_b)
+    s = float(scale.detach()) if isinstance(scale, torch.Tensor) else float(scale)
+    return ops.cosine_cross_entropy_grouped(_f16_operand(a.detach()), _f16_operand(b.detach()), s, labels, normalize_a, normalize_b)[0]
 
 
 class CosineSigmoidFn(torch.autograd.Function):

@@ -152,13 +152,12 @@ class CoCoOp(torch.nn.Module):
         return self.learner(features)
 
     def loss(self, features, labels):
-        """mean over the images of the cross-entropy of logit_scale.exp() * normalise(features[b]) . normalise(text[b, :]) against labels[b]: one call of
-        the one-row cosine cross-entropy per image, the [B, N] logits are never written."""
+        """mean over the images of the cross-entropy of logit_scale.exp() * normalise(features[b]) . normalise(text[b, :]) against labels[b]: the B
+        one-row cosine cross-entropies as the groups of ONE grouped call (features [B, 1, D] against text [B, N, E]), each with the bits of the single
+        call on that image; the [B, N] logits are never written."""
         text, scale = self.learner(features), self.logit_scale()
         labels = labels.to(features.device).long()
-        terms = [pag.cosine_cross_entropy(features[b:b + 1].contiguous(), text[b], scale, labels=labels[b:b + 1], normalize_a=True, normalize_b=True)
-                 for b in range(features.shape[0])]
-        return torch.stack([t.reshape(()) for t in terms]).mean()
+        return pag.cosine_cross_entropy_grouped(features.unsqueeze(1), text, scale, labels.view(-1, 1), normalize_a=True, normalize_b=True).mean()
 
     def classify(self, features, topk=0):
         """arg-max class (int64 [Q]) of every image against ITS OWN N text rows, image chunk by image chunk; with topk > 0 also the top-k values and

@@ -21,6 +21,9 @@
 //   Under NORMALIZE the panel gradient is chained through x / ||x|| by ce_norm_backward_kernel in fp32 (the fp16 rounding of x' taken as the identity).
 // Every workgroup walks ALL walked rows in index order and an element has one accumulator: a row's lse, loss term and gradient do not depend on RF, the grid or
 // (labelled, direction 0) the other rows; where the own rows are few panels, the walked tiles are shared between workgroups in fixed chunks (ce_chunks).
+// Groups (pclip_cosine_ce_grouped_f16 / _backward_f16, labelled mode): G problems of one shape are the GROUPED instantiations of the same kernels with the
+// group as a grid dimension — a base offset in front of the same walk, so a group's bits are the single call's — and every helper pass (row norms, transpose,
+// chunk sum, norm backward, the means and dscale sums) is issued once for all groups: the launches of a call do not depend on G.
 // Only __syncthreads barriers and compiler-counted waits: nothing here for the race-stress build.
 #include "pclip_panel_walk.h"
 
@@ -69,10 +72,28 @@ __device__ __forceinline__ void load_panel(half_t* panel, int LDP, const half_t*
     }
 }
 
-template <int NCH, int RF>
+// element i of a label vector of either width
+__device__ __forceinline__ const void* labels_at(const void* labels, int i64, size_t i) {
+    return i64 ? (const void*)(reinterpret_cast<const int64_t*>(labels) + i) : (const void*)(reinterpret_cast<const int32_t*>(labels) + i);
+}
+
+// GROUPED (pclip_cosine_ce_grouped_f16), launched over grid (panels, 1, G): G labelled forward walks of one shape in one launch.
+//   What is walked: by workgroup (p, g), panel p of a_g = a + g gsa ([M, D], rows lda apart) against ALL rows of b_g = b + g gsb ([T, D], rows ldb apart),
+//   with the labels, lse, target and loss rows of the group at g M.
+//   The order: this kernel's own — 64-column blocks dealt to the CE_FW waves, k ascending, a row's lane groups then its waves merged in a fixed order.
+//   The rounding points: those of the list at the head of this file, unchanged (cos an fp32 MFMA accumulation, s = scale * cos in fp32, nothing to fp16).
+//   blockIdx.z is the GROUP and nothing else: the bases are advanced once, in size_t, before the walk; no value crosses groups, so group g's numbers are
+//   the bits of the ungrouped launch on (a_g, b_g) alone.  The ungrouped instantiation reads neither stride (the habit of pclip_rows.h).
+template <int NCH, int RF, bool GROUPED = false>
 __global__ __launch_bounds__(64 * CE_FW) void ce_fwd_kernel(const half_t* __restrict__ a, int lda, int M, const half_t* __restrict__ b, int ldb, int T, int D, float scale,
                                                      int norm_a, int symmetric, const void* __restrict__ labels, int lab64, float* __restrict__ lse_row,
-                                                     float* __restrict__ tgt, float* __restrict__ row_loss, float2* __restrict__ colpart) {
+                                                     float* __restrict__ tgt, float* __restrict__ row_loss, float2* __restrict__ colpart, size_t gsa, size_t gsb) {
+    if (GROUPED) {
+        const size_t g = blockIdx.z, r0 = g * M;
+        a += g * gsa, b += g * gsb;
+        labels = labels_at(labels, lab64, r0);
+        lse_row += r0, tgt += r0, row_loss += r0;
+    }
     extern __shared__ __attribute__((aligned(16))) char ce_smem[];
     __shared__ float red[CE_FW][RF][16][3];
     half_t* panel = reinterpret_cast<half_t*>(ce_smem);                                      // [16 RF][D + 8]
@@ -214,8 +235,13 @@ __global__ __launch_bounds__(256) void ce_col_combine_kernel(const float2* __res
     row_loss[t] = 0.5f * ((lse_row[t] - tgt[t]) + (lc - tgt[t]));
 }
 
-// out[0] = mul * sum x[0 .. n), one workgroup, fp64, a fixed order
+// out[0] = mul * sum x[0 .. n), one workgroup, fp64, a fixed order.  GROUPED, launched with G workgroups: out[g] = mul * sum x[g n .. g n + n), each in that order
+template <bool GROUPED = false>
 __global__ __launch_bounds__(256) void ce_sum_kernel(const float* __restrict__ x, int n, double mul, float* __restrict__ out) {
+    if (GROUPED) {
+        x += (size_t)blockIdx.x * n;
+        out += blockIdx.x;
+    }
     __shared__ double part[256];
     double s = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) s += (double)x[i];
@@ -228,8 +254,13 @@ __global__ __launch_bounds__(256) void ce_sum_kernel(const float* __restrict__ x
     if (threadIdx.x == 0) out[0] = (float)(mul * part[0]);
 }
 
-// out = sum over the chunks of part [nchunks][n], in chunk order (n % 4 == 0)
+// out = sum over the chunks of part [nchunks][n], in chunk order (n % 4 == 0).  GROUPED, grid (flat, G): part [G][nchunks][n] -> out [G][n], group blockIdx.y
+template <bool GROUPED = false>
 __global__ __launch_bounds__(256) void ce_sum_chunks_kernel(const float* __restrict__ part, int nchunks, size_t n, float* __restrict__ out) {
+    if (GROUPED) {
+        part += blockIdx.y * (nchunks * n);
+        out += blockIdx.y * n;
+    }
     for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (size_t)gridDim.x * 256 * 4) {
         float4_t s = *reinterpret_cast<const float4_t*>(part + i);
         for (int c = 1; c < nchunks; ++c) s += *reinterpret_cast<const float4_t*>(part + (size_t)c * n + i);
@@ -241,12 +272,34 @@ __global__ __launch_bounds__(256) void ce_sum_chunks_kernel(const float* __restr
 // Of the shared skeleton of pclip_panel_walk.h this kernel calls bwd_second_product and store_grad_panel.  Its staging, its first product and its wt0 prefetch are
 // written out (the text of bwd_first_product / bwd_prefetch_t): each of them behind the shared function re-rolled the register allocation of the RF = 4 form and
 // cost 0.5 - 0.9 % at 32768^2 (profiles/panel_walk_refactor.txt, section 5).  A change to the backward walk is made here and in the header.
-template <int NCH, int RF, int NDF>
+//
+// GROUPED (pclip_cosine_ce_grouped_backward_f16), launched over grid (panels, chunks, G): G labelled backward walks of one shape in one launch.
+//   What is walked: by workgroup (p, c, g), panel p of the own rows of group g against chunk c of THAT group's walked tiles — ce_chunks is a function of
+//   (Ro, Rw, D) and so the same for every group — into the group's own gradient panel (or chunk partial) and dscale partial.
+//   The order: this kernel's own (walked tiles ascending within a chunk, k ascending, one accumulator per element).
+//   The rounding points: those of the list at the head of this file, unchanged (2^14 E to fp16 once; weight, scale and the target term in fp32).
+//   blockIdx.z is the GROUP and nothing else: every base is advanced once by g times its stride (CeBwdStrides, size_t) before the walk; nothing is added
+//   across groups, so group g's numbers are the bits of the ungrouped launch on that group alone.  The ungrouped instantiation does not read the strides.
+struct CeBwdStrides {             // from group g to group g + 1, in elements
+    size_t own, walk, walkT;      // halves: the operands as the kernel reads them (the walked one possibly its normalised copy) and the walked transposes
+    size_t rows;                  // = M: the labels and the row lse belong to the a side, whichever side is own
+    size_t gout, dsc;             // floats: the gradient panels (chunks x Ro x D where the walk is chunked, Ro x D otherwise), the dscale partials
+};
+template <int NCH, int RF, int NDF, bool GROUPED = false>
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const half_t* __restrict__ own, int ldo, int Ro, const half_t* __restrict__ walk, int ldw, int Rw,
                                                      const half_t* __restrict__ walkT, int ldt, int D, float scale, float weight, int norm_own, int symmetric,
                                                      const void* __restrict__ lab_own, const void* __restrict__ lab_walk, int lab64,
                                                      const float* __restrict__ lse_own, const float* __restrict__ lse_walk, float* __restrict__ gout,
-                                                     float* __restrict__ dsc_part) {
+                                                     float* __restrict__ dsc_part, CeBwdStrides gs) {
+    if (GROUPED) {
+        const size_t g = blockIdx.z, r0 = g * gs.rows;
+        own += g * gs.own, walk += g * gs.walk, walkT += g * gs.walkT, gout += g * gs.gout;
+        if (lab_own) lab_own = labels_at(lab_own, lab64, r0);
+        if (lab_walk) lab_walk = labels_at(lab_walk, lab64, r0);
+        if (lse_own) lse_own += r0;
+        if (lse_walk) lse_walk += r0;
+        if (dsc_part) dsc_part += g * gs.dsc;
+    }
     extern __shared__ __attribute__((aligned(16))) char ce_smem[];
     const int LDP = D + PW_PAD;
     half_t* panel = reinterpret_cast<half_t*>(ce_smem);                                      // [16 RF][D + 8]
@@ -366,8 +419,13 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const half_t* __restrict__ 
 }
 
 // g <- (g - y (y . g)) / ||x||, y = x / ||x|| in fp32: the gradient of x -> x / ||x|| applied to a row of dL/dx' in place (one wave per row)
-template <int NCH>
-__global__ __launch_bounds__(256) void ce_norm_backward_kernel(const half_t* __restrict__ x, int ldx, float* __restrict__ g, int R, int D) {
+// GROUPED, launched with gridDim.y = G: the rows of G operands of R rows each, group blockIdx.y's x at x + blockIdx.y gsx, its gradient the dense [R, D] block of g
+template <int NCH, bool GROUPED = false>
+__global__ __launch_bounds__(256) void ce_norm_backward_kernel(const half_t* __restrict__ x, int ldx, float* __restrict__ g, int R, int D, size_t gsx) {
+    if (GROUPED) {
+        x += blockIdx.y * gsx;
+        g += blockIdx.y * ((size_t)R * D);
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int row = blockIdx.x * 4 + wave; row < R; row += gridDim.x * 4) {
         RowRegs<NCH> rr;
@@ -507,7 +565,7 @@ extern "C" int pclip_cosine_ce_f16(const void* a, int lda, int M, const void* b,
             static DevOnce attr;
             if (int e = pclip_raise_lds(attr, {(const void*)ce_fwd_kernel<nch, rf>}, CE_LDS_MAX, fn)) return e;
             ce_fwd_kernel<nch, rf><<<npanels, 64 * CE_FW, lds, s>>>((const half_t*)a, lda, M, bw, ldbw, T, D, scale, (flags & PCLIP_CE_NORMALIZE_A) ? 1 : 0, symmetric, labels,
-                                                                   (flags & PCLIP_CE_LABELS_I64) ? 1 : 0, lse_row, tgt, row_loss, colpart);
+                                                                   (flags & PCLIP_CE_LABELS_I64) ? 1 : 0, lse_row, tgt, row_loss, colpart, 0, 0);
             return pclip_check_launch("cosine_ce");
         }))
         return e;
@@ -515,7 +573,7 @@ extern "C" int pclip_cosine_ce_f16(const void* a, int lda, int M, const void* b,
         ce_col_combine_kernel<<<ceil_div(T, 256), 256, 0, s>>>(colpart, npanels, T, lse_row, tgt, lse_col, row_loss);
         if (int e = pclip_check_launch("cosine_ce (columns)")) return e;
     }
-    ce_sum_kernel<<<1, 256, 0, s>>>(row_loss, M, 1.0 / M, loss);
+    ce_sum_kernel<><<<1, 256, 0, s>>>(row_loss, M, 1.0 / M, loss);
     return pclip_check_launch("cosine_ce (mean)");
 }
 
@@ -562,7 +620,7 @@ extern "C" int pclip_cosine_ce_backward_f16(const void* a, int lda, int M, const
             static DevOnce attr;
             if (int e = pclip_raise_lds(attr, {(const void*)ce_bwd_kernel<nch, rf, ndf>}, CE_LDS_MAX, fn)) return e;
             ce_bwd_kernel<nch, rf, ndf><<<grid, 256, lds, s>>>(own, ldo, Ro, walk, ldw, Rw, walkT, ldt, D, scale, weight, norm_own, symmetric, lab_own, lab_walk,
-                                                              (flags & PCLIP_CE_LABELS_I64) ? 1 : 0, lse_own, lse_walk, gpanel, dsc_part);
+                                                              (flags & PCLIP_CE_LABELS_I64) ? 1 : 0, lse_own, lse_walk, gpanel, dsc_part, CeBwdStrides{});
             return pclip_check_launch("cosine_ce_backward");
         }))
         return e;
@@ -570,20 +628,141 @@ extern "C" int pclip_cosine_ce_backward_f16(const void* a, int lda, int M, const
         const size_t n = (size_t)Ro * D;
         size_t g = (n / 4 + 255) / 256;
         g = g > 4096 ? 4096 : g;
-        ce_sum_chunks_kernel<<<(int)g, 256, 0, s>>>(gpanel, nchunks, n, grad);
+        ce_sum_chunks_kernel<><<<(int)g, 256, 0, s>>>(gpanel, nchunks, n, grad);
         if (int e = pclip_check_launch("cosine_ce_backward (chunks)")) return e;
     }
     if (norm_own) {
         int g = ceil_div(Ro, 4);
         g = g > 8192 ? 8192 : g;
-        if (D <= 512) ce_norm_backward_kernel<1><<<g, 256, 0, s>>>(own, ldo, grad, Ro, D);
-        else if (D <= 1024) ce_norm_backward_kernel<2><<<g, 256, 0, s>>>(own, ldo, grad, Ro, D);
-        else ce_norm_backward_kernel<4><<<g, 256, 0, s>>>(own, ldo, grad, Ro, D);
+        if (D <= 512) ce_norm_backward_kernel<1><<<g, 256, 0, s>>>(own, ldo, grad, Ro, D, 0);
+        else if (D <= 1024) ce_norm_backward_kernel<2><<<g, 256, 0, s>>>(own, ldo, grad, Ro, D, 0);
+        else ce_norm_backward_kernel<4><<<g, 256, 0, s>>>(own, ldo, grad, Ro, D, 0);
         if (int e = pclip_check_launch("cosine_ce_backward (row norms)")) return e;
     }
     if (dscale) {
-        ce_sum_kernel<<<1, 256, 0, s>>>(dsc_part, npanels * nchunks, 1.0, dscale);
+        ce_sum_kernel<><<<1, 256, 0, s>>>(dsc_part, npanels * nchunks, 1.0, dscale);
         if (int e = pclip_check_launch("cosine_ce_backward (dscale)")) return e;
+    }
+    return PCLIP_OK;
+}
+
+// ---- G independent labelled problems of one shape in one call: group g is (a + g gsa [M, D], b + g gsb [T, D], labels + g M) ----------------------------
+// Every launch below covers all groups (the group is a grid dimension of each), so a call issues the launches of ONE plain call whatever G.  The workspace is the plain call's G times over, region by region: each region holds its G per-group pieces densely, one behind the other.
+
+extern "C" size_t pclip_cosine_ce_grouped_workspace(int backward, int G, int M, int T, int D) {
+    if (G < 1) return 0;
+    return (size_t)G * pclip_cosine_ce_workspace(backward, M, T, D);
+}
+
+namespace {
+int ce_grouped_validate(const char* fn, const void* a, int lda, size_t gsa, int M, const void* b, int ldb, size_t gsb, int T, int D, int G, int flags,
+                        const void* labels, const void* ws, size_t ws_bytes, int backward) {
+    PCLIP_REQUIRE(G >= 1 && G <= 65535, "%s: G=%d must be in 1 .. 65535 (the groups are the grid's z dimension)", fn, G);
+    PCLIP_REQUIRE(!(flags & PCLIP_CE_SYMMETRIC), "%s: PCLIP_CE_SYMMETRIC is not supported in groups (labelled mode only)", fn);
+    PCLIP_REQUIRE(gsa % 8 == 0 && gsb % 8 == 0, "%s: the group strides gsa=%zu and gsb=%zu must be multiples of 8 halves", fn, gsa, gsb);
+    return ce_validate(fn, a, lda, M, b, ldb, T, D, flags, labels, ws, ws_bytes, pclip_cosine_ce_grouped_workspace(backward, G, M, T, D));
+}
+}  // namespace
+
+extern "C" int pclip_cosine_ce_grouped_f16(const void* a, int lda, size_t gsa, int M, const void* b, int ldb, size_t gsb, int T, int D, int G, float scale,
+                                           int flags, const void* labels, float* lse_row, float* row_loss, float* loss, void* ws, size_t ws_bytes,
+                                           pclip_stream_t stream) {
+    const char* fn = "pclip_cosine_ce_grouped_f16";
+    if (int e = ce_grouped_validate(fn, a, lda, gsa, M, b, ldb, gsb, T, D, G, flags, labels, ws, ws_bytes, 0)) return e;
+    PCLIP_REQUIRE(lse_row && row_loss && loss, "%s: lse_row, row_loss and loss are required", fn);
+    hipStream_t s = (hipStream_t)stream;
+    const CeFwdWs w = ce_fwd_ws(M, T, D);
+    char* wsb = (char*)ws;
+    const half_t* bw = (const half_t*)b;
+    int ldbw = ldb;
+    size_t gsbw = gsb;
+    if (flags & PCLIP_CE_NORMALIZE_B) {
+        half_t* bn = (half_t*)(wsb + (size_t)G * w.bn);
+        if (int e = launch_norm_rows_grouped<CE_DMAX>((const half_t*)b, ldb, gsb, bn, T, D, G, s, "cosine_ce_grouped (row norms)")) return e;
+        bw = bn, ldbw = D, gsbw = (size_t)T * D;
+    }
+    const int RF = ce_rf_fwd(M, D), npanels = ceil_div(M, 16 * RF);
+    const size_t lds = (size_t)16 * RF * (D + PW_PAD) * 2;
+    float* tgt = (float*)(wsb + (size_t)G * w.tgt);
+    if (int e = panel_dispatch(D, RF, [&](auto nch, auto rf, auto) -> int {
+            static DevOnce attr;
+            if (int e = pclip_raise_lds(attr, {(const void*)ce_fwd_kernel<nch, rf, true>}, CE_LDS_MAX, fn)) return e;
+            ce_fwd_kernel<nch, rf, true><<<dim3(npanels, 1, G), 64 * CE_FW, lds, s>>>((const half_t*)a, lda, M, bw, ldbw, T, D, scale,
+                                                                                      (flags & PCLIP_CE_NORMALIZE_A) ? 1 : 0, 0, labels,
+                                                                                      (flags & PCLIP_CE_LABELS_I64) ? 1 : 0, lse_row, tgt, row_loss, nullptr, gsa, gsbw);
+            return pclip_check_launch("cosine_ce_grouped");
+        }))
+        return e;
+    ce_sum_kernel<true><<<G, 256, 0, s>>>(row_loss, M, 1.0 / M, loss);
+    return pclip_check_launch("cosine_ce_grouped (means)");
+}
+
+extern "C" int pclip_cosine_ce_grouped_backward_f16(const void* a, int lda, size_t gsa, int M, const void* b, int ldb, size_t gsb, int T, int D, int G,
+                                                    float scale, int flags, const void* labels, const float* lse_row, float weight, int direction, float* grad,
+                                                    float* dscale, void* ws, size_t ws_bytes, pclip_stream_t stream) {
+    const char* fn = "pclip_cosine_ce_grouped_backward_f16";
+    if (int e = ce_grouped_validate(fn, a, lda, gsa, M, b, ldb, gsb, T, D, G, flags, labels, ws, ws_bytes, 1)) return e;
+    PCLIP_REQUIRE(direction == 0 || direction == 1, "%s: direction=%d must be 0 (dL/da) or 1 (dL/db)", fn, direction);
+    PCLIP_REQUIRE(lse_row && grad, "%s: lse_row and grad are required", fn);
+    PCLIP_REQUIRE((uintptr_t)grad % 16 == 0, "%s: grad must be 16-byte aligned", fn);
+    hipStream_t s = (hipStream_t)stream;
+    const CeBwdWs w = ce_bwd_ws(M, T, D);
+    char* wsb = (char*)ws;
+    // own = the side whose gradient this call produces, walked = the other (as in pclip_cosine_ce_backward_f16, labelled)
+    const half_t* own = (const half_t*)(direction ? b : a);
+    const half_t* walk = (const half_t*)(direction ? a : b);
+    const int ldo = direction ? ldb : lda, Ro = direction ? T : M, Rw = direction ? M : T;
+    int ldw = direction ? lda : ldb;
+    const size_t gso = direction ? gsb : gsa;
+    size_t gsw = direction ? gsa : gsb;
+    const int norm_own = (flags & (direction ? PCLIP_CE_NORMALIZE_B : PCLIP_CE_NORMALIZE_A)) ? 1 : 0;
+    const int norm_walk = (flags & (direction ? PCLIP_CE_NORMALIZE_A : PCLIP_CE_NORMALIZE_B)) ? 1 : 0;
+    const float* lse_own = direction ? nullptr : lse_row;
+    const float* lse_walk = direction ? lse_row : nullptr;
+    const void* lab_own = direction == 0 ? labels : nullptr;
+    const void* lab_walk = direction == 1 ? labels : nullptr;
+    if (norm_walk) {
+        half_t* wn = (half_t*)(wsb + (size_t)G * w.wn);
+        if (int e = launch_norm_rows_grouped<CE_DMAX>(walk, ldw, gsw, wn, Rw, D, G, s, "cosine_ce_grouped (row norms)")) return e;
+        walk = wn, ldw = D, gsw = (size_t)Rw * D;
+    }
+    half_t* walkT = (half_t*)(wsb + (size_t)G * w.wt);
+    const int ldt = round64(Rw);
+    if (int e = launch_transpose_grouped(walk, ldw, gsw, Rw, D, G, walkT, ldt, s, "cosine_ce_grouped_backward (transpose)")) return e;
+
+    const int RF = rf_for(Ro, D), npanels = ceil_div(Ro, 16 * RF);
+    const int nchunks = ce_chunks(Ro, Rw, D, direction == 1);
+    const size_t n = (size_t)Ro * D;
+    float* gpanel = nchunks > 1 ? (float*)(wsb + (size_t)G * w.part) : grad;
+    const size_t lds = (size_t)16 * RF * (D + PW_PAD) * 2 + (size_t)4 * 16 * RF * PW_PLD * 2 + 8 * sizeof(int) + 4 * sizeof(float);
+    float* dsc_part = dscale ? (float*)(wsb + (size_t)G * w.dsc) : nullptr;
+    const CeBwdStrides gs = {gso, gsw, (size_t)D * ldt, (size_t)M, (size_t)nchunks * n, (size_t)npanels * nchunks};
+    if (int e = panel_dispatch(D, RF, [&](auto nch, auto rf, auto ndf) -> int {
+            static DevOnce attr;
+            if (int e = pclip_raise_lds(attr, {(const void*)ce_bwd_kernel<nch, rf, ndf, true>}, CE_LDS_MAX, fn)) return e;
+            ce_bwd_kernel<nch, rf, ndf, true><<<dim3(npanels, nchunks, G), 256, lds, s>>>(own, ldo, Ro, walk, ldw, Rw, walkT, ldt, D, scale, weight, norm_own, 0, lab_own,
+                                                                                          lab_walk, (flags & PCLIP_CE_LABELS_I64) ? 1 : 0, lse_own, lse_walk, gpanel,
+                                                                                          dsc_part, gs);
+            return pclip_check_launch("cosine_ce_grouped_backward");
+        }))
+        return e;
+    if (nchunks > 1) {
+        size_t g = (n / 4 + 255) / 256;
+        g = g > 4096 ? 4096 : g;
+        ce_sum_chunks_kernel<true><<<dim3((int)g, G), 256, 0, s>>>(gpanel, nchunks, n, grad);
+        if (int e = pclip_check_launch("cosine_ce_grouped_backward (chunks)")) return e;
+    }
+    if (norm_own) {
+        int g = ceil_div(Ro, 4);
+        g = g > 8192 ? 8192 : g;
+        if (D <= 512) ce_norm_backward_kernel<1, true><<<dim3(g, G), 256, 0, s>>>(own, ldo, grad, Ro, D, gso);
+        else if (D <= 1024) ce_norm_backward_kernel<2, true><<<dim3(g, G), 256, 0, s>>>(own, ldo, grad, Ro, D, gso);
+        else ce_norm_backward_kernel<4, true><<<dim3(g, G), 256, 0, s>>>(own, ldo, grad, Ro, D, gso);
+        if (int e = pclip_check_launch("cosine_ce_grouped_backward (row norms)")) return e;
+    }
+    if (dscale) {
+        ce_sum_kernel<true><<<G, 256, 0, s>>>(dsc_part, npanels * nchunks, 1.0, dscale);
+        if (int e = pclip_check_launch("cosine_ce_grouped_backward (dscale)")) return e;
     }
     return PCLIP_OK;
 }

@@ -75,8 +75,14 @@ __device__ __forceinline__ void stage_panel(half_t* panel, int LDP, const half_t
 }
 
 // rows normalised into a workspace (dense [R, D]): the walked operand under a normalise flag
-template <int NCH>
-__global__ __launch_bounds__(256) void norm_rows_kernel(const half_t* __restrict__ x, int ldx, half_t* __restrict__ y, int R, int D) {
+// GROUPED, launched with gridDim.y = G: G operands of R rows each in one launch, group blockIdx.y reading at x + blockIdx.y gsx and writing its dense
+// [R, D] block of y [G R, D].  The ungrouped instantiation does not read gsx (the habit of pclip_rows.h).
+template <int NCH, bool GROUPED = false>
+__global__ __launch_bounds__(256) void norm_rows_kernel(const half_t* __restrict__ x, int ldx, half_t* __restrict__ y, int R, int D, size_t gsx) {
+    if (GROUPED) {
+        x += blockIdx.y * gsx;
+        y += blockIdx.y * ((size_t)R * D);
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int row = blockIdx.x * 4 + wave; row < R; row += gridDim.x * 4) {
         RowRegs<NCH> r;
@@ -215,9 +221,14 @@ __device__ __forceinline__ void store_grad_panel(float* __restrict__ gout, int i
 
 // y [D][ldt] = x^T, 64 x 64 tiles through LDS; rows R .. ldt - 1 of x read as zeros (ldt = R rounded up to 64: every column of y is written)
 // (a template, TS = 64 the one tile size: only the files that launch it instantiate it)
-template <int TS>
-__global__ __launch_bounds__(256) void transpose_kernel(const half_t* __restrict__ x, int ldx, int R, half_t* __restrict__ y, int ldt) {
+// GROUPED, launched with gridDim.z = G: G transposes of one shape, group blockIdx.z from x + blockIdx.z gsx into its dense [D][ldt] block of y.
+template <int TS, bool GROUPED = false>
+__global__ __launch_bounds__(256) void transpose_kernel(const half_t* __restrict__ x, int ldx, int R, half_t* __restrict__ y, int ldt, size_t gsx) {
     static_assert(TS == 64, "transpose_kernel: 64 x 64 tiles");
+    if (GROUPED) {
+        x += blockIdx.z * gsx;
+        y += blockIdx.z * ((size_t)gridDim.y * 64 * ldt);
+    }
     __shared__ half_t tile[64][66];
     const int r0 = blockIdx.x * 64, d0 = blockIdx.y * 64;
     for (int i = threadIdx.x; i < 64 * 64; i += 256) {
@@ -263,10 +274,21 @@ template <int DMAX>
 int launch_norm_rows(const half_t* x, int ldx, half_t* y, int R, int D, hipStream_t s, const char* what) {
     int g = ceil_div(R, 4);
     g = g > 8192 ? 8192 : g;
-    if (D <= 512) norm_rows_kernel<1><<<g, 256, 0, s>>>(x, ldx, y, R, D);
-    else if (D <= 1024) norm_rows_kernel<2><<<g, 256, 0, s>>>(x, ldx, y, R, D);
-    else if (DMAX <= 2048 || D <= 2048) norm_rows_kernel<4><<<g, 256, 0, s>>>(x, ldx, y, R, D);
-    else if constexpr (DMAX > 2048) norm_rows_kernel<8><<<g, 256, 0, s>>>(x, ldx, y, R, D);
+    if (D <= 512) norm_rows_kernel<1><<<g, 256, 0, s>>>(x, ldx, y, R, D, 0);
+    else if (D <= 1024) norm_rows_kernel<2><<<g, 256, 0, s>>>(x, ldx, y, R, D, 0);
+    else if (DMAX <= 2048 || D <= 2048) norm_rows_kernel<4><<<g, 256, 0, s>>>(x, ldx, y, R, D, 0);
+    else if constexpr (DMAX > 2048) norm_rows_kernel<8><<<g, 256, 0, s>>>(x, ldx, y, R, D, 0);
+    return pclip_check_launch(what);
+}
+// the rows of G operands of R rows each (group g at x + g gsx, G <= 65535) normalised in ONE launch: y dense [G R, D]
+template <int DMAX>
+int launch_norm_rows_grouped(const half_t* x, int ldx, size_t gsx, half_t* y, int R, int D, int G, hipStream_t s, const char* what) {
+    static_assert(DMAX <= 2048, "launch_norm_rows_grouped: NCH <= 4");
+    int g = ceil_div(R, 4);
+    g = g > 8192 ? 8192 : g;
+    if (D <= 512) norm_rows_kernel<1, true><<<dim3(g, G), 256, 0, s>>>(x, ldx, y, R, D, gsx);
+    else if (D <= 1024) norm_rows_kernel<2, true><<<dim3(g, G), 256, 0, s>>>(x, ldx, y, R, D, gsx);
+    else norm_rows_kernel<4, true><<<dim3(g, G), 256, 0, s>>>(x, ldx, y, R, D, gsx);
     return pclip_check_launch(what);
 }
 
@@ -274,7 +296,13 @@ int launch_norm_rows(const half_t* x, int ldx, half_t* y, int R, int D, hipStrea
 // (a template only so that, like transpose_kernel, it is instantiated in the files that call it and pclip_logits.hip carries no transpose kernel)
 template <int TS = 64>
 int launch_transpose(const half_t* x, int ldx, int R, int D, half_t* xT, int ldt, hipStream_t s, const char* what) {
-    transpose_kernel<TS><<<dim3(ldt / 64, D / 64), 256, 0, s>>>(x, ldx, R, xT, ldt);
+    transpose_kernel<TS><<<dim3(ldt / 64, D / 64), 256, 0, s>>>(x, ldx, R, xT, ldt, 0);
+    return pclip_check_launch(what);
+}
+// G of them in one launch (G <= 65535): x_g = x + g gsx, the xT_g [D][ldt] dense one behind the other
+template <int TS = 64>
+int launch_transpose_grouped(const half_t* x, int ldx, size_t gsx, int R, int D, int G, half_t* xT, int ldt, hipStream_t s, const char* what) {
+    transpose_kernel<TS, true><<<dim3(ldt / 64, D / 64, G), 256, 0, s>>>(x, ldx, R, xT, ldt, gsx);
     return pclip_check_launch(what);
 }
 

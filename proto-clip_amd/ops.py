@@ -356,6 +356,97 @@ def cosine_cross_entropy_backward(a, b, scale: float, lse_row, lse_col=None, lab
     return (grads[0] if want_a else None), grads[1], ds
 
 
+def _f16_groups(t: torch.Tensor, what: str):
+    """A checked 3-D fp16 device operand [G, R, D] as the grouped kernels address it: (tensor, row pitch, group stride) in halves.  Taken as it is — a view
+    into a larger buffer included — when the kernel can address it (unit stride along D, row pitch >= D and group stride multiples of 8 halves, 16-byte
+    aligned), copied otherwise."""
+    G, R, D = t.shape
+    bad_cols = D > 1 and t.stride(2) != 1
+    bad_rows = R > 1 and (t.stride(1) < D or t.stride(1) % 8)
+    bad_groups = G > 1 and t.stride(0) % 8
+    if bad_cols or bad_rows or bad_groups or t.data_ptr() % 16:
+        t = t.clone(memory_format=torch.contiguous_format)
+    return t, (t.stride(1) if R > 1 else D), (t.stride(0) if G > 1 else R * D)
+
+
+def _cosine_ce_grouped_args(what, a, b, labels, normalize_a, normalize_b):
+    """The operands of the two grouped cosine cross-entropy calls as the kernels take them: (a, lda, gsa, b, ldb, gsb, G, M, T, D, labels, flags).
+    Types and shapes are checked first, each refusal naming its argument, then the device."""
+    if isinstance(a, torch.Tensor) and a.dim() == 2:
+        a = a.unsqueeze(1)                                                                          # [G, D]: one row per group
+    for name, t in (("a", a), ("b", b)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float16:
+            raise _lib.PclipError(f"{what}: {name}: expected a float16 tensor, got {getattr(t, 'dtype', type(t))}")
+        if t.dim() != 3 or min(t.shape) < 1:
+            raise _lib.PclipError(f"{what}: {name}: expected a non-empty 3-D tensor [G, rows, D], got shape {tuple(t.shape)}")
+    (G, M, D), (Gb, T, Db) = a.shape, b.shape
+    if G != Gb:
+        raise _lib.PclipError(f"{what}: a has {G} groups, b has {Gb}")
+    if D != Db:
+        raise _lib.PclipError(f"{what}: a has {D} columns, b has {Db}")
+    if not isinstance(labels, torch.Tensor) or labels.dtype not in (torch.int32, torch.int64) or tuple(labels.shape) not in ((G, M),) + (((G,),) if M == 1 else ()):
+        raise _lib.PclipError(f"{what}: labels must be an int32 / int64 tensor of shape [G={G}, M={M}], got {getattr(labels, 'dtype', None)} "
+                              f"{tuple(getattr(labels, 'shape', ()))}")
+    for name, t in (("a", a), ("b", b), ("labels", labels)):
+        if not t.is_cuda:
+            raise _lib.PclipError(f"{what}: {name}: expected a device tensor, got a CPU tensor (libpclip has no CPU fallback)")
+    require_cuda(a, b, labels)
+    a, lda, gsa = _f16_groups(a, f"{what}: a")
+    b, ldb, gsb = _f16_groups(b, f"{what}: b")
+    flags = (_lib.CE_NORMALIZE_A if normalize_a else 0) | (_lib.CE_NORMALIZE_B if normalize_b else 0)
+    flags |= _lib.CE_LABELS_I64 if labels.dtype == torch.int64 else 0
+    return a, lda, gsa, b, ldb, gsb, G, M, T, D, labels.contiguous(), flags
+
+
+def cosine_cross_entropy_grouped(a, b, scale: float, labels, normalize_a: bool = False, normalize_b: bool = False):
+    """G independent labelled `cosine_cross_entropy` problems of one shape in one call (pclip_cosine_ce_grouped_f16): a [G, M, D] (or [G, D]: M = 1),
+    b [G, T, D] fp16, labels [G, M] int32 / int64 indexing the rows of the group's own b[g].  Group and row strides are taken from the tensors: a view into
+    a larger buffer is read in place.  Returns (loss [G] fp32 — loss[g] the mean of group g's M terms —, lse_row [G, M] fp32, rows [G, M] fp32, the terms).
+    Group g's numbers are the bits of `cosine_cross_entropy(a[g], b[g], scale, labels[g], ...)`; the number of launches does not depend on G."""
+    a, lda, gsa, b, ldb, gsb, G, M, T, D, labels, flags = _cosine_ce_grouped_args("cosine_cross_entropy_grouped", a, b, labels, normalize_a, normalize_b)
+    dev = a.device
+    lse_row = torch.empty(G, M, dtype=torch.float32, device=dev)
+    rows = torch.empty(G, M, dtype=torch.float32, device=dev)
+    loss = torch.empty(G, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    nws = int(lib.pclip_cosine_ce_grouped_workspace(0, G, M, T, D))
+    ws = _workspace(nws, dev)
+    check(lib.pclip_cosine_ce_grouped_f16(ptr(a), lda, gsa, M, ptr(b), ldb, gsb, T, D, G, float(np.float32(scale)), flags, ptr(labels), ptr(lse_row), ptr(rows),
+                                          ptr(loss), ptr(ws), nws, stream()), "pclip_cosine_ce_grouped_f16")
+    return loss, lse_row, rows
+
+
+def cosine_cross_entropy_grouped_backward(a, b, scale: float, lse_row, labels, normalize_a: bool = False, normalize_b: bool = False, want_a: bool = True,
+                                          want_b: bool = True, want_scale: bool = True, grad: float = 1.0, mean_over: int = None):
+    """The gradients of `cosine_cross_entropy_grouped` from its lse rows, of every group's OWN loss: (dL_g/da [G, M, D] fp32 | None,
+    dL_g/db [G, T, D] fp32 | None, dL_g/dscale [G] fp32 | None) — group by group the bits of `cosine_cross_entropy_backward` on that group alone.
+    grad: the upstream gradient as a number, the same for every group; mean_over: the row count a group's loss was averaged over (default M)."""
+    what = "cosine_cross_entropy_grouped_backward"
+    a, lda, gsa, b, ldb, gsb, G, M, T, D, labels, flags = _cosine_ce_grouped_args(what, a, b, labels, normalize_a, normalize_b)
+    if not isinstance(lse_row, torch.Tensor) or lse_row.dtype != torch.float32 or lse_row.numel() != G * M or not lse_row.is_contiguous():
+        raise _lib.PclipError(f"{what}: lse_row must be a contiguous float32 tensor of G * M = {G * M} entries")
+    require_cuda(a, lse_row)
+    dev = a.device
+    weight = float(grad) / (mean_over or M)
+    lib = _lib.load()
+    nws = int(lib.pclip_cosine_ce_grouped_workspace(1, G, M, T, D))
+    ws = _workspace(nws, dev)
+    ds = torch.empty(G, dtype=torch.float32, device=dev) if want_scale else None
+    walks = [(0, M, want_a or (want_scale and not want_b)), (1, T, want_b)]          # (dscale is a by-product of a gradient walk: of dL/da's if no other runs)
+    grads, ds_left = [], ds
+    for direction, rows, run in walks:
+        if not run:
+            grads.append(None)
+            continue
+        g = torch.empty(G, rows, D, dtype=torch.float32, device=dev)
+        check(lib.pclip_cosine_ce_grouped_backward_f16(ptr(a), lda, gsa, M, ptr(b), ldb, gsb, T, D, G, float(np.float32(scale)), flags, ptr(labels), ptr(lse_row),
+                                                       float(np.float32(weight)), direction, ptr(g), ptr(ds_left), ptr(ws), nws, stream()),
+              "pclip_cosine_ce_grouped_backward_f16")
+        ds_left = None
+        grads.append(g)
+    return (grads[0] if want_a else None), grads[1], ds
+
+
 def _cosine_sigmoid_args(what, a, b, scale, bias, ids_a, ids_b, normalize_a, normalize_b):
     """The operands of the two sigmoid-loss calls as the kernels take them: (a, b, lda, ldb, M, T, D, scale, bias, ids_a, ids_b, flags)."""
     require_cuda(a, b, ids_a, ids_b)

@@ -147,6 +147,17 @@ def clip_logits_loss(features, clip_weights, labels, scale=100., layout=None):
     return pag.cosine_cross_entropy(features, _clip_weight_rows(features, clip_weights, layout, taped=True), scale, labels=labels)
 
 
+def clip_logits_loss_grouped(features, weights, labels, scale=100., normalize_features=False, normalize_weights=False):
+    """`clip_logits_loss` for G classifiers at once, each with its OWN weights (CoCoOp's per-image text rows, the episodes of episodic training): features
+    [G, M, D] (or [G, D]: one sample per group), weights [G, N, D] rows, labels [G, M] into the group's own N classes.  The mean over the groups of the
+    groups' mean cross-entropies, in one grouped launch per pass whatever G (`autograd.cosine_cross_entropy_grouped` gives the [G] vector itself);
+    gradients for the features, the weights and a tensor `scale`.  normalize_*: L2-normalise that side's rows inside the kernel, the gradient chained."""
+    for name, t in (("features", features), ("weights", weights)):
+        if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float16, torch.float32):
+            raise PclipError(f"{name} must be a float16 / float32 tensor")
+    return pag.cosine_cross_entropy_grouped(features, weights, scale, labels, normalize_a=normalize_features, normalize_b=normalize_weights).mean()
+
+
 def clip_contrastive_loss(image_features, text_features, logit_scale):
     """CLIP's symmetric contrastive loss on a batch of matching image / text features [n, D]: both sides L2-normalised, targets on the diagonal,
     1/2 (image -> text + text -> image) cross-entropy over `logit_scale * i' @ t'^T`.  logit_scale is the ALREADY exponentiated scale, a float or a 0-dim

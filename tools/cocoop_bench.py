@@ -10,7 +10,8 @@
 2. One full step, forward plus backward to the five tensors: the real ViT-B/16 text tower (seeded random weights), n_ctx = 4, 1000 class names x B = 1 and 4,
    37 class names x B = 1 and 16.  Against a plain-torch restatement of the same chain with scaled_dot_product_attention (fp16 linears, LayerNorm in fp32,
    QuickGELU, the tower frozen, the same truncated length, one dense [B, N] cross-entropy), with the peak memory of a step above what is resident before it.
-3. The share of the B per-image loss calls in that step: the loss and its backward alone on the step's own text features."""
+3. The share of the loss in that step: the grouped call over the B images and its backward alone on the step's own text features (against the per-image
+   loop it replaced: tools/cosine_ce_grouped_bench.py)."""
 import argparse
 import os
 import statistics
@@ -172,9 +173,7 @@ def step_part(lines, model, N, B, n_ctx, rounds):
 
     def losses_alone():
         t = text.detach().requires_grad_(True)
-        terms = [pag.cosine_cross_entropy(feats[b:b + 1].contiguous(), t[b], scale_t, labels=labels[b:b + 1], normalize_a=True, normalize_b=True)
-                 for b in range(B)]
-        (torch.stack([x.reshape(()) for x in terms]).mean() * scale).backward()
+        (pag.cosine_cross_entropy_grouped(feats.unsqueeze(1), t, scale_t, labels.view(-1, 1), normalize_a=True, normalize_b=True).mean() * scale).backward()
 
     variants = [("step: this library", ours), ("step: plain torch + SDPA", plain)]
     times = alternate(variants, rounds)
@@ -183,7 +182,8 @@ def step_part(lines, model, N, B, n_ctx, rounds):
     lines.pop()
     lt = alternate([("loss", losses_alone)], rounds)["loss"]
     share = statistics.median(lt) / med["step: this library"]
-    lines.append(f"  the {B} per-image loss calls with their backward, alone: {statistics.median(lt):.3f} ms (min {min(lt):.3f}) = {100 * share:.1f} % of the step")
+    lines.append(f"  the loss over the {B} images (one grouped call) with its backward, alone: {statistics.median(lt):.3f} ms (min {min(lt):.3f}) = "
+                 f"{100 * share:.1f} % of the step")
     ours()
     plain()
     lines.append("  ||grad (a) - (b)|| / ||(b)||: " + "  ".join(f"{name} {float((p.grad - q.grad).norm() / q.grad.norm()):.1e}"

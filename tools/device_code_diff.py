@@ -39,6 +39,17 @@ MOVED = {"rows_replace_kernel": ("vpt_replace_kernel",),
          "small_linear_dw_kernel<float>": ("couple_dw_kernel", "metanet_dw_kernel<float>"),
          "small_linear_dw_kernel<half_t>": ("metanet_dw_kernel<half_t>",),
          "small_linear_db_kernel<0>": ("couple_db_kernel", "metanet_db_kernel")}
+# the cosine cross-entropy kernels with a group flag (csrc/pclip_cosine_ce.hip, csrc/pclip_panel_walk.h): the ungrouped AND the grouped instantiation against
+# the kernel's own earlier name — the grouped one is the same walk behind a base offset
+_CE_FORMS = ["ce_fwd_kernel<%s>" % f for f in ("1, 1", "1, 2", "1, 4", "2, 1", "2, 2", "4, 1")]
+_CE_FORMS += ["ce_bwd_kernel<%s>" % f for f in ("1, 1, 8", "1, 2, 8", "1, 4, 8", "2, 1, 16", "2, 2, 16", "4, 1, 32")]
+_CE_FORMS += ["%s<%d>" % (k, n) for k in ("norm_rows_kernel", "ce_norm_backward_kernel") for n in (1, 2, 4, 8)] + ["transpose_kernel<64>"]
+for _f in _CE_FORMS:
+    for _flag in ("false", "true"):
+        MOVED["%s, %s>" % (_f[:-1], _flag)] = (_f,)
+for _f in ("ce_sum_kernel", "ce_sum_chunks_kernel"):
+    for _flag in ("false", "true"):
+        MOVED["%s<%s>" % (_f, _flag)] = (_f,)
 TOTAL_TOL = 0.01
 
 
