@@ -230,6 +230,41 @@ int pclip_cosine_ce_grouped_backward_f16(const void* a, int lda, size_t gsa, int
 /* G times pclip_workspace_bytes(PCLIP_OP_COSINE_CE [backward: _BACKWARD], M, T, D): at G = 1 the plain call's size.  0 for G < 1. */
 size_t pclip_cosine_ce_grouped_workspace(int backward, int G, int M, int T, int D);
 
+/* ---- distillation: KL from a teacher's cosine logits to the student's (both sets of logits are those of clip/model.py:356-370) -------- */
+
+/* s[m, t] = scale * cos_s[m, t] as in pclip_cosine_ce_f16 on (a [M, D], b [T, D]); z[m, t] = tscale * cos_t[m, t], the same on the teacher's own operands
+ * (ta [M, Dt], tb [T, Dt]): its own width Dt, pitches and normalise flags (PCLIP_KD_NORMALIZE_A / _B for a / b, _TA / _TB for ta / tb).  Nothing is rounded
+ * to fp16 on the way to s or z.  With p = softmax_t z[m, :] and q = softmax_t s[m, :],
+ *   row_loss[m] = sum_t p (z - s) - lse_t z[m, :] + lse_t s[m, :]   ( = KL(p || q) ),   loss = (sum_m row_loss[m]) / M, one fixed-order fp64 sum.
+ * No log p is formed: an entry whose p underflows contributes an exact zero.  The value is NOT clamped at zero: a teacher that equals the student gives a
+ * row term within a few units of its rounding error of 0, on either side.  A temperature is the caller's: divide both scales by it and multiply the
+ * backward's weight by its square.  ta == a (with Dt == D) and tb == b are allowed — the same cached features before two classifiers is the common case.
+ * Outputs (fp32, all required): lse_row [M] = lse_t s, tlse_row [M] = lse_t z, row_loss [M], loss [1].  Guarantees:
+ *   two calls give the same bits (no floating-point atomics);
+ *   a row's lse_row, tlse_row and row_loss depend on that row of a and ta and on b, tb and the scales alone — not on M, the other rows, the panel or the grid;
+ *   lse_row has the bits of pclip_cosine_ce_f16's lse_row on (a, b, scale), tlse_row those on (ta, tb, tscale).
+ * Any M, T >= 1; D % 64 == 0, D <= 2048, and the same for Dt independently of D; lda, ldb (>= D) and ldta, ldtb (>= Dt) multiples of 8 halves, 16-byte
+ * aligned bases; scale and tscale finite; ws: pclip_workspace_bytes(PCLIP_OP_COSINE_KD, M, T, max(D, Dt)) (PCLIP_E_WORKSPACE if smaller).  Everything else
+ * is PCLIP_E_INVALID before any launch. */
+int pclip_cosine_kd_f16(const void* a, int lda, int M, const void* b, int ldb, int T, int D, float scale, const void* ta, int ldta, const void* tb, int ldtb,
+                        int Dt, float tscale, int flags, float* lse_row, float* tlse_row, float* row_loss, float* loss, void* ws, size_t ws_bytes,
+                        pclip_stream_t stream);
+/* The gradients of the above for the STUDENT (the teacher receives none), recomputed tile by tile from the two lse vectors of the forward:
+ *   G[m, t] = weight * ( exp(s - lse_row[m]) - exp(z - tlse_row[m]) ),  weight = 1 / M for the mean (times the upstream gradient and a temperature's square);
+ *   direction 0: grad [M, D] fp32 (dense) = dL/da = scale G b', chained in fp32 through the normalisation under PCLIP_KD_NORMALIZE_A;
+ *   direction 1: grad [T, D] fp32 (dense) = dL/db = scale G^T a', chained under PCLIP_KD_NORMALIZE_B.
+ * dscale (nullable, [1] fp32) = sum G o cos_s, from the unrounded tile.  The signed tile q - p in [-1, 1] enters the second matrix product rounded to fp16
+ * as 2^14 (q - p) (unit 2^-11); weight and scale act in fp32.  Deterministic; a row of dL/da depends on that row of a and ta, the class operands, the
+ * scales and weight alone.  Same envelope as the forward, direction 0 or 1, grad 16-byte aligned;
+ * ws: pclip_workspace_bytes(PCLIP_OP_COSINE_KD_BACKWARD, M, T, max(D, Dt)). */
+int pclip_cosine_kd_backward_f16(const void* a, int lda, int M, const void* b, int ldb, int T, int D, float scale, const void* ta, int ldta, const void* tb,
+                                 int ldtb, int Dt, float tscale, int flags, const float* lse_row, const float* tlse_row, float weight, int direction,
+                                 float* grad, float* dscale, void* ws, size_t ws_bytes, pclip_stream_t stream);
+#define PCLIP_KD_NORMALIZE_A 0x1
+#define PCLIP_KD_NORMALIZE_B 0x2
+#define PCLIP_KD_NORMALIZE_TA 0x4
+#define PCLIP_KD_NORMALIZE_TB 0x8
+
 /* ---- the pairwise sigmoid (SigLIP) loss over cosine logits, multi-positive by ids (clip/model.py:356-370 gives the logits) ------------- */
 
 /* x[m, t] = fma(scale, cos[m, t], bias) in fp32, cos = the fp32 matrix-pipe accumulation of a'[m, :] . b'[t, :], one accumulator over k = 0, 32, ... on every
@@ -870,6 +905,8 @@ int pclip_preprocess_u8(const void* const* srcs, const int32_t* desc, int B, int
 #define PCLIP_OP_TIP_BACKWARD 7       /* N = NK, the key rows: the queries transposed, a class per key row, the largest |dL|: O(Q D + NK) */
 #define PCLIP_OP_COSINE_SIGMOID 8          /* Q = M, N = T: the normalised rows of b: O(T D) */
 #define PCLIP_OP_COSINE_SIGMOID_BACKWARD 9 /* Q = M, N = T: the walked operand normalised and transposed, partial panels of a shared walk, per-panel scalars: O(max(M, T) D + panels) */
+#define PCLIP_OP_COSINE_KD 10          /* Q = M, N = T, D = max(D, Dt): both class operands normalised, the cross-entropy forward's own workspace, M labels: O(T D + M) */
+#define PCLIP_OP_COSINE_KD_BACKWARD 11 /* Q = M, N = T, D = max(D, Dt): both walked operands normalised, the student's transposed, partial panels of a shared walk: O(max(M, T) D) */
 size_t pclip_workspace_bytes(int op, int Q, int N, int D);
 
 #ifdef __cplusplus

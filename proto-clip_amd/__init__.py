@@ -13,3 +13,5 @@ from . import maple  # noqa: F401,E402  (multi-modal prompt learning, deep text 
 from .maple import MaPLe, MultiModalPromptLearner, run_maple  # noqa: F401,E402
 from . import cocoop  # noqa: F401,E402  (the image-conditioned context: ConditionalPromptLearner, CoCoOp, run_cocoop)
 from .cocoop import CoCoOp, ConditionalPromptLearner, run_cocoop  # noqa: F401,E402
+from . import prograd  # noqa: F401,E402  (prompt-aligned gradient: CoOp with a KL to the zero-shot classifier and the gradient projection: ProGrad, run_prograd)
+from .prograd import ProGrad, run_prograd  # noqa: F401,E402

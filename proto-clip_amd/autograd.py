@@ -236,6 +236,70 @@ def _f16_operand(t):
     return t if t.dtype == torch.float16 else ops.cast_f16(t.float().contiguous())
 
 
+class CosineKdFn(torch.autograd.Function):
+    """Distillation loss over cosine logits (ops.cosine_kd): mean_m KL(softmax(tscale ta' @ tb'^T / tau) || softmax(scale a' @ b'^T / tau)) tau^2.  Saves the
+    operands and the two lse vectors — nothing of size M T; the backward recomputes both logit tiles (pclip_cosine_kd_backward_f16).  a, b: fp16, or fp32
+    (cast once; the gradient comes back fp32).  scale: a Python float, or a 0-dim tensor that then receives a gradient (its VALUE is read on the host).  The
+    teacher (ta, tb fp16 constants, tscale a number or a constant 0-dim tensor) receives no gradient: `cosine_kd` refuses one that asks for it."""
+
+    @staticmethod
+    def forward(ctx, a, b, scale, ta, tb, tscale, temperature, normalize_a, normalize_b, normalize_ta, normalize_tb):
+        a16, b16 = _f16_operand(a), _f16_operand(b)
+        ta16 = a16 if ta is a else _f16_operand(ta)
+        tb16 = b16 if tb is b else _f16_operand(tb)
+        tau = float(temperature)
+        ctx.scale = float(scale.detach()) if isinstance(scale, torch.Tensor) else float(scale)
+        ctx.tscale = float(tscale.detach()) if isinstance(tscale, torch.Tensor) else float(tscale)
+        ctx.tau = tau
+        ctx.mode = (bool(normalize_a), bool(normalize_b), bool(normalize_ta), bool(normalize_tb))
+        ctx.refs = tuple((t.dtype, t.shape) if isinstance(t, torch.Tensor) else None for t in (a, b, scale))      # what each gradient is cast back to
+        loss, lse_row, tlse_row = ops.cosine_kd(a16, b16, ctx.scale / tau, ta16, tb16, ctx.tscale / tau, *ctx.mode)
+        ctx.same = (ta16 is a16, tb16 is b16)
+        ctx.save_for_backward(a16, b16, None if ctx.same[0] else ta16, None if ctx.same[1] else tb16, lse_row, tlse_row)
+        return loss * (tau * tau) if tau != 1.0 else loss
+
+    @staticmethod
+    def backward(ctx, g):
+        a16, b16, ta16, tb16, lse_row, tlse_row = ctx.saved_tensors
+        ta16 = a16 if ctx.same[0] else ta16
+        tb16 = b16 if ctx.same[1] else tb16
+        need_a, need_b, need_s = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        tau = ctx.tau
+        ga, gb, gs = ops.cosine_kd_backward(a16, b16, ctx.scale / tau, ta16, tb16, ctx.tscale / tau, lse_row, tlse_row, *ctx.mode, want_a=need_a, want_b=need_b,
+                                            want_scale=need_s, grad=tau * tau)
+        g = g.float()
+
+        def cast(t, ref, mul=1.0):
+            if t is None:
+                return None
+            t = (t * g if mul == 1.0 else t * (g * mul)).reshape(ref[1])
+            return ops.cast_f16(t.contiguous()) if ref[0] == torch.float16 else t.to(ref[0])
+        # d/dscale of a function of scale / tau: the kernel's dscale is taken with respect to its own scale argument
+        return (cast(ga, ctx.refs[0]) if need_a else None, cast(gb, ctx.refs[1]) if need_b else None, cast(gs, ctx.refs[2], 1.0 / tau) if need_s else None,
+                None, None, None, None, None, None, None, None)
+
+
+def cosine_kd(a, b, scale, teacher_a, teacher_b, teacher_scale, temperature=1.0, normalize_a=False, normalize_b=False, normalize_teacher_a=False,
+              normalize_teacher_b=False):
+    """The loss of `CosineKdFn` with a tape where one is wanted, the bare forward under torch.no_grad() or for constants.  temperature: both sets of logits
+    are divided by it and the loss multiplied by its square (Hinton's convention: the gradient keeps its size).  A teacher that requires grad is refused."""
+    for name, t in (("teacher_a", teacher_a), ("teacher_b", teacher_b), ("teacher_scale", teacher_scale)):
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise PclipError(f"cosine_kd: {name} requires grad, but the teacher receives no gradient (pass {name}.detach() to say so)")
+    tau = float(temperature)
+    if not (tau > 0.0 and np.isfinite(tau)):
+        raise PclipError(f"cosine_kd: temperature={temperature} must be positive and finite")
+    if wants_grad(a, b, scale if isinstance(scale, torch.Tensor) else None):
+        return CosineKdFn.apply(a, b, scale, teacher_a, teacher_b, teacher_scale, tau, normalize_a, normalize_b, normalize_teacher_a, normalize_teacher_b)
+    a16, b16 = _f16_operand(a.detach()), _f16_operand(b.detach())
+    ta16 = a16 if teacher_a is a else _f16_operand(teacher_a)
+    tb16 = b16 if teacher_b is b else _f16_operand(teacher_b)
+    s = float(scale.detach()) if isinstance(scale, torch.Tensor) else float(scale)
+    ts = float(teacher_scale.detach()) if isinstance(teacher_scale, torch.Tensor) else float(teacher_scale)
+    loss = ops.cosine_kd(a16, b16, s / tau, ta16, tb16, ts / tau, normalize_a, normalize_b, normalize_teacher_a, normalize_teacher_b)[0]
+    return loss * (tau * tau) if tau != 1.0 else loss
+
+
 class GroupedCosineCeFn(torch.autograd.Function):
     """G independent labelled cross-entropies over cosine logits in one call (ops.cosine_cross_entropy_grouped): a [G, M, D] (or [G, D]), b [G, T, D],
     labels [G, M].  Returns the [G] VECTOR of group losses — the caller chooses the reduction — each the bits of `CosineCeFn` on that group alone.

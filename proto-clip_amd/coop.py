@@ -156,6 +156,18 @@ class CoOp(torch.nn.Module):
         """Cross-entropy of logit_scale.exp() * normalise(image_features) @ normalise(text)^T against `labels`; the [Q, N] logits are never written."""
         return pag.cosine_cross_entropy(image_features, self.prompt_learner(), self.logit_scale(), labels=labels, normalize_a=True, normalize_b=True)
 
+    def distill_loss(self, image_features, teacher_weights, teacher_scale=None, temperature=1.0):
+        """KL from a frozen classifier's prediction — `teacher_weights` [N, Et] fp16 rows, e.g. the hand-crafted prompts' text features, read against the same
+        `image_features` when Et is their width — to this model's: mean KL(softmax(teacher logits / tau) || softmax(own logits / tau)) tau^2, both sides
+        L2-normalised in the kernel, neither [Q, N] matrix written (autograd.cosine_kd).  teacher_scale=None: logit_scale's value."""
+        return self._distill(image_features, self.prompt_learner(), teacher_weights, teacher_scale, temperature)
+
+    def _distill(self, image_features, text, teacher_weights, teacher_scale, temperature):
+        scale = self.logit_scale()
+        ts = float(scale.detach()) if teacher_scale is None else teacher_scale
+        return pag.cosine_kd(image_features, text, scale, image_features, teacher_weights, ts, temperature=temperature, normalize_a=True, normalize_b=True,
+                             normalize_teacher_a=True, normalize_teacher_b=True)
+
     def text_rows(self):
         """The learned classifier: L2-normalised text features [N, E] fp16, a constant."""
         with torch.no_grad():

@@ -518,6 +518,8 @@ extern "C" size_t pclip_workspace_bytes(int op, int Q, int N, int D) {
         case PCLIP_OP_TIP_BACKWARD: return pclip_tip_workspace(Q, N, D);
         case PCLIP_OP_COSINE_SIGMOID: return pclip_cosine_sigmoid_workspace(0, Q, N, D);
         case PCLIP_OP_COSINE_SIGMOID_BACKWARD: return pclip_cosine_sigmoid_workspace(1, Q, N, D);
+        case PCLIP_OP_COSINE_KD: return pclip_cosine_kd_workspace(0, Q, N, D);
+        case PCLIP_OP_COSINE_KD_BACKWARD: return pclip_cosine_kd_workspace(1, Q, N, D);
         default: return 0;
     }
 }

@@ -23,6 +23,7 @@ int pclip_check_launch(const char* what);
 size_t pclip_cosine_ce_workspace(int backward, int M, int T, int D);   // pclip_cosine_ce.hip, behind pclip_workspace_bytes
 size_t pclip_tip_workspace(int Q, int NK, int D);                      // pclip_tip.hip, behind pclip_workspace_bytes
 size_t pclip_cosine_sigmoid_workspace(int backward, int M, int T, int D);   // pclip_cosine_sigmoid.hip, behind pclip_workspace_bytes
+size_t pclip_cosine_kd_workspace(int backward, int M, int T, int Dx);       // pclip_cosine_kd.hip, behind pclip_workspace_bytes (Dx = max(D, Dt))
 #define PCLIP_REQUIRE(cond, ...)              \
     do {                                      \
         if (!(cond)) {                        \

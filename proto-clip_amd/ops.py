@@ -356,6 +356,89 @@ def cosine_cross_entropy_backward(a, b, scale: float, lse_row, lse_col=None, lab
     return (grads[0] if want_a else None), grads[1], ds
 
 
+def _cosine_kd_args(what, a, b, scale, ta, tb, tscale, normalize_a, normalize_b, normalize_ta, normalize_tb):
+    """The operands of the two distillation calls as the kernels take them: (a, lda, b, ldb, ta, ldta, tb, ldtb, M, T, D, Dt, scale, tscale, flags).
+    A teacher operand that IS the student's tensor stays that tensor (one checked copy at the most)."""
+    require_cuda(a, b, ta, tb)
+    same_a, same_b = ta is a, tb is b
+    a, b = _f16_rows(a, f"{what}: a"), _f16_rows(b, f"{what}: b")
+    ta = a if same_a else _f16_rows(ta, f"{what}: ta")
+    tb = b if same_b else _f16_rows(tb, f"{what}: tb")
+    (M, D), (T, Db), (Mt, Dt), (Tt, Dtb) = a.shape, b.shape, ta.shape, tb.shape
+    if D != Db:
+        raise _lib.PclipError(f"{what}: a has {D} columns, b has {Db}")
+    if Dt != Dtb:
+        raise _lib.PclipError(f"{what}: ta has {Dt} columns, tb has {Dtb}")
+    if M < 1 or T < 1:
+        raise _lib.PclipError(f"{what}: empty operand (M={M}, T={T})")
+    if Mt != M or Tt != T:
+        raise _lib.PclipError(f"{what}: the teacher's logits are [{Mt}, {Tt}], the student's [{M}, {T}]")
+    scale, tscale = float(np.float32(scale)), float(np.float32(tscale))
+    if not (np.isfinite(scale) and np.isfinite(tscale)):
+        raise _lib.PclipError(f"{what}: scale={scale} and tscale={tscale} must be finite")
+    flags = (_lib.KD_NORMALIZE_A if normalize_a else 0) | (_lib.KD_NORMALIZE_B if normalize_b else 0)
+    flags |= (_lib.KD_NORMALIZE_TA if normalize_ta else 0) | (_lib.KD_NORMALIZE_TB if normalize_tb else 0)
+    ld = lambda t, rows, cols: t.stride(0) if rows > 1 else cols
+    return a, ld(a, M, D), b, ld(b, T, D), ta, ld(ta, M, Dt), tb, ld(tb, T, Dt), M, T, D, Dt, scale, tscale, flags
+
+
+def cosine_kd(a, b, scale: float, ta, tb, tscale: float, normalize_a: bool = False, normalize_b: bool = False, normalize_ta: bool = False,
+              normalize_tb: bool = False, want_rows: bool = False):
+    """Distillation loss over cosine logits without either [M, T] matrix (pclip_cosine_kd_f16): the student's s = scale * a' @ b'^T (a [M, D], b [T, D] fp16)
+    against the teacher's z = tscale * ta' @ tb'^T (ta [M, Dt], tb [T, Dt] fp16, its own width and normalise flags; `ta is a` / `tb is b` are the common case).
+    loss = mean_m KL(softmax z[m, :] || softmax s[m, :]), in fp32 from unrounded logits; it is not clamped at zero (teacher == student gives a value within
+    a few units of its rounding error of 0, on either side).  A temperature is the caller's: divide both scales by it (autograd.cosine_kd does).
+    Returns (loss 0-dim fp32, lse_row [M] fp32, tlse_row [M] fp32) — the lse vectors have the bits of `cosine_cross_entropy`'s on the same operands —
+    and the per-row terms [M] as a fourth value with `want_rows`."""
+    a, lda, b, ldb, ta, ldta, tb, ldtb, M, T, D, Dt, scale, tscale, flags = _cosine_kd_args("cosine_kd", a, b, scale, ta, tb, tscale, normalize_a, normalize_b,
+                                                                                           normalize_ta, normalize_tb)
+    dev = a.device
+    lse_row = torch.empty(M, dtype=torch.float32, device=dev)
+    tlse_row = torch.empty(M, dtype=torch.float32, device=dev)
+    rows = torch.empty(M, dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    nws = _lib.workspace_bytes(_lib.OP_COSINE_KD, M, T, max(D, Dt))
+    ws = _workspace(nws, dev)
+    check(_lib.load().pclip_cosine_kd_f16(ptr(a), lda, M, ptr(b), ldb, T, D, scale, ptr(ta), ldta, ptr(tb), ldtb, Dt, tscale, flags, ptr(lse_row), ptr(tlse_row),
+                                          ptr(rows), ptr(loss), ptr(ws), nws, stream()), "pclip_cosine_kd_f16")
+    return (loss, lse_row, tlse_row, rows) if want_rows else (loss, lse_row, tlse_row)
+
+
+def cosine_kd_backward(a, b, scale: float, ta, tb, tscale: float, lse_row, tlse_row, normalize_a: bool = False, normalize_b: bool = False,
+                       normalize_ta: bool = False, normalize_tb: bool = False, want_a: bool = True, want_b: bool = True, want_scale: bool = True,
+                       grad: float = 1.0, mean_over: int = None):
+    """The student's gradients of `cosine_kd` from its two lse vectors: (dL/da [M, D] fp32 | None, dL/db [T, D] fp32 | None, dL/dscale 0-dim fp32 | None);
+    the teacher receives none.  Logit tiles of both are recomputed; the signed tile softmax(s) - softmax(z) enters the second matrix product rounded to
+    fp16 as 2^14 times itself, the weight and the scale act in fp32; under normalize_a / normalize_b the gradient is chained in fp32 through the
+    normalisation.  grad: the upstream gradient (and a temperature's square) as a number; mean_over: the row count of the mean (default M) — a row of
+    dL/da has the same bits in any batch with the same `grad / mean_over`."""
+    what = "cosine_kd_backward"
+    a, lda, b, ldb, ta, ldta, tb, ldtb, M, T, D, Dt, scale, tscale, flags = _cosine_kd_args(what, a, b, scale, ta, tb, tscale, normalize_a, normalize_b,
+                                                                                           normalize_ta, normalize_tb)
+    require_cuda(lse_row, tlse_row)
+    for name, t in (("lse_row", lse_row), ("tlse_row", tlse_row)):
+        if t is None or t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != M or not t.is_contiguous():
+            raise _lib.PclipError(f"{what}: {name} must be a contiguous float32 tensor of {M} entries")
+    dev = a.device
+    weight = float(grad) / (mean_over or M)
+    nws = _lib.workspace_bytes(_lib.OP_COSINE_KD_BACKWARD, M, T, max(D, Dt))
+    ws = _workspace(nws, dev)
+    ds = torch.empty((), dtype=torch.float32, device=dev) if want_scale else None
+    walks = [(0, M, want_a or (want_scale and not want_b)), (1, T, want_b)]          # (dscale is a by-product of a gradient walk: of dL/da's if no other runs)
+    grads, ds_left = [], ds
+    for direction, rows, run in walks:
+        if not run:
+            grads.append(None)
+            continue
+        g = torch.empty(rows, D, dtype=torch.float32, device=dev)
+        check(_lib.load().pclip_cosine_kd_backward_f16(ptr(a), lda, M, ptr(b), ldb, T, D, scale, ptr(ta), ldta, ptr(tb), ldtb, Dt, tscale, flags, ptr(lse_row),
+                                                       ptr(tlse_row), float(np.float32(weight)), direction, ptr(g), ptr(ds_left), ptr(ws), nws, stream()),
+              "pclip_cosine_kd_backward_f16")
+        ds_left = None
+        grads.append(g)
+    return (grads[0] if want_a else None), grads[1], ds
+
+
 def _f16_groups(t: torch.Tensor, what: str):
     """A checked 3-D fp16 device operand [G, R, D] as the grouped kernels address it: (tensor, row pitch, group stride) in halves.  Taken as it is — a view
     into a larger buffer included — when the kernel can address it (unit stride along D, row pitch >= D and group stride multiples of 8 halves, 16-byte

@@ -158,6 +158,23 @@ def clip_logits_loss_grouped(features, weights, labels, scale=100., normalize_fe
     return pag.cosine_cross_entropy_grouped(features, weights, scale, labels, normalize_a=normalize_features, normalize_b=normalize_weights).mean()
 
 
+def clip_logits_distill_loss(features, clip_weights, teacher_weights, scale=100., teacher_scale=None, temperature=1.0, teacher_features=None, layout=None):
+    """KL from a frozen teacher's zero-shot prediction to the student's, on cached features: mean_q KL(softmax(teacher_scale * tf @ teacher_weights / tau) ||
+    softmax(scale * features @ clip_weights / tau)) tau^2 (ProGrad's and PromptSRC's logit term, CLIP distillation), with gradients for the features, the
+    student's weights and a tensor `scale`; the teacher receives none, and one that requires grad is refused.  teacher_features=None: the same features go
+    to the teacher; teacher_scale=None: the same scale (its value, as a constant).  A teacher of another width takes its own `teacher_features`.  Operands
+    are taken as they are (normalised already); `layout` as in `clip_logits`, for both weight tensors.  Neither [Q, N] matrix is written, and nothing is
+    rounded to fp16 on the way to the loss."""
+    rows = _clip_weight_rows(features, clip_weights, layout, taped=True)
+    tf = features if teacher_features is None else teacher_features
+    trows = _clip_weight_rows(tf, teacher_weights, layout, taped=True)
+    if teacher_scale is None:
+        teacher_scale = float(scale.detach()) if isinstance(scale, torch.Tensor) else float(scale)
+    if teacher_features is None and features.requires_grad:
+        tf = features.detach()                                                  # the caller's own tensor, read as the teacher's constant input
+    return pag.cosine_kd(features, rows, scale, tf, trows, teacher_scale, temperature=temperature)
+
+
 def clip_contrastive_loss(image_features, text_features, logit_scale):
     """CLIP's symmetric contrastive loss on a batch of matching image / text features [n, D]: both sides L2-normalised, targets on the diagonal,
     1/2 (image -> text + text -> image) cross-entropy over `logit_scale * i' @ t'^T`.  logit_scale is the ALREADY exponentiated scale, a float or a 0-dim
