@@ -265,6 +265,33 @@ int pclip_cosine_kd_backward_f16(const void* a, int lda, int M, const void* b, i
 #define PCLIP_KD_NORMALIZE_TA 0x4
 #define PCLIP_KD_NORMALIZE_TB 0x8
 
+/* ---- feature-level regularisers: a normalised tower output against a constant target ------------------------------------------------- */
+
+/* The distance of n = x / ||x|| (x [M, D] fp16, rows ldx apart, the un-normalised tower output of clip/model.py:338-354; the normalisation is that of
+ * clip/model.py:361-362) from a constant t' (t [M, D] fp16, rows ldt apart; t' = t, or t / ||t|| under normalize_t, by the same instruction sequence as n):
+ *   PCLIP_FREG_L1:   rows[m] = sum_d |n_md - t'_md|,   loss = sum_m rows[m] / (M D)     torch: F.l1_loss(x / x.norm(dim=-1, keepdim=True), t', reduction="mean")
+ *   PCLIP_FREG_COS:  rows[m] = 1 - sum_d n_md t'_md,   loss = sum_m rows[m] / M         torch: 1 - F.cosine_similarity(x, t', dim=-1).mean()
+ * n and t' are formed in fp32 from the fp16 rows and NEVER rounded to fp16; every sum has one fixed order (csrc/pclip_feature_reg.hip's header states it and
+ * every rounding point).  Outputs, fp32: loss [1], rows [M], inv_norm [M] = 1 / ||x_m||.  No atomics: two calls give the same bits, and a row's term does
+ * not depend on M, on the row's position or on the grid.  A row of x with zero norm gives NaN in its own term and in the loss, nowhere else.
+ * D % 8 == 0, 8 <= D <= 4096; M >= 0 (M == 0: loss = +0, nothing is launched and rows / inv_norm / x / t are not looked at); ldx, ldt multiples of 8 halves
+ * >= D; x and t 16-byte aligned; ws: pclip_feature_reg_workspace(M) bytes, 0 up to PCLIP_FREG_CHUNK rows (PCLIP_E_WORKSPACE if smaller).  Everything else is
+ * PCLIP_E_INVALID before any launch. */
+int pclip_feature_reg_f16(const void* x, int ldx, const void* t, int ldt, int M, int D, int mode, int normalize_t, float* loss, float* rows, float* inv_norm,
+                          void* ws, size_t ws_bytes, pclip_stream_t stream);
+/* The gradient of the above with respect to x (t is a constant), what torch's autograd chains through l1_loss / cosine_similarity and the division by the
+ * norm: dx [M, D] fp32, dense.  weight = grad / (mean_over D) for L1, grad / mean_over for COS (mean_over = M for the mean above), as
+ * pclip_cosine_ce_backward_f16 takes its weight.  dn = weight sgn(n - t') with sgn(0) = 0 (L1), dn = -weight t' (COS); dx = (dn - n (n . dn)) / ||x||, all
+ * in fp32.  n and t' are recomputed from x and t by the forward's instruction sequence, so the sign is that of the very difference the forward summed.
+ * A row of dx depends on that row of x and t and on weight alone.  Same envelope; dx 16-byte aligned; M == 0 launches nothing. */
+int pclip_feature_reg_backward_f16(const void* x, int ldx, const void* t, int ldt, int M, int D, int mode, int normalize_t, float weight, float* dx,
+                                   pclip_stream_t stream);
+/* Bytes of workspace pclip_feature_reg_f16 needs for M rows: one float per chunk of PCLIP_FREG_CHUNK rows beyond one chunk, else 0. */
+size_t pclip_feature_reg_workspace(int M);
+#define PCLIP_FREG_L1 0
+#define PCLIP_FREG_COS 1
+#define PCLIP_FREG_CHUNK 1024
+
 /* ---- the pairwise sigmoid (SigLIP) loss over cosine logits, multi-positive by ids (clip/model.py:356-370 gives the logits) ------------- */
 
 /* x[m, t] = fma(scale, cos[m, t], bias) in fp32, cos = the fp32 matrix-pipe accumulation of a'[m, :] . b'[t, :], one accumulator over k = 0, 32, ... on every

@@ -15,3 +15,5 @@ from . import cocoop  # noqa: F401,E402  (the image-conditioned context: Conditi
 from .cocoop import CoCoOp, ConditionalPromptLearner, run_cocoop  # noqa: F401,E402
 from . import prograd  # noqa: F401,E402  (prompt-aligned gradient: CoOp with a KL to the zero-shot classifier and the gradient projection: ProGrad, run_prograd)
 from .prograd import ProGrad, run_prograd  # noqa: F401,E402
+from . import promptsrc  # noqa: F401,E402  (self-regulated prompts: independent deep prompts, feature and logit regularisers, Gaussian aggregation: PromptSRC, run_promptsrc)
+from .promptsrc import IndependentPromptLearner, PromptSRC, run_promptsrc  # noqa: F401,E402

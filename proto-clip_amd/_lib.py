@@ -14,6 +14,7 @@ OP_SQDIST, OP_CLASSIFY, OP_ADAPTER_FC, OP_LOGITS, OP_COSINE_CE, OP_COSINE_CE_BAC
 OP_COSINE_SIGMOID, OP_COSINE_SIGMOID_BACKWARD = 8, 9
 OP_COSINE_KD, OP_COSINE_KD_BACKWARD = 10, 11          # sized with D = max(D, Dt)
 KD_NORMALIZE_A, KD_NORMALIZE_B, KD_NORMALIZE_TA, KD_NORMALIZE_TB = 0x1, 0x2, 0x4, 0x8          # flags of pclip_cosine_kd_f16 / pclip_cosine_kd_backward_f16
+FREG_L1, FREG_COS, FREG_CHUNK = 0, 1, 1024          # modes of pclip_feature_reg_f16 / pclip_feature_reg_backward_f16; rows per chunk of the loss's second stage
 LOGITS_NORMALIZE_A, LOGITS_NORMALIZE_B = 0x1, 0x2          # flags of pclip_cosine_logits_f16
 SIG_NORMALIZE_A, SIG_NORMALIZE_B, SIG_IDS_I64 = 0x1, 0x2, 0x8          # flags of pclip_cosine_sigmoid_f16 / pclip_cosine_sigmoid_backward_f16
 CE_NORMALIZE_A, CE_NORMALIZE_B, CE_SYMMETRIC, CE_LABELS_I64 = 0x1, 0x2, 0x4, 0x8          # flags of pclip_cosine_ce_f16 / pclip_cosine_ce_backward_f16
@@ -77,6 +78,9 @@ _SIGS = {
     "pclip_cosine_kd_f16": [_P, c_int, c_int, _P, c_int, c_int, c_int, c_float, _P, c_int, _P, c_int, c_int, c_float, c_int, _P, _P, _P, _P, _P, c_size_t, _P],
     "pclip_cosine_kd_backward_f16": [_P, c_int, c_int, _P, c_int, c_int, c_int, c_float, _P, c_int, _P, c_int, c_int, c_float, c_int, _P, _P, c_float, c_int, _P, _P,
                                      _P, c_size_t, _P],
+    "pclip_feature_reg_f16": [_P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P],
+    "pclip_feature_reg_backward_f16": [_P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P],
+    "pclip_feature_reg_workspace": [c_int],
     "pclip_cosine_sigmoid_f16": [_P, c_int, c_int, _P, c_int, c_int, c_int, c_float, c_float, c_int, _P, _P, _P, _P, _P, c_size_t, _P],
     "pclip_cosine_sigmoid_backward_f16": [_P, c_int, c_int, _P, c_int, c_int, c_int, c_float, c_float, c_int, _P, _P, c_float, c_int, _P, _P, _P, _P, c_size_t, _P],
     "pclip_tip_logits_f16": [_P, c_int, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_float, c_float, c_float, _P, c_int, _P, _P, _P],
@@ -166,7 +170,7 @@ _SIGS = {
     "pclip_preprocess_u8": [_P, _P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, _P, c_int, _P, _P],
     "pclip_workspace_bytes": [c_int, c_int, c_int, c_int],
 }
-_RESTYPES = {"pclip_last_error": c_char_p, "pclip_workspace_bytes": c_size_t, "pclip_gemm_splitk_workspace": c_size_t, "pclip_cosine_ce_grouped_workspace": c_size_t, "pclip_gemm_kernel_launches": c_long}
+_RESTYPES = {"pclip_last_error": c_char_p, "pclip_workspace_bytes": c_size_t, "pclip_gemm_splitk_workspace": c_size_t, "pclip_cosine_ce_grouped_workspace": c_size_t, "pclip_feature_reg_workspace": c_size_t, "pclip_gemm_kernel_launches": c_long}
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
 

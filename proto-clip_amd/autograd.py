@@ -300,6 +300,38 @@ def cosine_kd(a, b, scale, teacher_a, teacher_b, teacher_scale, temperature=1.0,
     return loss * (tau * tau) if tau != 1.0 else loss
 
 
+class FeatureRegFn(torch.autograd.Function):
+    """A feature-level regulariser (ops.feature_reg): the L1 distance ("l1", PromptSRC) or one minus the cosine ("cos", KgCoOp) of the L2-normalised rows of
+    x from a constant target.  Saves x, the target and the inverse norms; the backward is one launch (pclip_feature_reg_backward_f16) that recomputes the
+    normalised rows.  x: fp16, or fp32 (cast once; the gradient comes back fp32).  The target (fp16, or fp32 cast once) receives no gradient:
+    `feature_reg` refuses one that asks for it."""
+
+    @staticmethod
+    def forward(ctx, x, t, mode, normalize_t):
+        x16, t16 = _f16_operand(x), _f16_operand(t)
+        ctx.mode = (str(mode), bool(normalize_t))
+        ctx.ref = (x.dtype, x.shape)
+        loss, inv = ops.feature_reg(x16, t16, *ctx.mode)
+        ctx.save_for_backward(x16, t16, inv)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        x16, t16, inv = ctx.saved_tensors
+        dx = (ops.feature_reg_backward(x16, t16, inv, *ctx.mode) * g.float()).reshape(ctx.ref[1])
+        return (ops.cast_f16(dx.contiguous()) if ctx.ref[0] == torch.float16 else dx.to(ctx.ref[0])), None, None, None
+
+
+def feature_reg(x, t, mode="l1", normalize_t=False):
+    """The loss of `FeatureRegFn` with a tape where one is wanted, the bare forward under torch.no_grad() or for a constant x.  A target that requires grad
+    is refused."""
+    if isinstance(t, torch.Tensor) and t.requires_grad:
+        raise PclipError("feature_reg: t requires grad, but the target receives no gradient (pass t.detach() to say so)")
+    if wants_grad(x):
+        return FeatureRegFn.apply(x, t, mode, normalize_t)
+    return ops.feature_reg(_f16_operand(x.detach()), _f16_operand(t), mode, normalize_t)[0]
+
+
 class GroupedCosineCeFn(torch.autograd.Function):
     """G independent labelled cross-entropies over cosine logits in one call (ops.cosine_cross_entropy_grouped): a [G, M, D] (or [G, D]), b [G, T, D],
     labels [G, M].  Returns the [G] VECTOR of group losses — the caller chooses the reduction — each the bits of `CosineCeFn` on that group alone.

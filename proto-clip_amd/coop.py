@@ -168,6 +168,13 @@ class CoOp(torch.nn.Module):
         return pag.cosine_kd(image_features, text, scale, image_features, teacher_weights, ts, temperature=temperature, normalize_a=True, normalize_b=True,
                              normalize_teacher_a=True, normalize_teacher_b=True)
 
+    def kg_loss(self, image_features, labels, zs_text_features, weight=8.0):
+        """KgCoOp (Yao et al., CVPR 2023): the cross-entropy plus `weight` times 1 - mean cosine of the learned text features to the frozen hand-crafted ones
+        (`zs_text_features` [N, E] fp16, normalised inside the kernel, so either form will do), from ONE `prompt_learner()` forward."""
+        text = self.prompt_learner()
+        ce = pag.cosine_cross_entropy(image_features, text, self.logit_scale(), labels=labels, normalize_a=True, normalize_b=True)
+        return ce + weight * pag.feature_reg(text, zs_text_features, "cos", True)
+
     def text_rows(self):
         """The learned classifier: L2-normalised text features [N, E] fp16, a constant."""
         with torch.no_grad():
@@ -179,19 +186,28 @@ class CoOp(torch.nn.Module):
         return utils.clip_zero_shot(features, self.text_rows(), scale=float(self.logit_scale()), topk=topk, layout="nd")
 
 
-def run_coop(cfg, train_features, train_labels, test_features, test_labels, classnames, clip_model, tokenize=None, tokenized_prompts=None):
+def run_coop(cfg, train_features, train_labels, test_features, test_labels, classnames, clip_model, tokenize=None, tokenized_prompts=None,
+             zs_text_features=None):
     """Train a context on cached features ([Q, D] fp16 and labels, as `pre_load_features` / `build_cache_model` hold them) with CoOp's recipe: SGD on `ctx`,
     learning rate 0.002, momentum 0.9, cosine schedule, batches of 32, cfg['coop_epochs'] epochs, cfg['n_ctx'] context rows (optional keys: 'ctx_init',
     'class_specific', 'coop_lr', 'coop_batch', 'coop_loss_scale', 'seed').  The loss goes through torch's GradScaler (initial scale 1024): the gradient
     stream inside the tower is fp16, and at 1000 classes an unscaled mean loss leaves most of it in fp16's subnormal range (profiles/coop.txt: 23 % gradient
     error unscaled, 0.4 % scaled); `ctx` and its gradient are fp32, so the scaler and the optimizer are torch's own.  Prints the test accuracy before training
-    and after every epoch; returns the trained `CoOp` module (`.results`: the figures)."""
+    and after every epoch; returns the trained `CoOp` module (`.results`: the figures).  With cfg['kg_weight'] the loss is `CoOp.kg_loss` against
+    `zs_text_features` ([N, E] fp16, the frozen hand-crafted text features: KgCoOp, weight 8 upstream); without the key nothing changes."""
     seed = int(cfg.get("seed", 1))
+    kg = cfg.get("kg_weight")
+    if kg is not None and zs_text_features is None:
+        raise PclipError("run_coop: cfg['kg_weight'] needs zs_text_features, the frozen text features [N, E] the context is held to")
     learner = PromptLearner(classnames, clip_model, n_ctx=cfg.get("n_ctx", 16), ctx_init=cfg.get("ctx_init"), class_specific=cfg.get("class_specific", False),
                             tokenize=tokenize, tokenized_prompts=tokenized_prompts, seed=seed)
     model = CoOp(clip_model, learner)
     labels = train_labels.to(train_features.device).long()
-    res, _ = train_prompts("CoOp", learner.parameters(), lambda idx: model.loss(train_features[idx].contiguous(), labels[idx]),
+    if kg is None:
+        loss_at = lambda idx: model.loss(train_features[idx].contiguous(), labels[idx])
+    else:
+        loss_at = lambda idx: model.kg_loss(train_features[idx].contiguous(), labels[idx], zs_text_features, weight=float(kg))
+    res, _ = train_prompts("CoOp", learner.parameters(), loss_at,
                            train_features.shape[0], train_features.device, epochs=int(cfg["coop_epochs"]), batch=int(cfg.get("coop_batch", 32)),
                            lr=cfg.get("coop_lr", 0.002), momentum=0.9, loss_scale=cfg.get("coop_loss_scale", 1024.0), seed=seed,
                            evaluate=lambda: accuracy(model.classify(test_features), test_labels))

@@ -12,8 +12,9 @@ A replaced row passes no gradient to the block below.  The towers are frozen and
 text_blocks=m)` composes with it.  depth = 1 is CoOp's context with a coupled shallow VPT.
 
 Envelope: transformer towers of head dimension 64, fp32 parameters, 1 <= n_ctx <= 16 (the coupling kernel's rows per depth), 1 <= depth <= min(vision
-layers, text layers), L0 + n_ctx <= 288 vision tokens, text width a multiple of 64, context shared by the classes.  Not here: PromptSRC's regularisers, a
-per-class (class-specific) context.  CoCoOp's meta-net (an image-conditioned context) is `cocoop.py`."""
+layers, text layers), L0 + n_ctx <= 288 vision tokens, text width a multiple of 64, context shared by the classes.  Not here: a per-class
+(class-specific) context.  PromptSRC's independent prompts and regularisers are `promptsrc.py`; CoCoOp's meta-net (an image-conditioned context) is
+`cocoop.py`."""
 import torch
 
 from . import autograd as pag
@@ -24,6 +25,39 @@ from .coop import PromptLearner
 from .prompt_train import accuracy, train_prompts
 from .tower import run_tower
 from .vpt import VisualPromptLearner
+
+
+def deep_text_features(who, clip_model, inner, ctx, n_ctx, depth):
+    """[N, E] fp16: the class prompts of `inner` (a coop.PromptLearner: its tokens, EOT check and L_eff) with ctx[0] spliced in, through the text tower with
+    ctx[i] replacing rows 1 .. n_ctx before block i, 1 <= i < depth.  ctx: fp32 [depth, n_ctx, Wt] on the tape.  The text path of `MultiModalPromptLearner`
+    and of `promptsrc.IndependentPromptLearner`, stated once; `who` names the learner in a refusal."""
+    m = clip_model
+    if m._text_stem_opt_in:
+        raise PclipError(f"{who}: the text embeddings have been opted in through unfreeze(stem=...); prompt learning beside a "
+                         "trainable stem is not supported (the context rows are spliced into a frozen embedding)")
+    taped = False
+    if torch.is_grad_enabled():
+        tail = m._text_tape_from()                                         # refuses a trainable embedding in the frozen prefix
+        taped = ctx.requires_grad or tail is not None
+    L = inner.run_length
+    emb16 = m._cache.get("tok", m.token_embedding.weight, lambda t: t.half().contiguous())
+    pos16 = m._cache.get("pos", m.positional_embedding, lambda t: t.half().contiguous())
+    tw = m.text_tower
+    deep = ctx[1:] if depth > 1 else None
+    what = f"{who} (n_ctx={n_ctx}, depth={depth}, {L} tokens per prompt, text tower on the tape from block 0)"
+    with torch.set_grad_enabled(taped):
+        outs = []
+        for i in range(0, inner.n_cls, m.text_chunk):
+            tokens = inner.tokenized_prompts[i:i + m.text_chunk]
+            B = tokens.shape[0]
+            if ops.splitk_active(B) or ops.splitk_active(B * L):
+                raise PclipError(f"{what}: a pass inside ops.low_latency() is not supported (the split-K linears have no backward and the prompted "
+                                 f"tower runs the taped kernel sequence); leave the context (B={B}, L={L})")
+            head = tokens[:, :L].contiguous()
+            x = pag.PromptEmbedFn.apply(ctx[0], tokens, emb16, pos16, n_ctx, L)
+            outs.append(run_tower(tw, x, B, L, (0, False), tw.pick(B, L, x.device, head), what=what, deep=deep,
+                                  deep_off=None if deep is None else 1))
+        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
 
 
 class MultiModalPromptLearner(torch.nn.Module):
@@ -106,34 +140,8 @@ class MultiModalPromptLearner(torch.nn.Module):
 
     def text_features(self):
         """[N, E] fp16: the class prompts with ctx[0] spliced in, through the text tower with ctx[i] replacing rows 1 .. n_ctx before block i."""
-        m, inner = self.clip_model, self._text
         self._check_parameters()
-        if m._text_stem_opt_in:
-            raise PclipError("MultiModalPromptLearner: the text embeddings have been opted in through unfreeze(stem=...); prompt learning beside a "
-                             "trainable stem is not supported (the context rows are spliced into a frozen embedding)")
-        taped = False
-        if torch.is_grad_enabled():
-            tail = m._text_tape_from()                                         # refuses a trainable embedding in the frozen prefix
-            taped = self.ctx.requires_grad or tail is not None
-        L = inner.run_length
-        emb16 = m._cache.get("tok", m.token_embedding.weight, lambda t: t.half().contiguous())
-        pos16 = m._cache.get("pos", m.positional_embedding, lambda t: t.half().contiguous())
-        tw = m.text_tower
-        deep = self.ctx[1:] if self.depth > 1 else None
-        what = f"MultiModalPromptLearner (n_ctx={self.n_ctx}, depth={self.depth}, {L} tokens per prompt, text tower on the tape from block 0)"
-        with torch.set_grad_enabled(taped):
-            outs = []
-            for i in range(0, self.n_cls, m.text_chunk):
-                tokens = inner.tokenized_prompts[i:i + m.text_chunk]
-                B = tokens.shape[0]
-                if ops.splitk_active(B) or ops.splitk_active(B * L):
-                    raise PclipError(f"{what}: a pass inside ops.low_latency() is not supported (the split-K linears have no backward and the prompted "
-                                     f"tower runs the taped kernel sequence); leave the context (B={B}, L={L})")
-                head = tokens[:, :L].contiguous()
-                x = pag.PromptEmbedFn.apply(self.ctx[0], tokens, emb16, pos16, self.n_ctx, L)
-                outs.append(run_tower(tw, x, B, L, (0, False), tw.pick(B, L, x.device, head), what=what, deep=deep,
-                                      deep_off=None if deep is None else 1))
-            return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+        return deep_text_features("MultiModalPromptLearner", self.clip_model, self._text, self.ctx, self.n_ctx, self.depth)
 
     def visual_rows(self):
         """[depth, n_ctx, Wv] fp32: the coupling function of every depth, one launch."""

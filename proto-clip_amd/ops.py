@@ -439,6 +439,69 @@ def cosine_kd_backward(a, b, scale: float, ta, tb, tscale: float, lse_row, tlse_
     return (grads[0] if want_a else None), grads[1], ds
 
 
+_FREG_MODES = {"l1": _lib.FREG_L1, "cos": _lib.FREG_COS, "cosine": _lib.FREG_COS}
+
+
+def _feature_reg_args(what, x, t, mode, normalize_t):
+    """The operands of the two feature-regulariser calls as the kernels take them: (x, ldx, t, ldt, M, D, mode, normalize_t).  Refusals come before any
+    launch; an operand the kernel cannot address in place (a misaligned or oddly strided view) is copied once."""
+    if not isinstance(mode, str) or mode not in _FREG_MODES:
+        raise _lib.PclipError(f"{what}: mode={mode!r} is neither 'l1' nor 'cos'")
+    for name, v in (("x", x), ("t", t)):
+        if not isinstance(v, torch.Tensor) or v.dtype != torch.float16 or v.dim() != 2:
+            raise _lib.PclipError(f"{what}: {name} must be a 2-D float16 tensor, got {getattr(v, 'dtype', type(v))} {tuple(getattr(v, 'shape', ()))}")
+    if x.shape != t.shape:
+        raise _lib.PclipError(f"{what}: x is {tuple(x.shape)}, the target {tuple(t.shape)}")
+    M, D = x.shape
+    if D % 8 or not 8 <= D <= 4096:
+        raise _lib.PclipError(f"{what}: D={D} must be a multiple of 8 in 8..4096")
+    require_cuda(x, t)
+    x, t = _f16_rows(x, f"{what}: x"), _f16_rows(t, f"{what}: t")
+    return x, (x.stride(0) if M > 1 else D), t, (t.stride(0) if M > 1 else D), M, D, _FREG_MODES[mode], 1 if normalize_t else 0
+
+
+def feature_reg(x, t, mode: str = "l1", normalize_t: bool = False, want_rows: bool = False):
+    """The distance of the L2-normalised rows of x [M, D] fp16 (a tower's un-normalised output) from the constant t [M, D] fp16 — as it is, or normalised as x
+    is with `normalize_t` — in one row pass (pclip_feature_reg_f16); row-strided views are read in place.
+      mode "l1":  F.l1_loss(x / x.norm(dim=-1, keepdim=True), t', reduction="mean")       PromptSRC's feature regularisers
+      mode "cos": 1 - F.cosine_similarity(x, t', dim=-1).mean()                           KgCoOp's
+    The normalised rows stay fp32 (torch on fp16 tensors rounds them to fp16 before the loss).  A zero row of x gives NaN, in its own term and the loss only.
+    Returns (loss 0-dim fp32, inv_norm [M] fp32 = 1 / ||x_m||), and the per-row terms [M] fp32 as a third value with `want_rows`.  M == 0: +0, no launch."""
+    x, ldx, t, ldt, M, D, mode, nt = _feature_reg_args("feature_reg", x, t, mode, normalize_t)
+    dev = x.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    rows = torch.empty(M, dtype=torch.float32, device=dev)
+    inv = torch.empty(M, dtype=torch.float32, device=dev)
+    nws = int(_lib.load().pclip_feature_reg_workspace(M))
+    ws = _workspace(nws, dev) if nws else None
+    check(_lib.load().pclip_feature_reg_f16(ptr(x), ldx, ptr(t), ldt, M, D, mode, nt, ptr(loss), ptr(rows), ptr(inv), ptr(ws), nws, stream()),
+          "pclip_feature_reg_f16")
+    return (loss, inv, rows) if want_rows else (loss, inv)
+
+
+def feature_reg_backward(x, t, inv_norm, mode: str, normalize_t: bool, grad: float = 1.0, mean_over: int = None):
+    """The gradient of `feature_reg` with respect to x: [M, D] fp32 (the target is a constant).  dn = w sgn(n - t') with sgn(0) = 0 ("l1", w = grad /
+    (mean_over D)) or -w t' ("cos", w = grad / mean_over), dx = (dn - n (n . dn)) / ||x||, all fp32; n and t' are recomputed from x and t by the forward's
+    instruction sequence.  inv_norm: the forward's [M] vector — it identifies the forward this belongs to and is checked, the kernel recomputes its bits.
+    grad: the upstream gradient as a number; mean_over: the row count of the mean (default M) — a row of dx has the same bits in any batch with the same
+    grad / mean_over."""
+    what = "feature_reg_backward"
+    x, ldx, t, ldt, M, D, mode, nt = _feature_reg_args(what, x, t, mode, normalize_t)
+    if not isinstance(inv_norm, torch.Tensor) or inv_norm.dtype != torch.float32 or inv_norm.dim() != 1 or inv_norm.shape[0] != M:
+        raise _lib.PclipError(f"{what}: inv_norm must be the forward's float32 vector of {M} entries")
+    require_cuda(x, inv_norm)
+    over = M if mean_over is None else int(mean_over)
+    if over < 1 and M > 0:
+        raise _lib.PclipError(f"{what}: mean_over={mean_over} must be positive")
+    dx = torch.empty(M, D, dtype=torch.float32, device=x.device)
+    if M == 0:
+        return dx
+    weight = float(grad) / (over * D if mode == _lib.FREG_L1 else over)
+    check(_lib.load().pclip_feature_reg_backward_f16(ptr(x), ldx, ptr(t), ldt, M, D, mode, nt, float(np.float32(weight)), ptr(dx), stream()),
+          "pclip_feature_reg_backward_f16")
+    return dx
+
+
 def _f16_groups(t: torch.Tensor, what: str):
     """A checked 3-D fp16 device operand [G, R, D] as the grouped kernels address it: (tensor, row pitch, group stride) in halves.  Taken as it is — a view
     into a larger buffer included — when the kernel can address it (unit stride along D, row pitch >= D and group stride multiples of 8 halves, 16-byte

@@ -175,6 +175,19 @@ def clip_logits_distill_loss(features, clip_weights, teacher_weights, scale=100.
     return pag.cosine_kd(features, rows, scale, tf, trows, teacher_scale, temperature=temperature)
 
 
+def clip_feature_l1_loss(features, target, normalize_target=False):
+    """PromptSRC's feature regulariser: F.l1_loss(features / features.norm(dim=-1, keepdim=True), target', reduction="mean") on [M, D] tower outputs, with a
+    gradient for `features`; target' is `target` as given, or normalised the same way with `normalize_target`.  One launch each way
+    (autograd.feature_reg); the normalised rows stay fp32.  The target is a constant: one that requires grad is refused."""
+    return pag.feature_reg(features, target, "l1", normalize_target)
+
+
+def clip_feature_cosine_loss(features, target, normalize_target=False):
+    """KgCoOp's regulariser: 1 - mean(cosine_similarity(features, target')) on [M, D] tower outputs, with a gradient for `features`; target' is `target` as
+    given (normalised already), or normalised in the kernel with `normalize_target`.  The target is a constant: one that requires grad is refused."""
+    return pag.feature_reg(features, target, "cos", normalize_target)
+
+
 def clip_contrastive_loss(image_features, text_features, logit_scale):
     """CLIP's symmetric contrastive loss on a batch of matching image / text features [n, D]: both sides L2-normalised, targets on the diagonal,
     1/2 (image -> text + text -> image) cross-entropy over `logit_scale * i' @ t'^T`.  logit_scale is the ALREADY exponentiated scale, a float or a 0-dim
